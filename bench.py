@@ -30,7 +30,16 @@ run's executed half-shot iterations and divided by this run's kernel time (HIP
 events on the launch stream). The HBM figures (measured PMC bytes, and
 SURVEY.md §8d's algorithmic streaming model) are reported beside it.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+A plain run sets up, warms up, times the `--steps` steps and prints the result
+line (the roofline is priced from the timed steps' own HIP events and takes no
+run of its own). `--full` adds what needs runs of its own: the CPU baselines
+(`cpu_baseline`), the same workload through the HBM-resident kernel
+(`hbm_streaming`), the end-to-end configs[3] / configs[4] legs (`simulate`)
+and the NumPy parity pins (`parity_pin`). `--dump-outputs DIR` writes what the
+last timed step decoded as DIR/<name>.npy (dump_outputs); the inputs are
+seeded, so the same arguments give the same inputs in every run.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--full] [--dump-outputs DIR]
                        [--code C] [--algo MS|BP] [--schedule F|L|S] [--p P] [--iters I]
 """
 import argparse
@@ -73,16 +82,25 @@ def parse(argv=None):
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--io", default="bits", choices=["bits", "bytes"],
                     help="syndrome / hard-decision format in HBM: bit-packed 64-bit words (default) or bytes")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the CPU baselines (--cpu-seconds), the HBM-resident leg "
+                         "(--hbm-leg) and the end-to-end legs (--sim-legs); a plain run sets up, warms up, "
+                         "times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step decoded as DIR/<name>.npy (float32 / float64): per "
+                         "half the iteration counts and flags of every shot and the hard decisions of a "
+                         "fixed seeded sample of shots")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="bounded CPU-baseline sample per leg (0 disables)")
+                    help="--full: bounded CPU-baseline sample per leg (0 disables)")
     ap.add_argument("--path", default="auto", choices=["auto", "hbm"],
                     help="hbm: decode through the HBM-resident kernel (library option force_hbm) in the timed region")
     ap.add_argument("--hbm-leg", type=int, default=1,
-                    help="N=1: also time the same workload through the HBM-resident kernel (hbm_streaming field)")
+                    help="--full, N=1: also time the same workload through the HBM-resident kernel "
+                         "(hbm_streaming field)")
     ap.add_argument("--worklog", default=None,
                     help="write per-launch work (kernel, half-shots, iterations) as JSON (profiling)")
     ap.add_argument("--sim-legs", default="3,4",
-                    help="end-to-end legs after the headline, comma-separated BASELINE.json config indices "
+                    help="--full: end-to-end legs after the headline, comma-separated BASELINE.json config indices "
                          "(3: LP118_2 MS-L + OSD-0 at p = 0.1, strong and per-rank; 4: LP118_2 BP-L, the "
                          "p-sweep [0.01, 0.02, 0.05, 0.1] through simulate), '' for none")
     ap.add_argument("--sim-shots", type=int, default=1 << 20,
@@ -532,6 +550,40 @@ def sim_legs(args, dist, world):
 
 
 # ---------------------------------------------------------------------------
+# --dump-outputs: what the last timed step decoded
+# ---------------------------------------------------------------------------
+DUMP_SAMPLE = 4096             # shots whose hard decisions are written (all of them up to this batch size)
+
+
+def dump_outputs(path, results, ns, bits, rank=0, world=1):
+    """Write one step's DecodeResults (X half, Z half) as float32 .npy files
+    under `path`: <half>_iters and <half>_flags for every shot (batches past
+    2^20: for the sampled shots), <half>_ehat ([shots, n] 0/1, unpacked when
+    bit-packed) for the shots listed in sample_shots (float64): a fixed seeded
+    choice of DUMP_SAMPLE shots, the same from run to run, so that two builds
+    compare output for output. (2^20 shots per half: 2 x 8 MiB of iters +
+    flags, 2 x 4096 x n x 4 B of hard decisions; under 64 MB for every bundled
+    code.) With more than one rank each prefixes its files rank<r>_."""
+    import torch
+    from qldpcsim_amd import decoders
+    os.makedirs(path, exist_ok=True)
+    pre = f"rank{rank}_" if world > 1 else ""
+    B = results[0].iters.shape[0]
+    pick = np.sort(np.random.default_rng(20251226).choice(B, min(B, DUMP_SAMPLE), replace=False))
+    np.save(os.path.join(path, pre + "sample_shots.npy"), pick.astype(np.float64))
+    idx = torch.as_tensor(pick, device=results[0].iters.device)
+    for half, r, n in zip("xz", results, ns):
+        e = r.ehat.index_select(0, idx)
+        if bits:
+            e = decoders.unpack_bits(e, n)
+        it, fl = r.iters, r.flags
+        if B > 1 << 20:
+            it, fl = it.index_select(0, idx), fl.index_select(0, idx)
+        for name, t in (("ehat", e), ("iters", it), ("flags", fl)):
+            np.save(os.path.join(path, f"{pre}{half}_{name}.npy"), t.to(torch.float32).cpu().numpy())
+
+
+# ---------------------------------------------------------------------------
 # one rank
 # ---------------------------------------------------------------------------
 def run_rank(args, rank, world, local):
@@ -546,7 +598,7 @@ def run_rank(args, rank, world, local):
         raise SystemExit(f"bench.py: rank {rank} has local rank {local} but only {ndev} device(s) are "
                          "visible (one GPU per rank; QLDPC_BENCH_BACKEND=gloo to rehearse on shared devices)")
     cpu = None
-    if world == 1 and rank == 0 and args.cpu_seconds > 0:
+    if args.full and world == 1 and rank == 0 and args.cpu_seconds > 0:
         cpu = cpu_baselines(args)          # before the GPU is touched (spawned pool)
     dev = torch.device("cuda", local % ndev)
     torch.cuda.set_device(dev)
@@ -617,7 +669,8 @@ def run_rank(args, rank, world, local):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        for r in step():
+        last = step()
+        for r in last:
             iters_sum += r.iters.sum(dtype=torch.int64)
     torch.cuda.synchronize()
     if world > 1:
@@ -625,6 +678,8 @@ def run_rank(args, rank, world, local):
     elapsed = time.perf_counter() - t0
     kern_ms, launches = _lib.timing_read()
     _lib.timing_enable(False)
+    if args.dump_outputs:                                  # before any later leg reuses the buffers
+        dump_outputs(args.dump_outputs, last, [H.shape[1] for H, _, _, _ in halves], bits, rank, world)
     if world > 1:
         tdev = dev if backend == "nccl" else torch.device("cpu")
         t = torch.tensor([elapsed], dtype=torch.float64, device=tdev)
@@ -656,7 +711,7 @@ def run_rank(args, rank, world, local):
         pass
 
     hbm_leg = None
-    if world == 1 and args.hbm_leg and not args.worklog and args.path != "hbm":
+    if args.full and world == 1 and args.hbm_leg and not args.worklog and args.path != "hbm":
         hbm_leg = hbm_streaming_leg(halves, outs, prior, args, B, bits, algo_launch, dev)
 
     sched_name = {"F": "flooding", "L": "layered", "S": "serial"}[args.schedule]
@@ -688,11 +743,12 @@ def run_rank(args, rank, world, local):
                            "no data-path collective",
         },
         "roofline": roof,
-        "parity_pin": {k: v for k, v in decoders.parity_pins().items()},
     }
+    if args.full:
+        out["parity_pin"] = {k: v for k, v in decoders.parity_pins().items()}
     if hbm_leg is not None:
         out["hbm_streaming"] = hbm_leg
-    if args.sim_legs.strip() and not args.worklog:
+    if args.full and args.sim_legs.strip() and not args.worklog:
         out["simulate"] = sim_legs(args, dist if world > 1 else None, world)
     if cpu is not None:
         out["cpu_baseline"] = cpu

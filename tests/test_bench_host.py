@@ -79,6 +79,50 @@ def test_no_device_fails_loudly():
     assert r.returncode != 0 and "no HIP device" in r.stderr
 
 
+def test_full_is_off_by_default_and_keeps_the_leg_options():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 3)
+    a = bench.parse(["--full", "--dump-outputs", "d", "--cpu-seconds", "1", "--sim-legs", "3", "--hbm-leg", "0"])
+    assert a.full is True and a.dump_outputs == "d" and (a.cpu_seconds, a.sim_legs, a.hbm_leg) == (1.0, "3", 0)
+
+
+def test_dump_outputs_writes_float32_and_a_fixed_sample(tmp_path):
+    """dump_outputs on host tensors: iterations and flags of every shot, the
+    hard decisions (bit-packed or bytes) of the same seeded, sorted sample of
+    shots in every call, all as float32; ranks of a larger world prefix theirs."""
+    import torch
+    from qldpcsim_amd import decoders
+    rng = np.random.default_rng(5)
+    B, ns = bench.DUMP_SAMPLE + 37, (70, 129)          # n not a multiple of 64; more shots than the sample
+    e = [rng.integers(0, 2, (B, n), dtype=np.uint8) for n in ns]
+    it = [rng.integers(1, 51, B, dtype=np.int32) for _ in ns]
+    fl = [rng.integers(0, 4, B, dtype=np.int32) for _ in ns]
+    for bits, sub in ((True, "bits"), (False, "bytes")):
+        res = [decoders.DecodeResult(decoders.pack_bits(torch.as_tensor(x)) if bits else torch.as_tensor(x),
+                                     torch.as_tensor(i), None, torch.as_tensor(f)) for x, i, f in zip(e, it, fl)]
+        bench.dump_outputs(str(tmp_path / sub), res, ns, bits)
+        got = {f[:-4]: np.load(tmp_path / sub / f) for f in os.listdir(tmp_path / sub)}
+        pick = got.pop("sample_shots")
+        assert pick.dtype == np.float64 and len(pick) == bench.DUMP_SAMPLE and np.all(np.diff(pick) > 0)
+        pick = pick.astype(np.int64)
+        assert set(got) == {h + "_" + k for h in "xz" for k in ("ehat", "iters", "flags")}
+        assert all(v.dtype == np.float32 for v in got.values())
+        for h, x, i, f in zip("xz", e, it, fl):
+            assert np.array_equal(got[h + "_ehat"], x[pick]) and np.array_equal(got[h + "_iters"], i)
+            assert np.array_equal(got[h + "_flags"], f)
+    assert np.array_equal(np.load(tmp_path / "bits" / "sample_shots.npy"),
+                          np.load(tmp_path / "bytes" / "sample_shots.npy"))
+    bench.dump_outputs(str(tmp_path / "r"), res, ns, False, rank=1, world=2)
+    assert sorted(os.listdir(tmp_path / "r"))[0] == "rank1_sample_shots.npy" and len(os.listdir(tmp_path / "r")) == 7
+    # past 2^20 shots the per-shot arrays are sampled too (the 64 MB cap)
+    B = (1 << 20) + 1
+    big = decoders.DecodeResult(torch.zeros((B, 3), dtype=torch.uint8), torch.arange(B, dtype=torch.int32), None,
+                                torch.zeros(B, dtype=torch.int32))
+    bench.dump_outputs(str(tmp_path / "big"), [big, big], (3, 3), False)
+    assert np.array_equal(np.load(tmp_path / "big" / "z_iters.npy"), np.load(tmp_path / "big" / "sample_shots.npy"))
+    assert np.load(tmp_path / "big" / "x_flags.npy").shape == (bench.DUMP_SAMPLE,)
+
+
 def test_find_profile_matches_the_workload(tmp_path, monkeypatch):
     """Two entries of one kernel build (same machine-code hash) profiled on
     different workloads: the roofline takes the counters of its own workload

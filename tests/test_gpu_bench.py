@@ -1,6 +1,7 @@
 """bench.py's contract on the GPU: one JSON line with the driver's keys, the
-roofline (on-chip bound priced from the committed counter profile) and
-CPU-baseline objects, and the multi-rank paths: spawned by `--gpus N` itself,
+roofline (on-chip bound priced from the committed counter profile), under
+`--full` the CPU-baseline, HBM-leg and end-to-end objects, a plain run's lean
+line and `--dump-outputs`, and the multi-rank paths: spawned by `--gpus N` itself,
 and launched by torch.distributed.run as the driver does. On this one-GPU box
 two ranks share the device over gloo (QLDPC_BENCH_BACKEND); with RCCL,
 `--gpus 2` must refuse to run."""
@@ -31,7 +32,8 @@ def _bench(*args, env=None, timeout=110):
 
 
 def test_bench_single_gpu_line():
-    r = _bench("--steps", "2", "--warmup", "1", "--batch", "65536", "--cpu-seconds", "1", "--sim-shots", "65536")
+    r = _bench("--full", "--steps", "2", "--warmup", "1", "--batch", "65536", "--cpu-seconds", "1",
+               "--sim-shots", "65536")
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)
     sim = d["simulate"]                                        # the configs[3] / configs[4] legs
@@ -65,6 +67,41 @@ def test_bench_single_gpu_line():
     assert 0 < hs["frac"] < 1 and hs["peak_gbs"] == 8000.0
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """Without --full the line is the headline alone (no CPU baseline, HBM leg,
+    end-to-end legs or parity pins), --steps is the number of timed steps, and
+    --dump-outputs writes what the last timed step decoded: float32 arrays that
+    equal a decode of the same seeded syndromes made here."""
+    import numpy as np
+    import torch
+    from qldpcsim_amd import codes, decoders
+    B = 8192
+    r = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(B),
+               "--dump-outputs", str(tmp_path / "o"))
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _last_json(r.stdout)
+    assert KEYS <= set(d) and not {"cpu_baseline", "hbm_streaming", "simulate", "parity_pin"} & set(d)
+    assert d["steps"] == 3 and d["roofline"]["launches"] == 6 and d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(B / (d["ms_per_step"] * 1e-3), rel=1e-9)
+    got = {f[:-4]: np.load(tmp_path / "o" / f) for f in sorted(os.listdir(tmp_path / "o"))}
+    assert set(got) == {"sample_shots", "x_ehat", "x_iters", "x_flags", "z_ehat", "z_iters", "z_flags"}
+    assert sum(v.nbytes for v in got.values()) <= 64e6
+    shots = got.pop("sample_shots")
+    assert shots.dtype == np.float64 and all(v.dtype == np.float32 for v in got.values())
+    pick = shots.astype(np.int64)
+    assert len(pick) == 4096 and np.all(np.diff(pick) > 0) and 0 <= pick[0] and pick[-1] < B
+    # the benchmark's inputs: seeded on the device, X half (Hz) first
+    Hx, Hz = codes.load_code("LP118_0")
+    g = torch.Generator(device="cuda:0").manual_seed(20251226)
+    for half, H in (("x", Hz), ("z", Hx)):
+        syn = torch.randint(0, 2, (B, H.shape[0]), dtype=torch.uint8, device="cuda:0", generator=g)
+        want = decoders.decode_batch(H, syn, 0.05 / 3, 50, algo="MS")
+        assert got[half + "_ehat"].shape == (4096, H.shape[1])
+        assert np.array_equal(got[half + "_ehat"], want.ehat.cpu().numpy()[pick])
+        assert np.array_equal(got[half + "_iters"], want.iters.cpu().numpy())
+        assert np.array_equal(got[half + "_flags"], want.flags.cpu().numpy())
+
+
 def test_bench_hbm_path_line():
     """--path hbm times the HBM-resident kernel as the main leg: same workload,
     its roofline includes the measured-HBM unit (bound hbm when the committed
@@ -93,7 +130,7 @@ def test_bench_layered_channel_line():
 def test_bench_spawns_ranks_itself_over_gloo():
     env = dict(os.environ, QLDPC_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
-    r = _bench("--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "16384", "--sim-legs", "3",
+    r = _bench("--full", "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "16384", "--sim-legs", "3",
                "--sim-shots", "32768", env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)
@@ -122,7 +159,7 @@ def test_bench_refuses_more_ranks_than_gpus_over_rccl():
 def test_bench_two_ranks_share_gpu_over_gloo_torchrun():
     env = dict(os.environ, QLDPC_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                        "--master-addr", "127.0.0.1", "--master-port", "29531", "bench.py", "--gpus", "2",
+                        "--master-addr", "127.0.0.1", "--master-port", "29531", "bench.py", "--full", "--gpus", "2",
                         "--steps", "1", "--warmup", "1", "--batch", "16384", "--sim-legs", "3", "--sim-shots",
                         "16384"],
                        cwd=ROOT, capture_output=True, text=True, timeout=110, env=env)

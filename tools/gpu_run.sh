@@ -4,7 +4,7 @@
 #   tests          full `pytest -m gpu`                       -> gpurun_out/TAG_pytest_gpu.log
 #   parity         decoder parity subset (parity, bits, osd)  -> gpurun_out/TAG_parity.log
 #   smoke          __graft_entry__.smoke()                    -> gpurun_out/TAG_smoke.log
-#   bench          bench.py --steps 20 --warmup 5 (headline)  -> gpurun_out/TAG_bench.log
+#   bench          bench.py --full --steps 20 --warmup 5 (headline and every leg) -> TAG_bench.log in the output folder
 #   bench-cfg      bench.py on the configs[2]-[4] decoders    -> gpurun_out/TAG_bench_cfg.jsonl
 #   roof-decoders  counter profile (tools/gpu_profile_roofline.sh) of the configs[2]-[4] decoders
 #   roof-bp / roof-msl  counter profiles of the BP decoders / the layered MS decoder only
@@ -66,7 +66,7 @@ for step in "$@"; do
       tail -2 $L ;;
     bench)
       L=$O/${TAG}_bench.log
-      timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $L 2>&1 || fail $step $? $L
+      timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $L 2>&1 || fail $step $? $L
       tail -1 $L | cut -c1-300 ;;
     bench-cfg)
       L=$O/${TAG}_bench_cfg.jsonl
