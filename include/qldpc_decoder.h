@@ -19,8 +19,27 @@
  *    QLDPC_E* code; qldpc_last_error() gives a message (thread-local).
  *  - "d_" pointers are device (HBM) pointers; "h_" pointers are host memory.
  *  - `stream` is a hipStream_t passed as void* (NULL = the null stream).
- *    Device entry points are asynchronous on that stream and do no
- *    allocation, copy or synchronisation (hipGraph-capturable).
+ *    Device entry points are asynchronous on that stream. In the steady state
+ *    they do no allocation, copy or synchronisation (hipGraph-capturable),
+ *    with these exceptions:
+ *     - the first decode of a (schedule, algo) after creation or after a
+ *       qldpc_set_option queries the device (occupancy) to build its launch
+ *       plan; no allocation, no synchronisation;
+ *     - a decode that takes the HBM-resident kernel (codes past the LDS
+ *       kernels, option force_hbm) grows the schedule's workspace when the
+ *       batch needs more tiles than it holds: hipMemGetInfo, then a wait for
+ *       the last launch that used the old workspace, hipFree and hipMalloc.
+ *       It never shrinks; qldpc_schedule_release_workspace frees it;
+ *     - the GPU OSD whose working matrix lives in global memory (m > 1024,
+ *       n > 2111 or option osd_hbm) takes its scratch with hipMallocAsync /
+ *       hipFreeAsync on `stream`, every call;
+ *     - the first OSD call for a code builds rank(H) and its column
+ *       bit-vectors on the host, and the first GPU OSD on a device allocates
+ *       and zeroes a small per-device ticket array (hipMalloc, hipMemset);
+ *     - option osd_prof synchronises `stream` and copies counters, every call.
+ *  - Decodes of one schedule take their half-shot queue counter from a ring
+ *    of 64 slots: at most 64 launches of one schedule may be in flight at
+ *    once across all streams.
  *  - Results are bit-exact with the reference for MS (hard decisions,
  *    iteration counts, float64 posteriors) and for BP,
  *    whose tanh / arctanh / log restate the NumPy 2.2.6 / SVML functions the

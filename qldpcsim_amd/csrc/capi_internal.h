@@ -1,0 +1,256 @@
+// capi_internal.h — private to the host translation units of the C ABI
+// (capi*.cpp): errors, options, owning device buffers, and the definitions of
+// qldpc_code / qldpc_schedule. Nothing declared in namespace capi is exported.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cstdint>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/qldpc_decoder.h"
+#include "decoder_kernels.h"
+#include "hbm_kernels.h"
+
+#pragma GCC visibility push(hidden)
+namespace capi {
+
+// ---------------------------------------------------------------------------
+// errors (capi.cpp)
+// ---------------------------------------------------------------------------
+extern thread_local std::string g_err;
+int fail(int code, const char* fmt, ...);
+
+#define HIP_TRY(expr)                                                                       \
+  do {                                                                                      \
+    hipError_t _e = (expr);                                                                 \
+    if (_e != hipSuccess)                                                                   \
+      return capi::fail(QLDPC_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e),  \
+                        __FILE__, __LINE__);                                                \
+  } while (0)
+
+// ---------------------------------------------------------------------------
+// options (include/qldpc_decoder.h; capi.cpp): read at launch, never from the
+// environment; `gen` changes with every set so cached launch plans are rebuilt
+// ---------------------------------------------------------------------------
+struct Options {
+  std::atomic<int64_t> force_hbm{0}, flood_generic{0}, layered_generic{0}, ms_lanes_per_check{0}, bp_wave{0},
+      bp_lg{1}, bp_team_w{0}, static_sched{0}, waves_per_wg{0}, wg_per_cu{0}, osd_column{0}, osd_tickets{1},
+      osd_prof{0}, osd_hbm{0};
+  std::atomic<uint32_t> gen{1};
+};
+extern Options g_opt;
+inline int64_t opt(std::atomic<int64_t> Options::*slot) { return (g_opt.*slot).load(std::memory_order_relaxed); }
+
+// ---------------------------------------------------------------------------
+// Owning device buffer (kPinned: page-locked host memory instead). Move-only;
+// freed by the destructor, so a create that fails half way leaks nothing.
+// ---------------------------------------------------------------------------
+template <typename T, bool kPinned = false>
+struct DevBuf {
+  T* p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    std::swap(p, o.p);
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  void reset() {
+    if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+  }
+  hipError_t alloc(size_t count) {
+    reset();
+    return kPinned ? hipHostMalloc((void**)&p, sizeof(T) * count) : hipMalloc((void**)&p, sizeof(T) * count);
+  }
+  // an empty table still gets one element, so its pointer is never null
+  hipError_t upload(const std::vector<T>& h) {
+    hipError_t e = alloc(std::max<size_t>(h.size(), 1));
+    if (e == hipSuccess && !h.empty()) e = hipMemcpy(p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice);
+    return e;
+  }
+  operator T*() const { return p; }
+};
+template <typename T>
+using PinBuf = DevBuf<T, true>;
+
+inline int align16(int x) { return (x + 15) & ~15; }
+
+// ---------------------------------------------------------------------------
+// One table image of a schedule: the bytes a kernel family reads its graph
+// tables from, and where each table starts, named as DecodeArgs names them.
+// A family that gives a DecodeArgs field another meaning says so where its
+// image is built (capi_schedule.cpp); fields it does not read keep the
+// generic image's values.
+// ---------------------------------------------------------------------------
+struct TableOffsets {  // DecodeArgs::off_<name>
+  int cn_tab = 0, row_ptr = 0, vn_ptr = 0, vn_chk = 0, lay_ptr = 0, lay_rows = 0, adj_ptr = 0, adj_vars = 0,
+      chunk_dmax = 0;
+};
+struct TableImage {
+  std::vector<uint8_t> bytes;      // host copy
+  DevBuf<unsigned char> dev;       // device copy (DecodeArgs::blob)
+  int lds_bytes = 0;               // bytes [lds_skip, lds_skip + lds_bytes) are staged into LDS
+  int lds_skip = 0;
+  TableOffsets off;
+
+  bool empty() const { return bytes.empty(); }
+  template <typename T>
+  int put(const std::vector<T>& v) {               // append at the next multiple of 16; returns the offset
+    const int off = align16((int)bytes.size());
+    bytes.resize(off + sizeof(T) * v.size());
+    if (!v.empty()) memcpy(bytes.data() + off, v.data(), sizeof(T) * v.size());
+    return off;
+  }
+  int seal() {                                     // pad to a multiple of 16, never empty; returns the size
+    bytes.resize(align16((int)bytes.size() + 1));
+    return (int)bytes.size();
+  }
+};
+
+// ---------------------------------------------------------------------------
+// Launch plan of (schedule, algo) under one option generation: everything a
+// decode launch needs that does not depend on the call (capi_decode.cpp)
+// ---------------------------------------------------------------------------
+enum KernelFamily { FAM_GENERIC, FAM_MS_FLOOD, FAM_MS_LAYERED, FAM_BP_TEAM, FAM_BP_TEAM_LG };
+
+struct KernelChoice {
+  const void* kernel = nullptr;
+  const char* name = "";    // as rocprofv3 reports it
+  KernelFamily family = FAM_GENERIC;
+  int team = 0;             // BP teams: waves per half-shot (one workgroup), 0 = wave kernels
+  int lanes = 0;            // ms_layered_kernel: lanes per check, 0 = chosen per layer
+  int max_waves = 0;        // most waves per workgroup the kernel was compiled for
+};
+
+struct LaunchPlan {
+  bool hbm = false;         // hbm_tile_kernel decodes: the LDS kernels cannot hold this schedule, or force_hbm
+  const void* kernel = nullptr;
+  const char* name = "";
+  int waves = 0, blocks_per_cu = 0, lds = 0;   // LDS kernels: waves per workgroup, workgroups per CU, LDS bytes
+  int team = 0, cus = 0;    // BP teams: waves per half-shot; compute units of the device
+  qldpc::DecodeArgs args{};  // every static field filled (LDS kernels)
+  qldpc::HbmArgs hargs{};    // the same for hbm_tile_kernel
+  int hbm_tiles_cap = 0;    // CUs x resident 64-slot tiles per CU
+  uint32_t gen = 0;         // g_opt.gen the plan was built under
+  bool ok = false;
+};
+
+}  // namespace capi
+#pragma GCC visibility pop
+
+// ---------------------------------------------------------------------------
+// code (Tanner graph; capi_code.cpp)
+// ---------------------------------------------------------------------------
+struct qldpc_code {
+  int m = 0, n = 0, E = 0, device = 0;
+  int uniform_deg = 0;  // row degree if every row has it, else 0
+  int max_row_deg = 0, max_col_deg = 0;
+  // GF(2) rank of H (gf2math.rank) and column bit-vectors, for OSD only:
+  // built on first use (code_osd_prep), a large code may never need them
+  mutable std::once_flag osd_once;
+  mutable int rank = -1;
+  bool zero_col = false;  // H has an all-zero column (GPU OSD: exact REF kernel only)
+  // the LDS-resident kernels' 16-bit tables hold this code (m, n, E <= 65535);
+  // otherwise every decode takes the HBM-resident kernel
+  bool lds_ok = true;
+  std::vector<int32_t> row_ptr, col_idx;     // CSR, np.where(H) order
+  std::vector<int32_t> vperm, vinv;          // relabeled -> original, original -> relabeled
+  std::vector<int32_t> csc_ptr, csc_edge;    // relabeled-variable CSC: CSR edge ids, ascending check
+  std::vector<int32_t> edge_pos;             // CSR edge -> CSC position
+  int mw = 0;                                // 64-bit words per column bit-vector
+  mutable std::vector<uint64_t> col_bits;    // [n][mw] column j of H (OSD)
+  capi::DevBuf<uint16_t> d_vinv;
+  // HBM-resident kernel: 32-bit graph tables (relabeled variables)
+  capi::DevBuf<int32_t> d_row_var, d_row_pos, d_col_ptr, d_vinv32;
+  capi::DevBuf<int32_t> d_row_ptr, d_col_idx;  // CSR for the GPU OSD
+  // layered MS stop-test filters (ms_layered_kernel): 32 fixed random parity
+  // checks of H's rows; wc[c] bit k = row c in check k, avar[v] bit k = parity
+  // of the rows of check k that hold relabeled variable v
+  std::vector<uint32_t> wc, avar;
+  uint32_t filt_all = 0;
+  capi::DevBuf<uint32_t> d_wc, d_rtab;  // rtab: [m][8] relabeled variables per row
+  capi::DevBuf<uint32_t> d_avar;        // [n] filter word per relabeled variable (layered BP)
+  // host staging workspace for qldpc_decode_host: device buffers, page-locked
+  // host mirrors (DMA copies) and a stream of its own (no device-wide sync)
+  std::mutex ws_mu;
+  int64_t ws_cap = 0;
+  capi::DevBuf<uint8_t> ws_syn, ws_ehat;
+  capi::DevBuf<int32_t> ws_iters, ws_flags;
+  capi::DevBuf<double> ws_post;
+  capi::PinBuf<uint8_t> hp_syn, hp_ehat;
+  capi::PinBuf<int32_t> hp_iters, hp_flags;
+  capi::PinBuf<double> hp_post;
+  hipStream_t ws_stream = nullptr;
+};
+
+// ---------------------------------------------------------------------------
+// schedule (layers) and its table images (capi_schedule.cpp)
+// ---------------------------------------------------------------------------
+struct qldpc_schedule {
+  const qldpc_code* code = nullptr;
+  bool layered = false;
+  int n_layers = 0;
+  int layer_g = 0;            // lanes per check shared by every layer, 0 = chosen per layer
+  capi::TableImage generic;      // every wave kernel and bp_team_kernel: the whole image in LDS
+  capi::TableImage layered_ms;   // ms_layered_kernel, uniform degree: layer-ordered tables
+  capi::TableImage layered_bp;   // bp_team_lg_kernel: layer pointers in LDS, every table global
+  capi::TableImage flood_ms;     // ms_flood_kernel, uniform degree: global tables, no LDS image
+  capi::LaunchPlan plan[2];   // per algo, under mu
+  std::mutex mu;
+  // HBM-resident kernel (hbm_kernels.hip): 32-bit layer tables and a grow-only
+  // slot-major workspace; hbm_ev orders launches that share the workspace
+  bool lds_ok = true;         // the LDS kernels' 16-bit layer tables hold this schedule
+  bool hbm_lazy = false;      // every row in exactly one layer (no state init pass)
+  std::vector<int32_t> h_lay_ptr, h_lay_rows, h_adj_ptr, h_adj_vars, h_fl_var, h_fl_pos;
+  capi::DevBuf<int32_t> d_h_lay_ptr, d_h_lay_rows, d_h_adj_ptr, d_h_adj_vars, d_h_fl_var, d_h_fl_pos;
+  void* hbm_ws = nullptr;
+  size_t hbm_ws_bytes = 0;
+  hipEvent_t hbm_ev = nullptr;
+  // half-shot work-queue counters (ring: concurrent launches on different
+  // streams take different slots; each is zeroed on the launch stream)
+  static constexpr int kQueueSlots = 64;
+  capi::DevBuf<uint32_t> d_queue;
+  std::atomic<uint32_t> qnext{0};
+};
+
+#pragma GCC visibility push(hidden)
+namespace capi {
+
+// Uniform row degree 7 or 8 with LDS offsets that fit 16 bits -> the
+// unrolled kernel instantiation and its pre-scaled table format.
+inline bool fast_table_ok(const qldpc_code* c) {
+  return (c->uniform_deg == 7 || c->uniform_deg == 8) && 8 * c->n < 65536 && 8 * c->E < 65536;
+}
+
+// capi_code.cpp: OSD's column bit-vectors and rank(H), built once on first OSD use
+void code_osd_prep(const qldpc_code* c);
+
+// capi_osd_host.cpp
+struct Gf2Basis {
+  int mw;
+  std::vector<uint64_t> vec;  // [m][mw], slot b holds a vector whose lowest set bit is b
+  std::vector<char> has;
+  Gf2Basis(int m, int mw_) : mw(mw_), vec((size_t)std::max(m, 1) * std::max(mw_, 1), 0), has(std::max(m, 1), 0) {}
+  bool insert(uint64_t* x);   // true if x (modified) was independent and got inserted
+};
+
+// capi_decode.cpp. choose_kernel and plan_static call no HIP function: the
+// static kernel arguments can be checked on a machine without a device.
+KernelChoice choose_kernel(const qldpc_schedule* s, int algo);
+// Fills every static DecodeArgs field but off_libm (plan_lds); returns the
+// LDS bytes the kernel keeps in front of the state slices.
+int plan_static(const qldpc_schedule* s, int algo, const KernelChoice& k, qldpc::DecodeArgs* a);
+// LDS bytes of a workgroup of `waves` waves; sets a->off_libm
+int plan_lds(int algo, int image_lds, int team, int waves, qldpc::DecodeArgs* a);
+void plan_static_hbm(const qldpc_schedule* s, qldpc::HbmArgs* a);
+
+}  // namespace capi
+#pragma GCC visibility pop

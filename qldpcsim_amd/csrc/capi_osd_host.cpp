@@ -1,0 +1,244 @@
+// capi_osd_host.cpp — host OSD (decoders.py:299-370): bit-packed GF(2)
+// elimination, one shot or a threaded batch.
+
+#include <thread>
+
+#include "capi_internal.h"
+
+using namespace capi;
+
+// XOR-basis insertion (also gf2math.rank for capi_code.cpp, gf2math.py:91-135)
+bool Gf2Basis::insert(uint64_t* x) {
+  for (int w = 0; w < mw; ++w) {
+    while (x[w]) {
+      const int b = w * 64 + __builtin_ctzll(x[w]);
+      if (!has[b]) {
+        memcpy(&vec[(size_t)b * mw], x, sizeof(uint64_t) * mw);
+        has[b] = 1;
+        return true;
+      }
+      const uint64_t* v = &vec[(size_t)b * mw];
+      for (int k = w; k < mw; ++k) x[k] ^= v[k];
+    }
+  }
+  return false;
+}
+
+// Order of iteration of CPython's `set(range(n)) - set(J)` (the reference's
+// infoSet, decoders.py:344): returns its first element. Emulates
+// setobject.c (set_difference -> set_add_entry / set_table_resize /
+// set_insert_clean; LINEAR_PROBES 9, PERTURB_SHIFT 5) for small-int keys
+// (hash(i) == i). Verified against the interpreter in tests.
+static int cpython_setdiff_first(int n, const std::vector<char>& inJ, int nJ) {
+  if (nJ == n) return -1;
+  if ((n >> 2) > nJ) {
+    // set_copy_and_difference: a copy of set(range(n)) (ascending slots)
+    for (int i = 0; i < n; ++i)
+      if (!inJ[i]) return i;
+    return -1;
+  }
+  size_t mask = 7;
+  std::vector<int64_t> table(8, -1);
+  size_t fill = 0, used = 0;
+  auto insert_clean = [](std::vector<int64_t>& t, size_t msk, int64_t key) {
+    size_t perturb = (size_t)key, i = (size_t)key & msk;
+    while (true) {
+      if (t[i] < 0) { t[i] = key; return; }
+      if (i + 9 <= msk) {
+        for (int j = 0; j < 9; ++j) {
+          ++i;
+          if (t[i] < 0) { t[i] = key; return; }
+        }
+      }
+      perturb >>= 5;
+      i = (i * 5 + 1 + perturb) & msk;
+    }
+  };
+  for (int key = 0; key < n; ++key) {
+    if (inJ[key]) continue;
+    // set_add_entry (new key, no dummies)
+    size_t perturb = (size_t)key, i = (size_t)key & mask;
+    while (true) {
+      size_t probes = (i + 9 <= mask) ? 9 : 0;
+      size_t k = i;
+      bool placed = false;
+      while (true) {
+        if (table[k] < 0) {
+          table[k] = key;
+          placed = true;
+          break;
+        }
+        if (probes-- == 0) break;
+        ++k;
+      }
+      if (placed) break;
+      perturb >>= 5;
+      i = (i * 5 + 1 + perturb) & mask;
+    }
+    ++fill;
+    ++used;
+    if (fill * 5 >= mask * 3) {
+      const size_t minused = used > 50000 ? used * 2 : used * 4;
+      size_t newsize = 8;
+      while (newsize <= minused) newsize <<= 1;
+      std::vector<int64_t> nt(newsize, -1);
+      for (size_t s2 = 0; s2 <= mask; ++s2)
+        if (table[s2] >= 0) insert_clean(nt, newsize - 1, table[s2]);
+      table.swap(nt);
+      mask = newsize - 1;
+    }
+  }
+  for (size_t s2 = 0; s2 <= mask; ++s2)
+    if (table[s2] >= 0) return (int)table[s2];
+  return -1;
+}
+
+extern "C" int qldpc_cpython_setdiff_first(int n, const int32_t* J, int nJ) {
+  std::vector<char> inJ(std::max(n, 1), 0);
+  int cnt = 0;
+  for (int k = 0; k < nJ; ++k)
+    if (J[k] >= 0 && J[k] < n && !inJ[J[k]]) inJ[J[k]] = 1, ++cnt;
+  return cpython_setdiff_first(n, inJ, cnt);
+}
+
+// ---------------------------------------------------------------------------
+// OSD (decoders.py:299-370), given the caller's reliability order `perm`
+// (np.argsort of decoders.py:320-325 — NumPy's own exp/argsort decide ties).
+// ---------------------------------------------------------------------------
+static int osd_one(const qldpc_code* c, const uint8_t* syn, const int32_t* perm, int order, uint8_t* ehat,
+                   int32_t* J_out, int32_t* J_size, int first_info_index) {
+  const int m = c->m, n = c->n, mw = c->mw;
+  if (n == 0) return QLDPC_OK;
+  code_osd_prep(c);
+  // (1) least reliable basis J (decoders.py:329-342): index 0 unconditionally,
+  //     then every column (in perm order) that raises the rank, until rank(H).
+  Gf2Basis B(std::max(mw * 64, 1), mw);
+  std::vector<uint64_t> x(std::max(mw, 1));
+  std::vector<int> J;
+  std::vector<char> inJ(n, 0);
+  auto col = [&](int i) { return &c->col_bits[(size_t)perm[i] * mw]; };
+  if (mw) memcpy(x.data(), col(0), sizeof(uint64_t) * mw);
+  int rank = mw ? (int)B.insert(x.data()) : 0;
+  J.push_back(0);
+  inJ[0] = 1;
+  if (rank >= c->rank)
+    return fail(QLDPC_ERANGE, "index %d is out of bounds for axis 1 with size %d", n, n);  // reference IndexError
+  int next = 1;
+  while (true) {
+    if (next >= n) return fail(QLDPC_ERANGE, "index %d is out of bounds for axis 1 with size %d", n, n);
+    memcpy(x.data(), col(next), sizeof(uint64_t) * mw);
+    if (B.insert(x.data())) {
+      J.push_back(next);
+      inJ[next] = 1;
+      if (++rank >= c->rank) break;
+    }
+    ++next;
+  }
+  const int nJ = (int)J.size();
+  if (J_out)
+    for (int k = 0; k < nJ; ++k) J_out[k] = J[k];
+  if (J_size) *J_size = nJ;
+  // (2) e_hat_perm = e_hat[perm]; order-k loop with aliasing:
+  //     the cumulative flip is I[0] for order 1 and nothing otherwise.
+  std::vector<uint8_t> ep(n);
+  for (int i = 0; i < n; ++i) ep[i] = ehat[perm[i]] & 1;
+  if (order == 1 && nJ < n) {
+    int i0 = first_info_index >= 0 ? first_info_index : cpython_setdiff_first(n, inJ, nJ);
+    if (i0 < 0 || i0 >= n || inJ[i0]) return fail(QLDPC_EINVAL, "bad first_info_index %d", i0);
+    ep[i0] ^= 1;
+  }
+  // (3) sJ = (syndrome + Hp[:, I] @ e_I) % 2
+  std::vector<uint64_t> sJ(std::max(mw, 1), 0);
+  for (int r = 0; r < m; ++r)
+    if (syn[r] & 1) sJ[r >> 6] |= 1ull << (r & 63);
+  for (int i = 0; i < n; ++i)
+    if (!inJ[i] && ep[i]) {
+      const uint64_t* cb = col(i);
+      for (int w = 0; w < mw; ++w) sJ[w] ^= cb[w];
+    }
+  // (4) (T @ sJ) % 2 with T from REF(Hp[:, J], reduced=True) (gf2math.py:139-187):
+  //     the same row operations applied to sJ as an augmented column.
+  const int rw = (nJ + 63) / 64;
+  std::vector<uint64_t> rows((size_t)m * rw, 0);
+  for (int k = 0; k < nJ; ++k) {
+    const uint64_t* cb = col(J[k]);
+    for (int w = 0; w < mw; ++w) {
+      uint64_t bits = cb[w];
+      while (bits) {
+        const int r = w * 64 + __builtin_ctzll(bits);
+        bits &= bits - 1;
+        rows[(size_t)r * rw + (k >> 6)] |= 1ull << (k & 63);
+      }
+    }
+  }
+  std::vector<uint8_t> s(m);
+  for (int r = 0; r < m; ++r) s[r] = (sJ[r >> 6] >> (r & 63)) & 1;
+  auto bit = [&](int r, int k) { return (rows[(size_t)r * rw + (k >> 6)] >> (k & 63)) & 1; };
+  auto xor_row = [&](int dst, int src) {
+    for (int w = 0; w < rw; ++w) rows[(size_t)dst * rw + w] ^= rows[(size_t)src * rw + w];
+    s[dst] ^= s[src];
+  };
+  int xr = 0;
+  for (int k = 0; k < nJ && m > 0; ++k) {
+    int r = xr;
+    while (r < m && !bit(r, k)) ++r;
+    if (r == m) continue;
+    if (r != xr) {
+      for (int w = 0; w < rw; ++w) std::swap(rows[(size_t)xr * rw + w], rows[(size_t)r * rw + w]);
+      std::swap(s[xr], s[r]);
+    }
+    for (int t = r + 1; t < m; ++t)
+      if (bit(t, k)) xor_row(t, xr);
+    for (int t = 0; t < xr; ++t)
+      if (bit(t, k)) xor_row(t, xr);
+    if (++xr >= m) break;
+  }
+  for (int k = 0; k < nJ; ++k) ep[J[k]] = k < m ? s[k] : 0;
+  for (int i = 0; i < n; ++i) ehat[perm[i]] = ep[i];  // e_hat[perm] = ... (:368)
+  return QLDPC_OK;
+}
+
+extern "C" int qldpc_osd_decode(const qldpc_code* code, const uint8_t* h_syn, const int32_t* h_perm, int order,
+                                uint8_t* h_ehat, int32_t* h_J, int32_t* h_J_size, int first_info_index) {
+  if (!code || !h_perm || !h_ehat || (!h_syn && code->m)) return fail(QLDPC_EINVAL, "null argument");
+  std::vector<char> seen(code->n, 0);
+  for (int i = 0; i < code->n; ++i) {
+    if (h_perm[i] < 0 || h_perm[i] >= code->n || seen[h_perm[i]]) return fail(QLDPC_EINVAL, "perm is not a permutation");
+    seen[h_perm[i]] = 1;
+  }
+  return osd_one(code, h_syn, h_perm, order, h_ehat, h_J, h_J_size, first_info_index);
+}
+
+int qldpc_host_thread_budget();                         // np_order.cpp
+
+extern "C" int qldpc_osd_decode_batch(const qldpc_code* code, int64_t count, const uint8_t* h_syn,
+                                      const int32_t* h_perm, int order, uint8_t* h_ehat, int nthreads) {
+  if (!code) return fail(QLDPC_EINVAL, "code is null");
+  if (count <= 0) return QLDPC_OK;
+  if (nthreads <= 0) nthreads = qldpc_host_thread_budget();
+  nthreads = (int)std::min<int64_t>(nthreads, count);
+  const int m = code->m, n = code->n;
+  std::atomic<int64_t> next{0};
+  std::atomic<int> rc{QLDPC_OK};
+  std::string err;
+  std::mutex emu;
+  auto worker = [&]() {
+    while (true) {
+      const int64_t b = next.fetch_add(1);
+      if (b >= count || rc.load() != QLDPC_OK) return;
+      const int r = qldpc_osd_decode(code, h_syn + b * m, h_perm + b * n, order, h_ehat + b * n,
+                                     nullptr, nullptr, -1);
+      if (r != QLDPC_OK) {
+        std::lock_guard<std::mutex> lk(emu);
+        if (rc.load() == QLDPC_OK) err = g_err;
+        rc = r;
+      }
+    }
+  };
+  std::vector<std::thread> th;
+  for (int t = 1; t < nthreads; ++t) th.emplace_back(worker);
+  worker();
+  for (auto& t : th) t.join();
+  if (rc.load() != QLDPC_OK) g_err = err;
+  return rc.load();
+}

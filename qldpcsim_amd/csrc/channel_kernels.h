@@ -1,5 +1,5 @@
 // channel_kernels.h — device depolarizing sampler and outcome counters
-// (simulate_p's shot source and counters), shared with capi.cpp.
+// (simulate_p's shot source and counters), shared with capi_channel.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

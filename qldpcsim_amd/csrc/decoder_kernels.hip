@@ -21,7 +21,7 @@
 //    the contiguous CSC segment in ascending check order — the exact order of
 //    NumPy's axis-0 reduction (MS, float32) or np.sum's pairwise rule (BP).
 //  * Persistent: each wave strides over half-shots; the grid is sized to the
-//    occupancy the LDS budget allows (host side, capi.cpp).
+//    occupancy the LDS budget allows (host side, capi_decode.cpp).
 //
 // Numerics: MS c2v = fl32(beta * min) formed in float64;
 // VN sum float32 sequential; posterior and v2c float64; first layer of the
@@ -423,7 +423,7 @@ struct LdsView {
   const qldpc_libm_tab* lt; // BP: NumPy libm tables (LDS)
 };
 
-// Graph table entry formats (capi.cpp builds them):
+// Graph table entry formats (capi_schedule.cpp builds them):
 //  DC == 0 (generic):   cn_tab[row_ptr[c] + k] = (relabeled var << 16) | csc position
 //  DC  > 0 (uniform row degree DC, rows padded to 8 entries, 16-byte aligned):
 //                       cn_tab[8c + k] = (4 * csc position) << 16 | (8 * relabeled var)
@@ -1021,7 +1021,7 @@ __global__ void __launch_bounds__(QLDPC_MAX_THREADS) decode_kernel(DecodeArgs a)
 // Differences from decode_kernel<MS, false, DC> (same arithmetic, same
 // results, bit for bit):
 //  * No graph tables in LDS. Each lane's static graph data comes once from
-//    HBM ("fblob", capi.cpp) and lives in VGPRs as ready-made LDS byte
+//    HBM ("fblob", capi_schedule.cpp) and lives in VGPRs as ready-made LDS byte
 //    addresses: pa[i][k] = &post[var], ca[i][k] = &c2v[csc position] of edge
 //    k of check c = lane + 64 i. The check-node step then spends no VALU on
 //    addressing. Pad checks (c >= m) read post[0] and write the 8-float pad
@@ -1059,7 +1059,7 @@ struct FloodTab {
     }
   }
 };
-struct FloodRuns {  // fblob header: runs of equal column degree (capi.cpp)
+struct FloodRuns {  // fblob header: runs of equal column degree (capi_schedule.cpp)
   int n_runs;
   int start[QLDPC_MAX_RUNS], count[QLDPC_MAX_RUNS], deg[QLDPC_MAX_RUNS], p0[QLDPC_MAX_RUNS];
 };
@@ -1853,7 +1853,7 @@ __global__ void __launch_bounds__(QLDPC_MAX_THREADS) ms_layered_kernel(DecodeArg
 // and against NumPy, tests/test_libm.py). When every edge of a check has
 // |v2c / 2| >= 19.5, all its t_k are +-1, np.prod is +-1, th2 = P / t_k is
 // +-1 and clips to +-(1 - eps) (decoders.py:256-258), so c2v_k = +-2
-// atanh(1 - eps): one constant, DecodeArgs::bp_csat (capi.cpp, the same
+// atanh(1 - eps): one constant, DecodeArgs::bp_csat (capi_decode.cpp, the same
 // restated atanh). A finite |x| is >= 19.5 iff its high word (sign cleared)
 // is >= 0x40338000 (19.5's low word is 0): DecodeArgs::bp_sat_hi, or
 // 0x7ff00000 (never) when the constant is not finite (eps <= 0: atanh(1)).
@@ -1959,7 +1959,7 @@ __device__ __forceinline__ uint32_t cn_bp_group(const DecodeArgs& a, const LdsVi
 
 // Every graph table in LDS: the flooding BP kernel (VALU-bound), and the
 // layered fallback when the schedule has no global layer image (n > 2048 or a
-// column degree > 31, capi.cpp); bp_team_lg_kernel is the layered default.
+// column degree > 31, capi_schedule.cpp); bp_team_lg_kernel is the layered default.
 template <bool LAYERED, int DC, int W>
 __global__ void __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))) bp_team_kernel(DecodeArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -2336,7 +2336,7 @@ __global__ void __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))
 }
 
 // ---------------------------------------------------------------------------
-// Host-side launch helpers (called from capi.cpp)
+// Host-side launch helpers (called from capi_decode.cpp)
 // ---------------------------------------------------------------------------
 // The BP team kernels and the flooding min-sum kernel are instantiated in
 // translation units of their own (bp_team_kernels.hip, built without SLP

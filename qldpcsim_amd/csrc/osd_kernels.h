@@ -1,4 +1,4 @@
-// osd_kernels.h — batched GPU OSD (decoders.py:299-370), shared with capi.cpp.
+// osd_kernels.h — batched GPU OSD (decoders.py:299-370), shared with capi_osd_device.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -359,7 +359,7 @@ def _thread_pool(n):
     return _POOL[n]
 
 
-_PINNED = {}
+_PINNED_BUF = {}             # key -> page-locked staging tensor (release_workspaces frees them)
 
 
 def _pinned(key, shape, dtype):
@@ -367,13 +367,13 @@ def _pinned(key, shape, dtype):
     reliability orders run at DMA speed instead of through pageable copies)."""
     import torch
     need = int(np.prod(shape))
-    buf = _PINNED.get(key)
+    buf = _PINNED_BUF.get(key)
     if buf is None or buf.numel() < need or buf.dtype != dtype:
         # page-locking is slow (ms per call): grow geometrically, start at 1 MiB
         old = 0 if buf is None or buf.dtype != dtype else buf.numel()
         cap = max(need, 2 * old, (1 << 20) // torch.empty((), dtype=dtype).element_size())
         buf = torch.empty(cap, dtype=dtype, pin_memory=True)
-        _PINNED[key] = buf
+        _PINNED_BUF[key] = buf
     return buf[:need].view(*shape)
 
 
@@ -464,7 +464,7 @@ def release_workspaces():
     workspaces of every cached schedule (hbm_tile_kernel's message state:
     up to half the free device memory per schedule, kept between launches)."""
     _DEVBUF.clear()
-    _PINNED.clear()
+    _PINNED_BUF.clear()
     _lib.release_hbm_workspaces()
 
 

@@ -558,3 +558,24 @@ def test_apply_osd_device_on_codes_past_the_register_kernels(m, n, osdpol):
                                 d(post, np.float64), torch.zeros(k, dtype=torch.int32, device="cuda"))
     decoders.apply_osd_device(H, d(syn, np.uint8), res, 0)
     np.testing.assert_array_equal(res.ehat.cpu().numpy(), want)
+
+
+def test_parity_pins_survive_device_osd_and_release(osdpol):
+    """The pin verdicts stay JSON-serialisable and unchanged through a device
+    OSD (which takes page-locked staging buffers) and release_workspaces()."""
+    import json
+    import torch
+    from qldpcsim_amd import codes, decoders
+    osdpol(device_min=1)
+    _, Hz = codes.load_code("steane")
+    syn = np.random.default_rng(5).integers(0, 2, (64, Hz.shape[0]), dtype=np.uint8)
+    before = json.dumps(decoders.parity_pins())
+    dsyn = torch.as_tensor(syn, device="cuda")
+    res = decoders.decode_batch(Hz, dsyn, 0.1 / 3, 1, algo="MS", want_post=True)   # one iteration: 27 shots left
+    assert int((res.flags & 1).eq(0).sum()) > 0
+    decoders.apply_osd_device(Hz, dsyn, res, 0)
+    torch.cuda.synchronize()
+    assert not np.any((res.ehat.cpu().numpy().astype(np.int64) @ Hz.T.astype(np.int64)) % 2 != syn)
+    assert json.dumps(decoders.parity_pins()) == before
+    decoders.release_workspaces()
+    assert json.dumps(decoders.parity_pins()) == before

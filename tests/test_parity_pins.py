@@ -64,3 +64,15 @@ def test_order_pin_failure_warns_and_routes_orders_to_numpy(fresh_pins, monkeypa
     post = np.random.default_rng(1).normal(0, 3, (5, 40))
     np.testing.assert_array_equal(decoders.osd_perms(post), np.stack([decoders.osd_perm(r) for r in post]))
     assert "AttributeError" in decoders.parity_pins()["reasons"]["order"]
+
+
+def test_release_workspaces_keeps_the_pin_verdicts(fresh_pins):
+    """The verdicts and the page-locked staging buffers are separate stores:
+    releasing the buffers leaves parity_pins() as it was, JSON-serialisable."""
+    import json
+    decoders.numpy_order_pinned()
+    decoders.numpy_libm_pinned()
+    before = decoders.parity_pins()
+    decoders.release_workspaces()
+    assert decoders.parity_pins() == before
+    assert json.loads(json.dumps(before)) == before

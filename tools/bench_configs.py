@@ -147,7 +147,7 @@ def main():
     ]
     if "--hbm-large" in sys.argv:
         # batches that fill the chip: the kernel keeps min(batch, 16 waves per
-        # CU, 64 GB of state) slots resident (capi.cpp decode_hbm)
+        # CU, 64 GB of state) slots resident (capi_decode.cpp decode_hbm)
         for pt in [(16384, 3, 6, "MS", None, 20, 196608), (16384, 3, 6, "MS", 0.02, 50, 262144),
                    (16384, 3, 6, "BP", None, 10, 98304)]:
             print(json.dumps(run_hbm(*pt)), flush=True)

@@ -1,7 +1,7 @@
 """LDS bank model of ms_flood_kernel's per-iteration LDS traffic, from the
 MI355X LDS table (MI355X_MICROARCH.md §LDS: lane groups per instruction,
 bank = (a/4) mod 32 or 64, one LDS-array cycle per distinct dword address on
-the busiest bank of a group). Recomputes the tables capi.cpp builds (degree
+the busiest bank of a group). Recomputes the tables capi_code.cpp / capi_schedule.cpp build (degree
 relabeling, CSC positions, row words) and counts array cycles per
 wave-iteration: check node (8 post reads b64 + 8 c2v reads b32 + 8 c2v writes
 b32 per check slot) and variable node (K c2v reads b32 per run chunk + one

@@ -56,7 +56,7 @@ for rep in range(reps + 1):
         times.append(time.perf_counter() - t)
 if worklog:
     # one osd_order_kernel, one osd_block_kernel and one osd_kernel (the
-    # column kernel's redo pass) per call (capi.cpp osd_device_impl)
+    # column kernel's redo pass) per call (capi_osd_device.cpp osd_device_impl)
     with open(worklog, "w") as f:
         json.dump({"unit": "osd_shot",
                    "launches": [{"kernel": kn, "half_shots": k, "iters": k}
