@@ -65,6 +65,8 @@ extern "C" {
 
 #define QLDPC_ALGO_MS 0   /* normalized min-sum, decoders.py:110-182 */
 #define QLDPC_ALGO_BP 1   /* sum-product (tanh rule), decoders.py:189-290 */
+#define QLDPC_ALGO_NG 2   /* naive greedy, decoders.py:27-66     (qldpc_hard_decode_* only) */
+#define QLDPC_ALGO_BF 3   /* bit flipping, decoders.py:74-102    (qldpc_hard_decode_* only) */
 
 /* Bit formats of syndromes and hard decisions on the device (the *_ex entry
  * points): one byte per bit, or 64-bit words with bit j % 64 of word j / 64
@@ -162,6 +164,48 @@ int qldpc_decode_host(const qldpc_code *code, const qldpc_schedule *sched, int a
                       const uint8_t *h_syn, int64_t batch, double p, int max_iter, double beta,
                       double eps, uint8_t *h_ehat, int32_t *h_iters, double *h_post,
                       int32_t *h_flags);
+
+/* The hard-decision decoders, batched, device pointers, asynchronous on
+ * `stream`. Replaces `batch` calls of NG_decoder(H, syndrome)
+ * (decoders.py:27-66) or BF_decoder(H, syndrome, max_iter) (:74-102) — what
+ * simulate_p runs for decType NG / BF (simulator.py:270-276). They take no
+ * schedule, prior or posteriors; results equal the reference's bit for bit
+ * (integer arithmetic only), its quirks included: BF's residual is "row holds
+ * a set estimate bit" XOR syndrome, a non-zero count and not a parity
+ * (:97-98), and NG flips the lowest-index variable among equal scores (:59).
+ *   algo     QLDPC_ALGO_NG or QLDPC_ALGO_BF (anything else: QLDPC_EINVAL; the
+ *            qldpc_decode_* functions answer QLDPC_EINVAL for these two)
+ *   d_syn    uint8 [batch][m] or uint64 [batch][ceil(m/64)]  (syn_format)
+ *   max_iter BF's iteration limit, >= 1 (the reference's default is 50);
+ *            ignored for NG, whose limit is 2n steps
+ *   d_ehat   uint8 [batch][n] or uint64 [batch][ceil(n/64)]  (ehat_format)
+ *   d_iters  int32 [batch]  BF: iterations as returned; NG: steps
+ *   d_flags  int32 [batch]  (nullable) QLDPC_FLAG_CONVERGED when the
+ *            reference's own stop condition held: BF's residual above all
+ *            zero (the true parity may still differ), NG's residual all zero
+ * Limits: m, n and the number of edges <= 65535 (16-bit tables; every such
+ * code's per-wave state fits a CU's LDS); past that, QLDPC_EUNSUP. An empty
+ * matrix is QLDPC_EINVAL. Arguments are checked before any HIP call. The
+ * first decode of a (code, algo) after creation or a qldpc_set_option uploads
+ * the code's tables (once) and queries the device for its launch plan; later
+ * ones only launch. Option "static_sched" applies as for qldpc_decode_device;
+ * at most 64 launches of one code may be in flight at once. */
+int qldpc_hard_decode_device(const qldpc_code *code, int algo, const void *d_syn, int syn_format,
+                             int64_t batch, int max_iter, void *d_ehat, int ehat_format, int32_t *d_iters,
+                             int32_t *d_flags, void *stream);
+
+/* Same with host buffers (one byte per bit), staged through the code's
+ * page-locked workspace, the one qldpc_decode_host uses. What the single-shot
+ * shims NG_decoder / BF_decoder call. */
+int qldpc_hard_decode_host(const qldpc_code *code, int algo, const uint8_t *h_syn, int64_t batch,
+                           int max_iter, uint8_t *h_ehat, int32_t *h_iters, int32_t *h_flags);
+
+/* Name of the kernel qldpc_hard_decode_device launches ("ng_kernel",
+ * "bf_kernel"), as rocprofv3 reports it, and its launch geometry (as
+ * qldpc_decode_launch_info). Measurement only. */
+int qldpc_hard_kernel_name(const qldpc_code *code, int algo, char *buf, int len);
+int qldpc_hard_launch_info(const qldpc_code *code, int algo, int *waves_per_wg, int *wg_per_cu,
+                           int *lds_bytes);
 
 /* OSD post-decoder, host. Replaces OSDdec (decoders.py:299-370) including its
  * aliasing semantics: order 0 -> solve;

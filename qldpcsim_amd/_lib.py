@@ -15,7 +15,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("QLDPC_LIB", os.path.join(_HERE, "_build", "libqldpc_hip.so"))
 
 QLDPC_OK, QLDPC_EINVAL, QLDPC_ERANGE, QLDPC_EUNSUP, QLDPC_EHIP, QLDPC_ENOMEM = 0, -1, -2, -3, -4, -5
-ALGO = {"MS": 0, "BP": 1}
+ALGO = {"MS": 0, "BP": 1, "NG": 2, "BF": 3}
+HARD_ALGOS = ("NG", "BF")            # no schedule, prior or posteriors (qldpc_hard_decode_*)
 FLAG_CONVERGED, FLAG_MIN_ZERO, FLAG_NONFINITE = 1, 2, 4
 FMT_BYTES, FMT_BITS = 0, 1          # syndrome / estimate formats (QLDPC_FMT_*)
 
@@ -26,6 +27,7 @@ EXPORTS = (
     "qldpc_schedule_create", "qldpc_schedule_destroy", "qldpc_schedule_release_workspace",
     "qldpc_decode_device", "qldpc_decode_device_ex", "qldpc_decode_host", "qldpc_decode_kernel_name",
     "qldpc_decode_launch_info",
+    "qldpc_hard_decode_device", "qldpc_hard_decode_host", "qldpc_hard_kernel_name", "qldpc_hard_launch_info",
     "qldpc_osd_decode", "qldpc_osd_decode_batch", "qldpc_osd_device", "qldpc_osd_order_device",
     "qldpc_osd_device_ordered", "qldpc_osd_device_ordered_ex", "qldpc_cpython_setdiff_first",
     "qldpc_osd_order_host", "qldpc_np_argsort_host", "qldpc_osd_keys_host", "qldpc_libm_eval_host",
@@ -72,6 +74,10 @@ def _load():
         "qldpc_decode_host": ([P, P, I, P, I64, D, I, D, D, P, P, P, P], I),
         "qldpc_decode_kernel_name": ([P, P, I, ctypes.c_char_p, I], I),
         "qldpc_decode_launch_info": ([P, P, I, ctypes.POINTER(I), ctypes.POINTER(I), ctypes.POINTER(I)], I),
+        "qldpc_hard_decode_device": ([P, I, P, I, I64, I, P, I, P, P, P], I),
+        "qldpc_hard_decode_host": ([P, I, P, I64, I, P, P, P], I),
+        "qldpc_hard_kernel_name": ([P, I, ctypes.c_char_p, I], I),
+        "qldpc_hard_launch_info": ([P, I, ctypes.POINTER(I), ctypes.POINTER(I), ctypes.POINTER(I)], I),
         "qldpc_osd_decode": ([P, P, P, I, P, P, P, I], I),
         "qldpc_osd_decode_batch": ([P, I64, P, P, I, P, I], I),
         "qldpc_osd_device": ([P, I64, P, P, I, P, P, P], I),
@@ -232,8 +238,13 @@ def release_hbm_workspaces():
 
 
 def kernel_name(H, layer_ptr, layer_rows, algo, device_index=None):
-    """Name of the decode kernel a launch for (H, schedule, algo) uses."""
+    """Name of the decode kernel a launch for (H, schedule, algo) uses (NG /
+    BF: the schedule is ignored)."""
     code = code_for(H, device_index)
+    if algo in HARD_ALGOS:
+        buf = ctypes.create_string_buffer(128)
+        check(lib.qldpc_hard_kernel_name(code.handle, ALGO[algo], buf, 128))
+        return buf.value.decode()
     sched = code.schedule(layer_ptr, layer_rows)
     buf = ctypes.create_string_buffer(128)
     check(lib.qldpc_decode_kernel_name(code.handle, sched.handle, ALGO[algo], buf, 128))
@@ -244,8 +255,11 @@ def launch_info(H, layer_ptr, layer_rows, algo, device_index=None):
     """(waves per workgroup, workgroups per CU, LDS bytes per workgroup) of
     that kernel's launch; zeros for the HBM-resident kernel."""
     code = code_for(H, device_index)
-    sched = code.schedule(layer_ptr, layer_rows)
     w, b, l = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    if algo in HARD_ALGOS:
+        check(lib.qldpc_hard_launch_info(code.handle, ALGO[algo], ctypes.byref(w), ctypes.byref(b), ctypes.byref(l)))
+        return w.value, b.value, l.value
+    sched = code.schedule(layer_ptr, layer_rows)
     check(lib.qldpc_decode_launch_info(code.handle, sched.handle, ALGO[algo], ctypes.byref(w), ctypes.byref(b),
                                        ctypes.byref(l)))
     return w.value, b.value, l.value

@@ -283,11 +283,7 @@ extern "C" int qldpc_timing_read(double* total_ms, int64_t* launches) {
 
 // A timed launch: timing_begin before the kernel is enqueued, timing_end
 // after. The event pair goes to g_events; drain_events_locked destroys it.
-struct TimedLaunch {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-};
-
-static int timing_begin(TimedLaunch* t, hipStream_t st) {
+int capi::timing_begin(TimedLaunch* t, hipStream_t st) {
   {
     std::lock_guard<std::mutex> lk(g_tmu);
     if (!g_timing) return QLDPC_OK;
@@ -298,7 +294,7 @@ static int timing_begin(TimedLaunch* t, hipStream_t st) {
   return QLDPC_OK;
 }
 
-static int timing_end(TimedLaunch* t, hipStream_t st) {
+int capi::timing_end(TimedLaunch* t, hipStream_t st) {
   if (!t->e0) return QLDPC_OK;
   HIP_TRY(hipEventRecord(t->e1, st));
   std::lock_guard<std::mutex> lk(g_tmu);
@@ -491,6 +487,35 @@ extern "C" int qldpc_decode_launch_info(const qldpc_code* code, const qldpc_sche
   return QLDPC_OK;
 }
 
+// The code's host staging workspace (under ws_mu), grown to hold `batch`
+// half-shots; the posterior buffers only once a caller wants posteriors.
+int capi::ws_reserve(qldpc_code* code, int64_t batch, bool want_post) {
+  const int m = code->m, n = code->n;
+  if (!code->ws_stream) HIP_TRY(hipStreamCreateWithFlags(&code->ws_stream, hipStreamNonBlocking));
+  if (batch > code->ws_cap) {
+    code->ws_cap = 0;
+    code->ws_post_cap = 0;
+    const int64_t cap = std::max<int64_t>(batch, 64);
+    const size_t cm = std::max<int64_t>(1, cap * m), cn = std::max<int64_t>(1, cap * n);
+    HIP_TRY(code->ws_syn.alloc(cm));
+    HIP_TRY(code->ws_ehat.alloc(cn));
+    HIP_TRY(code->ws_iters.alloc(cap));
+    HIP_TRY(code->ws_flags.alloc(cap));
+    HIP_TRY(code->hp_syn.alloc(cm));
+    HIP_TRY(code->hp_ehat.alloc(cn));
+    HIP_TRY(code->hp_iters.alloc(cap));
+    HIP_TRY(code->hp_flags.alloc(cap));
+    code->ws_cap = cap;
+  }
+  if (want_post && code->ws_post_cap < code->ws_cap) {
+    const size_t cn = std::max<int64_t>(1, code->ws_cap * n);
+    HIP_TRY(code->ws_post.alloc(cn));
+    HIP_TRY(code->hp_post.alloc(cn));
+    code->ws_post_cap = code->ws_cap;
+  }
+  return QLDPC_OK;
+}
+
 extern "C" int qldpc_decode_host(const qldpc_code* code_c, const qldpc_schedule* sched, int algo,
                                  const uint8_t* h_syn, int64_t batch, double p, int max_iter,
                                  double beta, double eps, uint8_t* h_ehat, int32_t* h_iters,
@@ -503,23 +528,7 @@ extern "C" int qldpc_decode_host(const qldpc_code* code_c, const qldpc_schedule*
   if (code->device < 0) return fail(QLDPC_EHIP, "no HIP device was visible when the code was created");
   std::lock_guard<std::mutex> lk(code->ws_mu);
   const int m = code->m, n = code->n;
-  if (!code->ws_stream) HIP_TRY(hipStreamCreateWithFlags(&code->ws_stream, hipStreamNonBlocking));
-  if (batch > code->ws_cap) {
-    code->ws_cap = 0;
-    const int64_t cap = std::max<int64_t>(batch, 64);
-    const size_t cm = std::max<int64_t>(1, cap * m), cn = std::max<int64_t>(1, cap * n);
-    HIP_TRY(code->ws_syn.alloc(cm));
-    HIP_TRY(code->ws_ehat.alloc(cn));
-    HIP_TRY(code->ws_iters.alloc(cap));
-    HIP_TRY(code->ws_flags.alloc(cap));
-    HIP_TRY(code->ws_post.alloc(cn));
-    HIP_TRY(code->hp_syn.alloc(cm));
-    HIP_TRY(code->hp_ehat.alloc(cn));
-    HIP_TRY(code->hp_iters.alloc(cap));
-    HIP_TRY(code->hp_flags.alloc(cap));
-    HIP_TRY(code->hp_post.alloc(cn));
-    code->ws_cap = cap;
-  }
+  if (int rc = ws_reserve(code, batch, h_post != nullptr)) return rc;
   hipStream_t st = code->ws_stream;
   if (batch * m) {
     memcpy(code->hp_syn, h_syn, batch * m);

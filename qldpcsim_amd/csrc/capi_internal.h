@@ -14,6 +14,7 @@
 
 #include "../../include/qldpc_decoder.h"
 #include "decoder_kernels.h"
+#include "hard_kernels.h"
 #include "hbm_kernels.h"
 
 #pragma GCC visibility push(hidden)
@@ -143,6 +144,17 @@ struct LaunchPlan {
   bool ok = false;
 };
 
+// Launch plan of (code, NG | BF) under one option generation (capi_hard.cpp):
+// the hard-decision kernels need no schedule, so the plan belongs to the code
+struct HardPlan {
+  const void* kernel = nullptr;
+  const char* name = "";
+  int waves = 0, blocks_per_cu = 0, lds = 0, cus = 0;
+  qldpc::HardArgs args{};    // every static field filled
+  uint32_t gen = 0;
+  bool ok = false;
+};
+
 }  // namespace capi
 #pragma GCC visibility pop
 
@@ -181,7 +193,7 @@ struct qldpc_code {
   // host staging workspace for qldpc_decode_host: device buffers, page-locked
   // host mirrors (DMA copies) and a stream of its own (no device-wide sync)
   std::mutex ws_mu;
-  int64_t ws_cap = 0;
+  int64_t ws_cap = 0, ws_post_cap = 0;   // half-shots held; of those, with posterior buffers
   capi::DevBuf<uint8_t> ws_syn, ws_ehat;
   capi::DevBuf<int32_t> ws_iters, ws_flags;
   capi::DevBuf<double> ws_post;
@@ -189,6 +201,17 @@ struct qldpc_code {
   capi::PinBuf<int32_t> hp_iters, hp_flags;
   capi::PinBuf<double> hp_post;
   hipStream_t ws_stream = nullptr;
+  // hard-decision decoders (capi_hard.cpp), under hard_mu: 16-bit CSR / CSC
+  // tables in original variable labels (row_ell | col_ell | row_ptr | row_var |
+  // col_ptr | col_chk),
+  // uploaded on first use; the launch plans per algo; a half-shot queue ring
+  // as qldpc_schedule's
+  static constexpr int kHardQueueSlots = 64;
+  std::mutex hard_mu;
+  capi::DevBuf<uint16_t> d_hard_tab;
+  capi::DevBuf<uint32_t> d_hard_queue;
+  std::atomic<uint32_t> hard_qnext{0};
+  capi::HardPlan hard_plan[2];   // [algo - QLDPC_ALGO_NG]
 };
 
 // ---------------------------------------------------------------------------
@@ -251,6 +274,20 @@ int plan_static(const qldpc_schedule* s, int algo, const KernelChoice& k, qldpc:
 // LDS bytes of a workgroup of `waves` waves; sets a->off_libm
 int plan_lds(int algo, int image_lds, int team, int waves, qldpc::DecodeArgs* a);
 void plan_static_hbm(const qldpc_schedule* s, qldpc::HbmArgs* a);
+// The code's host staging workspace (caller holds ws_mu), grown to `batch`
+// half-shots; posterior buffers only when wanted
+int ws_reserve(qldpc_code* code, int64_t batch, bool want_post);
+// HIP events around a kernel launch when qldpc_timing_enable is on
+struct TimedLaunch {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+};
+int timing_begin(TimedLaunch* t, hipStream_t st);
+int timing_end(TimedLaunch* t, hipStream_t st);
+
+// capi_hard.cpp. Calls no HIP function: the per-wave LDS layout of the
+// hard-decision kernels (every HardArgs field that depends on the code's
+// shape alone); returns QLDPC_EUNSUP past the 16-bit tables.
+int hard_layout(const qldpc_code* c, int algo, qldpc::HardArgs* a);
 
 }  // namespace capi
 #pragma GCC visibility pop

@@ -6,6 +6,10 @@
         reference qLDPCsim/decoders.py:189-290  -> (e_hat int64[n], n_iter)
     OSDdec(H, e_hat, syndrome, posteriorLLRs, order=0)
         reference qLDPCsim/decoders.py:299-370  -> e_hat (updated in place)
+    NG_decoder(H, syndrome)
+        reference qLDPCsim/decoders.py:27-66    -> (e_hat int8[n], steps)
+    BF_decoder(H, syndrome, max_iter=50)
+        reference qLDPCsim/decoders.py:74-102   -> (e_hat bool[n], n_iter)
 
 plus the batched entry point the simulator uses, `decode_batch`, which decodes
 many syndromes of one matrix in one kernel launch.
@@ -45,8 +49,8 @@ import numpy as np
 from . import _lib, hostcores
 from .schedule import pack_layers
 
-__all__ = ["MS_decoder", "BP_decoder", "OSDdec", "decode_batch", "DecodeResult", "osd_perm", "pack_bits",
-           "unpack_bits",
+__all__ = ["MS_decoder", "BP_decoder", "NG_decoder", "BF_decoder", "OSDdec", "decode_batch", "DecodeResult",
+           "osd_perm", "pack_bits", "unpack_bits",
            "osd_perms", "apply_osd", "apply_osd_device", "apply_osd_device_many", "osd_device_stage",
            "osd_device_finish", "osd_host_orders", "osd_status_check", "numpy_order_pinned",
            "numpy_libm_pinned", "parity_pins"]
@@ -101,9 +105,14 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
     `p` is the decoder prior (simulate passes p/3, simulator.py:278-282).
     `out` (device path): a DecodeResult of matching device tensors to write
     into instead of allocating (steady-state loops allocate nothing).
+    `algo`: "MS", "BP", or the hard-decision "NG" / "BF", which take only H,
+    the syndromes and (BF) `max_iter`: p, layers, beta and eps are ignored,
+    want_post / osd_order >= 0 raise ValueError, and the result's post is None.
     """
     if algo not in _lib.ALGO:
         raise ValueError("Unrecognized decoder type.")
+    if algo in _lib.HARD_ALGOS:
+        return _decode_batch_hard(H, syndromes, max_iter, algo, want_post, osd_order, stream, out, ehat_bits)
     if algo == "BP" and "libm" not in _PINNED:
         numpy_libm_pinned()                   # once: warns if BP cannot be bit-exact on this NumPy
     H = np.asarray(H)
@@ -171,6 +180,68 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
     if osd_order >= 0:
         apply_osd(H, syn, ehat, post, flags, osd_order)
     return res
+
+
+def _decode_batch_hard(H, syndromes, max_iter, algo, want_post, osd_order, stream, out, ehat_bits):
+    """decode_batch for algo "NG" / "BF" (ng_kernel / bf_kernel): no schedule,
+    prior or posteriors; `max_iter` is BF's and NG ignores it. DecodeResult.post
+    is None; `converged` is the reference's own stop condition (BF: its
+    non-zero-count residual all zero, which the true parity may contradict)."""
+    if want_post or osd_order >= 0:
+        raise ValueError(f"{algo} is a hard-decision decoder: it has no posteriors (want_post) and no OSD step")
+    H = np.asarray(H)
+    if H.ndim != 2 or H.size == 0:
+        raise ValueError("H must be a non-empty 2-D matrix")
+    m, n = H.shape
+    max_iter = int(max_iter) if algo == "BF" else 1
+    if max_iter < 1:
+        raise ValueError("max_iter must be >= 1")
+    A = _lib.ALGO[algo]
+    if _is_torch(syndromes):
+        import torch
+        dev = syndromes.device
+        code = _lib.code_for(H, dev.index)
+        syn = syndromes.contiguous()
+        wm, wn = (m + 63) // 64, (n + 63) // 64
+        if syn.dim() == 2 and syn.dtype == torch.uint8 and syn.shape[1] == m:
+            syn_fmt = _lib.FMT_BYTES
+        elif syn.dim() == 2 and syn.dtype == torch.int64 and syn.shape[1] == wm:
+            syn_fmt = _lib.FMT_BITS
+        else:
+            raise ValueError(f"syndromes must be uint8 [B, {m}] or int64 words [B, {wm}]")
+        B = syn.shape[0]
+        e_shape, e_dtype = ((B, wn), torch.int64) if ehat_bits else ((B, n), torch.uint8)
+        if out is not None:
+            ehat, iters, flags = out.ehat, out.iters, out.flags
+            if not (ehat.shape == e_shape and ehat.dtype == e_dtype and iters.shape == (B,) and
+                    iters.dtype == torch.int32 and flags.shape == (B,) and flags.dtype == torch.int32 and
+                    all(t.device == dev and t.is_contiguous() for t in (ehat, iters, flags))):
+                raise ValueError("out buffers do not match the batch (uint8 [B, n] or int64 [B, ceil(n/64)], "
+                                 "int32 [B], int32 [B]) on the syndromes' device")
+        else:
+            ehat = torch.empty(e_shape, dtype=e_dtype, device=dev)
+            iters = torch.empty(B, dtype=torch.int32, device=dev)
+            flags = torch.empty(B, dtype=torch.int32, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.lib.qldpc_hard_decode_device(
+            code.handle, A, syn.data_ptr(), syn_fmt, B, max_iter, ehat.data_ptr(),
+            _lib.FMT_BITS if ehat_bits else _lib.FMT_BYTES, iters.data_ptr(), flags.data_ptr(), st))
+        return DecodeResult(ehat, iters, None, flags)
+
+    syn = np.ascontiguousarray(syndromes)
+    if syn.ndim != 2 or syn.shape[1] != m:
+        raise ValueError(f"syndromes must be [B, {m}]")
+    if syn.size and (syn.min() < 0 or syn.max() > 1):
+        raise ValueError("syndrome entries must be 0 or 1")
+    syn = syn.astype(np.uint8, copy=False)
+    B = syn.shape[0]
+    code = _lib.code_for(H)
+    ehat = np.zeros((B, n), np.uint8)
+    iters = np.zeros(B, np.int32)
+    flags = np.zeros(B, np.int32)
+    _lib.check(_lib.lib.qldpc_hard_decode_host(code.handle, A, _lib.ptr(syn), B, max_iter, _lib.ptr(ehat),
+                                               _lib.ptr(iters), _lib.ptr(flags)))
+    return DecodeResult(ehat, iters, None, flags)
 
 
 def osd_perm(posteriorLLRs):
@@ -746,6 +817,38 @@ def BP_decoder(H: np.ndarray, syndrome: np.ndarray, p: float, max_iter: int = 99
     if not conv and OSDorder >= 0:                 # (:287-288)
         e_hat = OSDdec(H, e_hat, syndrome, post, OSDorder)
     return e_hat, it
+
+
+def _single_hard(H, syndrome, algo, max_iter=1):
+    H = np.asarray(H)
+    syndrome = np.asarray(syndrome)
+    m, n = H.shape
+    if syndrome.shape != (m,):
+        raise ValueError(f"syndrome must have shape ({m},), got {syndrome.shape}")
+    r = decode_batch(H, syndrome.reshape(1, m), 0.0, max_iter, algo=algo)
+    return r.ehat[0], int(r.iters[0])
+
+
+def NG_decoder(H: np.ndarray, syndrome: np.ndarray):
+    """Naive greedy (reference decoders.py:27-66) on the GPU: (int8 [n], steps)."""
+    H = np.asarray(H)
+    syndrome = np.asarray(syndrome)
+    if H.size == 0 or syndrome.size == 0:          # the bare array of MS / BP / BF (:86-87, DESIGN.md §7)
+        return np.zeros(H.shape[1] if H.size else 0, dtype=np.int8)
+    e, steps = _single_hard(H, syndrome, "NG")
+    return e.astype(np.int8), steps
+
+
+def BF_decoder(H: np.ndarray, syndrome: np.ndarray, max_iter: int = 50):
+    """Bit flipping (reference decoders.py:74-102) on the GPU: (bool [n], iterations)."""
+    H = np.asarray(H)
+    syndrome = np.asarray(syndrome)
+    if H.size == 0 or syndrome.size == 0:          # reference quirk: bare array (:86-87)
+        return np.zeros(H.shape[1] if H.size else 0, dtype=np.int8)
+    if max_iter < 1:                               # the loop does not run (:89, :102): float zeros
+        return np.zeros(H.shape[1]), max_iter
+    e, it = _single_hard(H, syndrome, "BF", max_iter)
+    return e.astype(bool), it
 
 
 def OSDdec(H: np.ndarray, e_hat: np.ndarray, syndrome: np.ndarray, posteriorLLRs: np.ndarray,

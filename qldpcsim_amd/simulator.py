@@ -259,14 +259,14 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
     if Hz.size and Hz.shape[1] != n:
         raise ValueError("Hx and Hz must have the same number of columns (physical qubits).")
     layersX, layersZ = select_layers(Hx, Hz, decSchedule)   # raises ValueError (:236)
-    if decType in ("NG", "BF"):
-        raise NotImplementedError(
-            f"decType {decType!r} (decoders.py NG_decoder/BF_decoder) is outside the MI355X "
-            "decoder's scope (SURVEY.md §2 rows 4-5); use 'MS' or 'BP'")
-    if decType not in ("MS", "BP"):
+    if decType not in _lib.ALGO:
         raise ValueError("Unrecognized decoder type.")
-    # the reference never passes OSDorder to BP_decoder (:281-282)
+    # the reference never passes OSDorder to BP_decoder (:281-282); NG and BF
+    # get (H, syndrome) alone (:270-276): no prior, no decIterations (BF runs
+    # its default 50), no OSD
     osd = OSDorder if decType == "MS" else -1
+    if decType in _lib.HARD_ALGOS:
+        decIterations = 50
     lpX, lrX = pack_layers(layersX, Hz.shape[0])    # X half decodes Hz with Hx's layers
     lpZ, lrZ = pack_layers(layersZ, Hx.shape[0])    # Z half decodes Hx with Hz's layers
 
@@ -524,7 +524,8 @@ def main(argv=None):
     parser.add_argument("--shots", type=int, default=1000, help="Number of Monte Carlo shots.")
     parser.add_argument("--rngSeed", type=int, default=None, help="RNG seed.")
     parser.add_argument("--decType", choices=["NG", "BF", "MS", "BP"], default="MS",
-                        help="Decoder type: [NG] Naive Greedy; [MS] Min-Sum; [BP] Belief Propagation.")
+                        help="Decoder type: [NG] Naive Greedy; [BF] Bit Flipping; [MS] Min-Sum; "
+                             "[BP] Belief Propagation.")
     parser.add_argument("--decIterations", type=int, default=99, help="Number of decoding iterations.")
     parser.add_argument("--decSchedule", choices=["F", "L", "S"], default="F",
                         help="Decoder scheduling method: [F] flooding; [L] layered; [S] serial.")
