@@ -82,6 +82,7 @@ extern "C" {
 
 typedef struct qldpc_code qldpc_code;         /* Tanner graph of one H, resident in HBM */
 typedef struct qldpc_schedule qldpc_schedule; /* layer partition bound to one code     */
+typedef struct qldpc_logicals qldpc_logicals; /* logical operators of a CSS pair, in HBM */
 
 const char *qldpc_last_error(void);
 const char *qldpc_version(void);
@@ -354,6 +355,51 @@ int qldpc_count_outcomes(const qldpc_code *hx, const qldpc_code *hz, int64_t bat
                          const int32_t *d_iters_x, const int32_t *d_iters_z, int64_t *d_counters,
                          void *stream);
 
+/* ---- Logical error counting of a CSS pair -------------------------------
+ * The reference's "degen" counter is an integer product that real codes never
+ * satisfy (simulator.py:296), so it reports 1 - exact / shots. These entry
+ * points add the stabiliser-group test: with Lx, Lz a paired basis of the
+ * pair's logical operators (Hz Lx^T = 0, Hx Lz^T = 0, Lx Lz^T = I; the
+ * package computes one in qldpcsim_amd/logicals.py), a residual
+ * rX = errX ^ ehat_x whose syndrome is zero is an X stabiliser exactly when
+ * Lz rX = 0 mod 2.
+ *
+ * qldpc_logicals_create: h_Lx, h_Lz are host uint8 [k][n] (0/1), 0 <= k <= n
+ * (k = 0: both may be NULL). Validates the shapes, packs both tables
+ * word-major (uint64 [ceil(n/64)][k padded to 64]) and uploads them to the
+ * codes' device: two hipMalloc and two synchronous copies, once; a failure
+ * frees what was uploaded. hx / hz must outlive the handle. Without a
+ * visible device the handle is still made (as qldpc_code_create).
+ * qldpc_logicals_destroy: hipFree of both tables; NULL is accepted.
+ *
+ * qldpc_count_logical_ex: qldpc_count_outcomes_ex and the logical test in one
+ * kernel (one pass over the batch's rows; the six-counter kernel is not
+ * launched). Per half-shot class: 2 decoder failure (H ehat != syndrome, the
+ * reference's test, :300-303), 1 logical error (not 2 and L r != 0), 0 success
+ * (not 2 and L r == 0; an exact match is class 0), L = Lz for the X half, Lx
+ * for the Z half. The logical reading assumes syndrome = H err.
+ *   d_counters  int64 [9], added to: the six of qldpc_count_outcomes, then
+ *               {logicalErrors_X, logicalErrors_Z (class-1 half-shots),
+ *                decSuccessLogical (shots with both halves class 0)}
+ *   d_class_x, d_class_z  uint8 [batch]                     (NULL: not written)
+ *   d_flip_x   uint64 [batch][ceil(k/64)]  Lz rX mod 2, bit i % 64 of word i / 64,
+ *   d_flip_z   the same for Lx rZ; written as computed for every class,
+ *              padding bits zero, nothing for k = 0            (NULL: not written)
+ * Every argument check (null handles, a handle built for another pair or
+ * device, unknown formats, negative batch, null required buffers) returns
+ * before any HIP call; batch == 0 returns QLDPC_OK. Asynchronous on `stream`:
+ * no allocation, no copy, no synchronisation. Option "logical_tabs" picks the
+ * table residency (LDS / global memory). */
+int qldpc_logicals_create(const qldpc_code *hx, const qldpc_code *hz, const uint8_t *h_Lx, const uint8_t *h_Lz,
+                          int k, qldpc_logicals **out);
+int qldpc_logicals_destroy(qldpc_logicals *lg);
+int qldpc_count_logical_ex(const qldpc_code *hx, const qldpc_code *hz, const qldpc_logicals *lg, int64_t batch,
+                           const uint64_t *d_errx, const uint64_t *d_errz, const void *d_syn_z,
+                           const void *d_syn_x, int syn_format, const void *d_ehat_x, const void *d_ehat_z,
+                           int ehat_format, const int32_t *d_iters_x, const int32_t *d_iters_z,
+                           int64_t *d_counters, uint8_t *d_class_x, uint8_t *d_class_z, uint64_t *d_flip_x,
+                           uint64_t *d_flip_z, void *stream);
+
 /* Kernel timing (HIP events around each decode kernel launch, on the launch
  * stream). Enabled by qldpc_timing_enable(1); qldpc_timing_read returns the
  * summed kernel milliseconds and launch count since the last reset. */
@@ -379,6 +425,8 @@ int qldpc_timing_read(double *total_ms, int64_t *launches);
  *   "osd_tickets" (1)         GPU OSD engine wave placed by per-CU SIMD tickets
  *   "osd_prof" (0)            print per-phase OSD cycles (builds with QLDPC_OSD_TIMING)
  *   "osd_hbm" (0)             GPU OSD through the device-memory kernel at any size (tests)
+ *   "logical_tabs" (0)        qldpc_count_logical_ex: logical tables staged in LDS (1), read from
+ *                             global memory (2), or chosen by size (0)
  * Unknown name: QLDPC_EINVAL. */
 int qldpc_set_option(const char *name, int64_t value);
 int qldpc_get_option(const char *name, int64_t *value);

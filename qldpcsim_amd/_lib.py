@@ -33,6 +33,7 @@ EXPORTS = (
     "qldpc_osd_order_host", "qldpc_np_argsort_host", "qldpc_osd_keys_host", "qldpc_libm_eval_host",
     "qldpc_channel_thresholds", "qldpc_channel_sample", "qldpc_channel_sample_ex", "qldpc_count_outcomes",
     "qldpc_count_outcomes_ex",
+    "qldpc_logicals_create", "qldpc_logicals_destroy", "qldpc_count_logical_ex",
     "qldpc_timing_enable", "qldpc_timing_reset", "qldpc_timing_read",
     "qldpc_set_option", "qldpc_get_option",
 )
@@ -94,6 +95,9 @@ def _load():
         "qldpc_channel_sample_ex": ([P, P, D, ctypes.c_uint64, ctypes.c_uint64, I64, P, P, P, P, I, P], I),
         "qldpc_count_outcomes": ([P, P, I64, P, P, P, P, P, P, P, P, P, P], I),
         "qldpc_count_outcomes_ex": ([P, P, I64, P, P, P, P, I, P, P, I, P, P, P, P], I),
+        "qldpc_logicals_create": ([P, P, P, P, I, PP], I),
+        "qldpc_logicals_destroy": ([P], I),
+        "qldpc_count_logical_ex": ([P, P, P, I64, P, P, P, P, I, P, P, I, P, P, P, P, P, P, P, P], I),
         "qldpc_timing_enable": ([I], I),
         "qldpc_timing_reset": ([], I),
         "qldpc_timing_read": ([P, P], I),
@@ -224,6 +228,49 @@ try:
 except ImportError:                                     # the normalising path alone
     _xxh = None
 _code_fast = {}
+
+
+class Logicals:
+    """Logical operators (Lx, Lz) of the pair (cx, cz) on the codes' device
+    (qldpc_logicals). Keeps both Codes alive."""
+
+    def __init__(self, cx, cz, Lx, Lz):
+        self.cx, self.cz = cx, cz
+        Lx = np.ascontiguousarray(Lx, dtype=np.uint8)
+        Lz = np.ascontiguousarray(Lz, dtype=np.uint8)
+        if Lx.ndim != 2 or Lx.shape != Lz.shape or (Lx.shape[0] and Lx.shape[1] != cx.n):
+            raise ValueError(f"logical operators must be two [k, {cx.n}] matrices")
+        self.k = int(Lx.shape[0])
+        self.kw = (self.k + 63) // 64
+        h = ctypes.c_void_p()
+        check(lib.qldpc_logicals_create(cx.handle, cz.handle, ptr(Lx) if self.k else None,
+                                        ptr(Lz) if self.k else None, self.k, ctypes.byref(h)))
+        self.handle = h
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h and lib is not None:
+            lib.qldpc_logicals_destroy(h)
+            self.handle = None
+
+
+_logicals_cache = {}
+
+
+def logicals_for(Hx, Hz, device_index=None):
+    """Cached Logicals of a CSS pair on a device: the operators come from
+    logicals.css_logicals, computed and uploaded once per pair."""
+    from . import logicals
+    cx, cz = code_for(Hx, device_index), code_for(Hz, device_index)
+    key = (id(cx), id(cz))
+    with _code_lock:
+        lg = _logicals_cache.get(key)
+    if lg is None:
+        Lx, Lz = logicals.css_logicals(Hx, Hz)
+        lg = Logicals(cx, cz, Lx, Lz)
+        with _code_lock:
+            lg = _logicals_cache.setdefault(key, lg)
+    return lg
 
 
 def release_hbm_workspaces():

@@ -5,7 +5,7 @@
 //   capi_decode.cpp      launch plans, decode entry points, timing, HBM path
 //   capi_osd_host.cpp    host OSD (bit-packed GF(2))
 //   capi_osd_device.cpp  GPU OSD launchers
-//   capi_channel.cpp     channel sampler and outcome counters
+//   capi_channel.cpp     channel sampler, outcome counters, logical operators
 // capi_internal.h holds what they share.
 
 #include <cstdarg>
@@ -50,7 +50,8 @@ static std::atomic<int64_t>* option_slot(const char* name) {
                {"bp_team_w", &Options::bp_team_w},     {"static_sched", &Options::static_sched},
                {"waves_per_wg", &Options::waves_per_wg}, {"wg_per_cu", &Options::wg_per_cu},
                {"osd_column", &Options::osd_column},   {"osd_tickets", &Options::osd_tickets},
-               {"osd_prof", &Options::osd_prof},       {"osd_hbm", &Options::osd_hbm}};
+               {"osd_prof", &Options::osd_prof},       {"osd_hbm", &Options::osd_hbm},
+               {"logical_tabs", &Options::logical_tabs}};
   for (const auto& e : table)
     if (strcmp(e.name, name) == 0) return &(g_opt.*(e.slot));
   return nullptr;

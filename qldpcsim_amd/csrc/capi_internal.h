@@ -41,7 +41,7 @@ int fail(int code, const char* fmt, ...);
 struct Options {
   std::atomic<int64_t> force_hbm{0}, flood_generic{0}, layered_generic{0}, ms_lanes_per_check{0}, bp_wave{0},
       bp_lg{1}, bp_team_w{0}, static_sched{0}, waves_per_wg{0}, wg_per_cu{0}, osd_column{0}, osd_tickets{1},
-      osd_prof{0}, osd_hbm{0};
+      osd_prof{0}, osd_hbm{0}, logical_tabs{0};
   std::atomic<uint32_t> gen{1};
 };
 extern Options g_opt;

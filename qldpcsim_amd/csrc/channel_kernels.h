@@ -45,11 +45,29 @@ struct CountArgs {
   long long batch;
 };
 
+// count_logical_kernel: the six counters of CountArgs plus the stabiliser-group
+// test of the residuals against the pair's logical operators.
+struct LogicalArgs {
+  CountArgs c;             // c.acc: [9] accumulated (the six, then logX, logZ, success)
+  const uint64_t* tab_z;   // Lz, word-major [W][kp]: word w of logical row i at w * kp + i (tests errX ^ eX)
+  const uint64_t* tab_x;   // Lx, the same layout (tests errZ ^ eZ)
+  int k, kp;               // logical qubits; k padded to a multiple of 64 (padding rows are zero)
+  int tabs_lds;            // both tables staged into LDS, else read from global memory
+  uint8_t* class_x;        // [batch] 0 success, 1 logical error, 2 decoder failure; may be null
+  uint8_t* class_z;
+  uint64_t* flip_x;        // [batch][kp / 64] Lz (errX ^ eX) mod 2, bit i % 64 of word i / 64; may be null
+  uint64_t* flip_z;        // [batch][kp / 64] Lx (errZ ^ eZ) mod 2
+};
+
 constexpr int kChannelWaves = 4;  // waves per workgroup (one shot per wave at a time)
+constexpr int kLogicalCounters = 9;
 
 // LDS bytes the two kernels need for these tables
 int channel_lds_bytes(const PairTabs& t, bool counters);
+// LDS bytes of count_logical_kernel, with both logical tables staged or not
+int logical_lds_bytes(const PairTabs& t, int kp, bool tabs_lds);
 hipError_t launch_channel_sample(const SampleArgs& a, int grid, hipStream_t stream);
 hipError_t launch_count_outcomes(const CountArgs& a, int grid, hipStream_t stream);
+hipError_t launch_count_logical(const LogicalArgs& a, int grid, hipStream_t stream);
 
 }  // namespace qldpc

@@ -24,7 +24,12 @@
 //     failX  Hz·eX mod 2 != sy_z,  failZ  Hx·eZ mod 2 != sy_x      (:300-303)
 //     iteration sums                                              (:291-292)
 //
-// Both kernels: one wavefront per shot (grid-stride), CSR of Hx / Hz staged
+// count_logical_kernel (the logical option) forms the same six counters and,
+// in the same pass, the stabiliser-group outcome of each half-shot from the
+// pair's logical operators: three more counters, optional per-shot classes
+// and flip words (see the kernel).
+//
+// All kernels: one wavefront per shot (grid-stride), CSR of Hx / Hz staged
 // once per workgroup into LDS as 16-bit column indices; lane l owns bit l of
 // every 64-qubit word (ballots assemble the words); checks are lane-parallel.
 // HBM-bound byte work, no MFMA: per shot the sampler writes 2·8·W + m_x + m_z
@@ -284,6 +289,151 @@ __global__ void __launch_bounds__(64 * kChannelWaves) count_outcomes_kernel(Coun
   }
 }
 
+// Lz·rX (or Lx·rZ) mod 2 for one shot: lane l owns logical rows l, l + 64, ...
+// of the word-major table `tab` ([W][kp]: consecutive lanes read consecutive
+// 8-byte words, so a 32-lane half covers all 64 banks once; r[w] is one
+// broadcast read), XOR-accumulates tab[w][i] & r[w] over the W residual words
+// and takes the popcount parity; a ballot makes each flip word. Padding rows
+// of the table are zero, so bits above k are. Lane g returns word g.
+__device__ __forceinline__ uint64_t logical_flips(const uint64_t* tab, const uint64_t* r, int W, int kp, int lane,
+                                                  bool* any) {
+  uint64_t mine = 0;
+  bool nz = false;
+  for (int i0 = 0; i0 < kp; i0 += 64) {
+    const uint64_t* col = tab + i0 + lane;
+    uint64_t x = 0;
+#pragma unroll 4
+    for (int w = 0; w < W; ++w) x ^= col[(size_t)w * kp] & r[w];
+    const uint64_t bits = __ballot(__popcll(x) & 1);
+    nz |= bits != 0;
+    if (lane == (i0 >> 6)) mine = bits;
+  }
+  *any = nz;
+  return mine;
+}
+
+// count_outcomes_kernel's six counters and, in the same pass over the shot's
+// rows, the stabiliser-group outcome of each half:
+//     class 2  decoder failure: H·e mod 2 != syndrome (failX / failZ above)
+//     class 1  logical error:   not 2, and L·(err ^ e) mod 2 != 0
+//     class 0  success:         not 2, and L·(err ^ e) mod 2 == 0 (the residual
+//                               is a stabiliser; an exact match is class 0)
+// with L = Lz for the X half and Lx for the Z half. Counters 6, 7: class-1 X /
+// Z half-shots; 8: shots with both halves class 0. The residual words, formed
+// in lanes < W, are published to the wave's LDS slot for logical_flips.
+// TLDS: both logical tables staged into LDS behind the CSR tables.
+template <int DC, bool VEC, bool TLDS>
+__global__ void __launch_bounds__(64 * kChannelWaves) count_logical_kernel(LogicalArgs la) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const CountArgs& a = la.c;
+  const PairTabs& t = a.t;
+  const Tabs tb = stage_tables(t, smem);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int W = t.W, n = t.n, kp = la.kp, kw = la.kp >> 6;
+  constexpr int NC = kLogicalCounters;
+  uint64_t* cmz = reinterpret_cast<uint64_t*>(tb.tail);
+  uint64_t* cmx = cmz + W;
+  unsigned long long* part = reinterpret_cast<unsigned long long*>(cmx + W);  // [waves][NC]
+  uint64_t* ltab = reinterpret_cast<uint64_t*>(part + NC * kChannelWaves);    // TLDS: Lz then Lx, [W][kp] each
+  const size_t tab_words = TLDS ? (size_t)W * kp : 0;
+  uint64_t* ex = ltab + 2 * tab_words + wave * 4 * W;
+  uint64_t* ez = ex + W;
+  uint64_t* rx = ez + W;  // residual words errX ^ eX
+  uint64_t* rz = rx + W;
+  for (int i = threadIdx.x; i < 2 * W; i += blockDim.x) cmz[i] = 0;
+  if constexpr (TLDS) {
+    for (size_t i = threadIdx.x; i < tab_words; i += blockDim.x) {
+      ltab[i] = la.tab_z[i];
+      ltab[tab_words + i] = la.tab_x[i];
+    }
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < t.ez; e += blockDim.x) {
+    const int j = t.ci_z[e];
+    atomicOr(reinterpret_cast<unsigned long long*>(&cmz[j >> 6]), 1ull << (j & 63));
+  }
+  for (int e = threadIdx.x; e < t.ex; e += blockDim.x) {
+    const int j = t.ci_x[e];
+    atomicOr(reinterpret_cast<unsigned long long*>(&cmx[j >> 6]), 1ull << (j & 63));
+  }
+  __syncthreads();
+  const uint64_t* lz = TLDS ? ltab : la.tab_z;
+  const uint64_t* lx = TLDS ? ltab + tab_words : la.tab_x;
+  const uint64_t my_cmz = lane < W ? cmz[lane] : 0, my_cmx = lane < W ? cmx[lane] : 0;
+  unsigned long long cnt[NC] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (long long b = (long long)blockIdx.x * kChannelWaves + wave; b < a.batch;
+       b += (long long)gridDim.x * kChannelWaves) {
+    const uint64_t tx = lane < W ? a.errx[b * W + lane] : 0, tz = lane < W ? a.errz[b * W + lane] : 0;
+    const int itx = a.itx[b], itz = a.itz[b];
+    if (a.eh_bits) {
+      if (lane < W) {
+        ex[lane] = reinterpret_cast<const uint64_t*>(a.ehx)[b * W + lane];
+        ez[lane] = reinterpret_cast<const uint64_t*>(a.ehz)[b * W + lane];
+      }
+    } else {
+      pack_estimate<VEC>(a.ehx + b * n, n, W, lane, reinterpret_cast<uint8_t*>(ex));
+      pack_estimate<VEC>(a.ehz + b * n, n, W, lane, reinterpret_cast<uint8_t*>(ez));
+    }
+    wave_sync();
+    bool lane_exact = true, lane_degen = true;
+    if (lane < W) {
+      const uint64_t dx = tx ^ ex[lane], dz = tz ^ ez[lane];
+      lane_exact = (dx | dz) == 0;
+      lane_degen = ((dx & my_cmz) | (dz & my_cmx)) == 0;
+      rx[lane] = dx;
+      rz[lane] = dz;
+    }
+    wave_sync();  // rx / rz are read by every lane below
+    const bool exact = __ballot(!lane_exact) == 0;
+    const bool degen = !exact && __ballot(!lane_degen) == 0;
+    bool fx = false, fz = false;
+    const uint32_t* ex32 = reinterpret_cast<const uint32_t*>(ex);
+    const uint32_t* ez32 = reinterpret_cast<const uint32_t*>(ez);
+    const int wmz = (t.mz + 63) >> 6, wmx = (t.mx + 63) >> 6;
+    for (int c = lane; c < t.mz; c += 64) {
+      const uint32_t s = a.syn_bits ? (uint32_t)(reinterpret_cast<const uint64_t*>(a.syz)[b * wmz + (c >> 6)] >> (c & 63)) & 1u
+                                    : a.syz[b * t.mz + c];
+      fx |= row_parity<DC>(tb.rpz, tb.ciz, c, ex32) != s;
+    }
+    for (int c = lane; c < t.mx; c += 64) {
+      const uint32_t s = a.syn_bits ? (uint32_t)(reinterpret_cast<const uint64_t*>(a.syx)[b * wmx + (c >> 6)] >> (c & 63)) & 1u
+                                    : a.syx[b * t.mx + c];
+      fz |= row_parity<DC>(tb.rpx, tb.cix, c, ez32) != s;
+    }
+    const bool failx = __ballot(fx) != 0, failz = __ballot(fz) != 0;
+    bool lgx = false, lgz = false;
+    const uint64_t flx = logical_flips(lz, rx, W, kp, lane, &lgx);
+    const uint64_t flz = logical_flips(lx, rz, W, kp, lane, &lgz);
+    if (lane < kw) {
+      if (la.flip_x) la.flip_x[b * kw + lane] = flx;
+      if (la.flip_z) la.flip_z[b * kw + lane] = flz;
+    }
+    if (lane == 0) {
+      const int cx = failx ? 2 : (lgx ? 1 : 0), cz = failz ? 2 : (lgz ? 1 : 0);
+      if (la.class_x) la.class_x[b] = (uint8_t)cx;
+      if (la.class_z) la.class_z[b] = (uint8_t)cz;
+      cnt[0] += failx;
+      cnt[1] += failz;
+      cnt[2] += exact;
+      cnt[3] += degen;
+      cnt[4] += (unsigned long long)(long long)itx;
+      cnt[5] += (unsigned long long)(long long)itz;
+      cnt[6] += cx == 1;
+      cnt[7] += cz == 1;
+      cnt[8] += (cx | cz) == 0;
+    }
+    wave_sync();  // the next shot overwrites the wave's slot
+  }
+  if (lane == 0)
+    for (int k = 0; k < NC; ++k) part[wave * NC + k] = cnt[k];
+  __syncthreads();
+  if (threadIdx.x < NC) {
+    unsigned long long s = 0;
+    for (int w = 0; w < kChannelWaves; ++w) s += part[w * NC + threadIdx.x];
+    if (s) atomicAdd(&a.acc[threadIdx.x], s);
+  }
+}
+
 // common row degree of Hx and Hz if both are uniform with a specialised
 // instantiation, else 0 (generic CSR loop)
 int uniform_degree(const PairTabs& t) {
@@ -332,6 +482,35 @@ hipError_t launch_count_outcomes(const CountArgs& a, int grid, hipStream_t strea
     case 16: return launch(count_outcomes_kernel<8, false>, &a, sizeof a, grid, lds, stream);
     case 1: return launch(count_outcomes_kernel<0, true>, &a, sizeof a, grid, lds, stream);
     default: return launch(count_outcomes_kernel<0, false>, &a, sizeof a, grid, lds, stream);
+  }
+}
+
+int logical_lds_bytes(const PairTabs& t, int kp, bool tabs_lds) {
+  long long b = (4 * (t.mz + 1 + t.mx + 1) + 2 * (t.ez + t.ex) + 7) & ~7;
+  b += 8 * 2 * t.W + 8 * kLogicalCounters * kChannelWaves;
+  if (tabs_lds) b += 2ll * 8 * t.W * kp;
+  b += kChannelWaves * 4 * t.W * 8;
+  return b > 0x7fffffff ? 0x7fffffff : (int)b;
+}
+
+template <int DC, bool VEC>
+static hipError_t launch_logical(const LogicalArgs& a, int grid, int lds, hipStream_t stream) {
+  return a.tabs_lds ? launch(count_logical_kernel<DC, VEC, true>, &a, sizeof a, grid, lds, stream)
+                    : launch(count_logical_kernel<DC, VEC, false>, &a, sizeof a, grid, lds, stream);
+}
+
+hipError_t launch_count_logical(const LogicalArgs& a, int grid, hipStream_t stream) {
+  const int lds = logical_lds_bytes(a.c.t, a.kp, a.tabs_lds != 0);
+  const bool vec = (a.c.t.n % 4 == 0) && ((uintptr_t)a.c.ehx % 4 == 0) && ((uintptr_t)a.c.ehz % 4 == 0);
+  switch (uniform_degree(a.c.t) * 2 + (vec ? 1 : 0)) {
+    case 13: return launch_logical<6, true>(a, grid, lds, stream);
+    case 12: return launch_logical<6, false>(a, grid, lds, stream);
+    case 15: return launch_logical<7, true>(a, grid, lds, stream);
+    case 14: return launch_logical<7, false>(a, grid, lds, stream);
+    case 17: return launch_logical<8, true>(a, grid, lds, stream);
+    case 16: return launch_logical<8, false>(a, grid, lds, stream);
+    case 1: return launch_logical<0, true>(a, grid, lds, stream);
+    default: return launch_logical<0, false>(a, grid, lds, stream);
   }
 }
 

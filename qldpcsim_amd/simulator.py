@@ -42,10 +42,13 @@ from . import _lib, decoders
 from .schedule import layerize, select_layers, pack_layers  # noqa: F401  (re-exported)
 
 __all__ = ["load_matrix", "simulate_p", "simulate", "main", "layerize", "sample_channel",
-           "count_outcomes"]
+           "count_outcomes", "count_logical_outcomes", "wilson_interval"]
 
 COUNTER_KEYS = ("DecFailures_X", "DecFailures_Z", "decSuccessExact", "decSuccessDegen",
                 "nIterAccX", "nIterAccZ")
+# the logical option's counters (class-1 half-shots per half; shots with both
+# halves class 0), after COUNTER_KEYS in the device accumulator
+LOGICAL_KEYS = ("logicalErrors_X", "logicalErrors_Z", "decSuccessLogical")
 
 
 def load_matrix(path: str) -> np.ndarray:
@@ -113,6 +116,70 @@ def count_outcomes(Hx, Hz, sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ):
     }
 
 
+def _pack_flips(F):
+    """0/1 [B, k] -> uint64 [B, ceil(k/64)], bit i % 64 of word i / 64."""
+    B, k = F.shape
+    kw = (k + 63) // 64
+    b = np.zeros((B, 8 * kw), dtype=np.uint8)
+    if k:
+        pk = np.packbits(F.astype(np.uint8), axis=1, bitorder="little")
+        b[:, :pk.shape[1]] = pk
+    return b.view("<u8").astype(np.uint64, copy=False).reshape(B, kw)
+
+
+def count_logical_outcomes(Hx, Hz, sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ, logicals=None,
+                           want_shots=False):
+    """count_outcomes plus the stabiliser-group outcome of each half-shot
+    (the NumPy twin of qldpc_count_logical_ex), vectorised over the batch.
+
+    With rX = errX ^ eX, rZ = errZ ^ eZ and (Lx, Lz) = `logicals` (default:
+    logicals.css_logicals(Hx, Hz)), the X half (the estimate that decodes Hz) is
+        class 2  decoder failure: Hz·eX mod 2 != sy_z (the reference's test)
+        class 1  logical error:   not 2, and Lz·rX mod 2 != 0
+        class 0  success:         not 2, and Lz·rX mod 2 == 0 (rX is then an
+                 X stabiliser; an exact match is class 0)
+    and the Z half mirrors it with Hx, sy_x, Lx, rZ. The logical reading
+    assumes sy = H·err: both shot sources guarantee it; for caller-supplied
+    samples it is the caller's contract.
+
+    Returns the six COUNTER_KEYS and the three LOGICAL_KEYS; with want_shots
+    also (class_x, class_z uint8 [B], flip_x, flip_z uint64 [B, ceil(k/64)]):
+    flip_x = Lz·rX mod 2, flip_z = Lx·rZ mod 2, bit i % 64 of word i / 64,
+    as computed for every class."""
+    if logicals is None:
+        from .logicals import css_logicals
+        logicals = css_logicals(Hx, Hz)
+    Lx, Lz = logicals
+    f32 = np.float32
+    out = count_outcomes(Hx, Hz, sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ)
+    sX = (np.asarray(eX).astype(f32) @ Hz.T.astype(f32)).astype(np.int64) % 2
+    sZ = (np.asarray(eZ).astype(f32) @ Hx.T.astype(f32)).astype(np.int64) % 2
+    failX = np.any(sX != sy_z, axis=1)
+    failZ = np.any(sZ != sy_x, axis=1)
+    fX = ((errX ^ eX).astype(f32) @ Lz.T.astype(f32)).astype(np.int64) % 2
+    fZ = ((errZ ^ eZ).astype(f32) @ Lx.T.astype(f32)).astype(np.int64) % 2
+    cX = np.where(failX, 2, np.any(fX != 0, axis=1).astype(np.uint8)).astype(np.uint8)
+    cZ = np.where(failZ, 2, np.any(fZ != 0, axis=1).astype(np.uint8)).astype(np.uint8)
+    out["logicalErrors_X"] = int((cX == 1).sum())
+    out["logicalErrors_Z"] = int((cZ == 1).sum())
+    out["decSuccessLogical"] = int(((cX == 0) & (cZ == 0)).sum())
+    if want_shots:
+        return out, (cX, cZ, _pack_flips(fX), _pack_flips(fZ))
+    return out
+
+
+def wilson_interval(successes, trials, z=1.959963984540054):
+    """Wilson score interval [lo, hi] of a binomial proportion, clipped to
+    [0, 1] (z = 1.959963984540054: 95 %)."""
+    if trials <= 0:
+        return [0.0, 1.0]
+    ph = successes / trials
+    den = 1.0 + z * z / trials
+    mid = (ph + z * z / (2.0 * trials)) / den
+    half = z * np.sqrt(ph * (1.0 - ph) / trials + z * z / (4.0 * trials * trials)) / den
+    return [float(max(0.0, mid - half)), float(min(1.0, mid + half))]
+
+
 class DeviceChannel:
     """Device-side shot source and outcome counters (channel_kernels.hip via
     the C ABI): the depolarizing draw of `sample_channel` as a counter-based
@@ -134,6 +201,7 @@ class DeviceChannel:
             self.cx = _lib.code_for(Hx, self.dev.index)
             self.cz = _lib.code_for(Hz, self.dev.index)
         self.mx, self.mz = self.cx.m, self.cz.m
+        self._Hx, self._Hz, self._lg = Hx, Hz, None
         self.seed = int(seed) & ((1 << 64) - 1)
         self.shot = int(shot0)
 
@@ -171,6 +239,17 @@ class DeviceChannel:
         torch = self.torch
         if acc is None:
             acc = torch.zeros(len(COUNTER_KEYS), dtype=torch.int64, device=self.dev)
+        B, syn_fmt, e_fmt = self._layout("count_device", sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ)
+        _lib.check(_lib.lib.qldpc_count_outcomes_ex(
+            self.cx.handle, self.cz.handle, int(B), errX.data_ptr(), errZ.data_ptr(), sy_z.data_ptr(),
+            sy_x.data_ptr(), syn_fmt, eX.data_ptr(), eZ.data_ptr(), e_fmt, itX.data_ptr(),
+            itZ.data_ptr(), acc.data_ptr(), self._stream()))
+        return acc
+
+    def _layout(self, who, sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ):
+        """(B, syndrome format, estimate format) of one batch's buffers;
+        ValueError if they do not match the batch layout."""
+        torch = self.torch
         B = sy_z.shape[0]
         ts = (sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ)
         syn_bits = sy_z.dtype == torch.int64
@@ -180,17 +259,52 @@ class DeviceChannel:
                 eX.shape != e_shape or eZ.shape != e_shape or errX.shape != (B, self.W) or \
                 eX.dtype not in (torch.uint8, torch.int64) or eZ.dtype != eX.dtype or \
                 sy_x.dtype != sy_z.dtype or itX.dtype != torch.int32 or itZ.dtype != torch.int32:
-            raise ValueError("count_device: buffers do not match the batch layout")
+            raise ValueError(f"{who}: buffers do not match the batch layout")
         F = lambda b: _lib.FMT_BITS if b else _lib.FMT_BYTES  # noqa: E731
-        _lib.check(_lib.lib.qldpc_count_outcomes_ex(
-            self.cx.handle, self.cz.handle, int(B), errX.data_ptr(), errZ.data_ptr(), sy_z.data_ptr(),
-            sy_x.data_ptr(), F(syn_bits), eX.data_ptr(), eZ.data_ptr(), F(e_bits), itX.data_ptr(),
-            itZ.data_ptr(), acc.data_ptr(), self._stream()))
-        return acc
+        return B, F(syn_bits), F(e_bits)
 
     def count(self, sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ):
         v = self.count_device(sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ).cpu().tolist()
         return dict(zip(COUNTER_KEYS, (int(x) for x in v)))
+
+    def logicals(self):
+        """The pair's logical operators on the device (built on first use from
+        logicals.css_logicals, cached per pair and device)."""
+        if self._lg is None:
+            with self.torch.cuda.device(self.dev):
+                self._lg = _lib.logicals_for(self._Hx, self._Hz, self.dev.index)
+        return self._lg
+
+    def count_logical_device(self, sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ, acc=None, want_shots=False):
+        """Adds the batch's nine counters (COUNTER_KEYS then LOGICAL_KEYS) to
+        `acc` (int64 [9] device tensor, created if None) in one kernel, without
+        a host sync. With want_shots returns (acc, class_x, class_z uint8 [B],
+        flip_x, flip_z int64 [B, ceil(k/64)] words): see
+        count_logical_outcomes."""
+        torch = self.torch
+        lg = self.logicals()
+        if acc is None:
+            acc = torch.zeros(len(COUNTER_KEYS) + len(LOGICAL_KEYS), dtype=torch.int64, device=self.dev)
+        if acc.shape != (len(COUNTER_KEYS) + len(LOGICAL_KEYS),) or acc.dtype != torch.int64 or \
+                acc.device != self.dev or not acc.is_contiguous():
+            raise ValueError("count_logical_device: acc must be an int64 [9] tensor on the channel's device")
+        B, syn_fmt, e_fmt = self._layout("count_logical_device", sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ)
+        shots = None
+        if want_shots:
+            shots = (torch.empty(B, dtype=torch.uint8, device=self.dev),
+                     torch.empty(B, dtype=torch.uint8, device=self.dev),
+                     torch.empty((B, lg.kw), dtype=torch.int64, device=self.dev),
+                     torch.empty((B, lg.kw), dtype=torch.int64, device=self.dev))
+        sp = [t.data_ptr() if t.numel() else None for t in shots] if want_shots else [None] * 4
+        _lib.check(_lib.lib.qldpc_count_logical_ex(
+            self.cx.handle, self.cz.handle, lg.handle, int(B), errX.data_ptr(), errZ.data_ptr(), sy_z.data_ptr(),
+            sy_x.data_ptr(), syn_fmt, eX.data_ptr(), eZ.data_ptr(), e_fmt, itX.data_ptr(), itZ.data_ptr(),
+            acc.data_ptr(), sp[0], sp[1], sp[2], sp[3], self._stream()))
+        return (acc,) + shots if want_shots else acc
+
+    def count_logical(self, sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ):
+        v = self.count_logical_device(sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ).cpu().tolist()
+        return dict(zip(COUNTER_KEYS + LOGICAL_KEYS, (int(x) for x in v)))
 
 
 def _device_ok():
@@ -241,7 +355,8 @@ def _host_orders_on(dev, staged):
 def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decType: str = "MS",
                decIterations: int = 99, decSchedule: str = "F", OSDorder: int = -1,
                rngSeed: Optional[int] = None, *, batch_size: Optional[int] = None,
-               verbose: bool = True, samples=None, sampler: Optional[str] = None) -> dict:
+               verbose: bool = True, samples=None, sampler: Optional[str] = None,
+               logical: bool = False) -> dict:
     """One depolarizing probability: sample, decode both halves, count.
 
     Returns the reference's dict (simulator.py:308-315). `samples`, if given,
@@ -249,6 +364,14 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
     the parity tests). `sampler`: "device" (HIP sampler + counters on the GPU,
     the default when a device is present), or "host" (NumPy). Extra keyword
     arguments default to reference behaviour.
+
+    `logical` (extension): also test every residual against the pair's logical
+    operators (count_logical_outcomes; on the device one counter kernel forms
+    all nine counters). The dict then gains the three LOGICAL_KEYS,
+    `logical_error_rate` = 1 - decSuccessLogical / shots and its 95 % Wilson
+    interval `logical_error_rate_ci95` = [lo, hi]. Raises ValueError if
+    (Hx, Hz) is not a CSS pair. With `samples`, sy = H·err is the caller's
+    contract.
     """
     if rngSeed is not None:
         np.random.seed(rngSeed)                    # reference side effect (:187-188)
@@ -275,7 +398,11 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
     my_start = rank * (shots // world) + min(rank, shots % world)
     seed = None if rngSeed is None else [int(rngSeed), int(rank)]
     rng = np.random.default_rng(seed)
-    tot = {k: 0 for k in COUNTER_KEYS}
+    keys = COUNTER_KEYS + LOGICAL_KEYS if logical else COUNTER_KEYS
+    if logical:
+        from .logicals import css_logicals
+        pair_logicals = css_logicals(Hx, Hz)       # raises ValueError before any shot is drawn
+    tot = {k: 0 for k in keys}
     t0 = time.time()
     done = 0
     if sampler not in (None, "device", "host"):
@@ -301,7 +428,8 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
         # the GPU runs batch b's decode and device OSD;
         # counters accumulate on the device (one sync per batch, in the OSD
         # staging; none without OSD until the end).
-        acc = torch.zeros(len(COUNTER_KEYS), dtype=torch.int64, device=dev)
+        acc = torch.zeros(len(keys), dtype=torch.int64, device=dev)
+        count_dev = ch.count_logical_device if logical else ch.count_device
         pending = None
         phase = 0
         osd_flags = []                             # IndexError flags, checked once at the end
@@ -349,7 +477,7 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
                     # worker thread while the GPU decoded this batch
                     decoders.osd_device_finish(items, staged, osd, host=pending[7].result())
                     decoders.osd_status_check(items, defer=osd_flags)
-                ch.count_device(sy_z_, sy_x_, errX_, errZ_, rX_.ehat, rZ_.ehat, rX_.iters, rZ_.iters, acc)
+                count_dev(sy_z_, sy_x_, errX_, errZ_, rX_.ehat, rZ_.ehat, rX_.iters, rZ_.iters, acc)
             if cur is not None and osd >= 0 and cur[6] is None:
                 # few OSD shots: stage (and sync on) this batch's decode now
                 cur[6] = decoders.osd_device_stage([(Hz, cur[0], cur[4]), (Hx, cur[1], cur[5])],
@@ -364,7 +492,7 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
                 print(f"\r(p={p:5.2e}) Decoding block n. {done:3}/{my_shots:4}... "
                       f"({done / (time.time() - t0):.3g} shots/s)", end="", flush=True)
         decoders.osd_status_raise(osd_flags)
-        tot = dict(zip(COUNTER_KEYS, (int(x) for x in acc.cpu().tolist())))
+        tot = dict(zip(keys, (int(x) for x in acc.cpu().tolist())))
     while not use_dev and done < my_shots:
         B = min(batch_size, my_shots - done)
         if samples is not None:
@@ -376,7 +504,11 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
                                    layer_ptr=lpX, layer_rows=lrX)
         rZ = decoders.decode_batch(Hx, sy_x, p / 3, decIterations, algo=decType, osd_order=osd,
                                    layer_ptr=lpZ, layer_rows=lrZ)
-        c = count_outcomes(Hx, Hz, sy_z, sy_x, errX, errZ, rX.ehat, rZ.ehat, rX.iters, rZ.iters)
+        if logical:
+            c = count_logical_outcomes(Hx, Hz, sy_z, sy_x, errX, errZ, rX.ehat, rZ.ehat, rX.iters, rZ.iters,
+                                       logicals=pair_logicals)
+        else:
+            c = count_outcomes(Hx, Hz, sy_z, sy_x, errX, errZ, rX.ehat, rZ.ehat, rX.iters, rZ.iters)
         for k in tot:
             tot[k] += c[k]
         done += B
@@ -389,12 +521,12 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
         import torch
         backend = dist.get_backend()
         dev = torch.device("cuda", torch.cuda.current_device()) if backend == "nccl" else torch.device("cpu")
-        t = torch.tensor([tot[k] for k in COUNTER_KEYS], dtype=torch.int64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)   # the sweep's only collective
-        tot = dict(zip(COUNTER_KEYS, (int(v) for v in t.cpu().tolist())))
+        t = torch.tensor([tot[k] for k in keys], dtype=torch.int64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)   # the sweep's only collective (six values, nine with logical)
+        tot = dict(zip(keys, (int(v) for v in t.cpu().tolist())))
     if verbose and rank == 0:
         print()
-    return {
+    res = {
         "DecFailures_X": tot["DecFailures_X"],
         "DecFailures_Z": tot["DecFailures_Z"],
         "decSuccessExact": tot["decSuccessExact"],
@@ -402,6 +534,12 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
         "Avg_number_of_iterations_X": tot["nIterAccX"] / float(shots),
         "Avg_number_of_iterations_Z": tot["nIterAccZ"] / float(shots),
     }
+    if logical:
+        for k in LOGICAL_KEYS:
+            res[k] = tot[k]
+        res["logical_error_rate"] = 1. - tot["decSuccessLogical"] / float(shots)
+        res["logical_error_rate_ci95"] = wilson_interval(shots - tot["decSuccessLogical"], shots)
+    return res
 
 
 def format_results(p, results, shots):
@@ -414,6 +552,18 @@ def format_results(p, results, shots):
         lines.append(f"         {pT:10.2e}         |     {qbler:7.2e}      |       "
                      f"{r['DecFailures_X']:5},{r['DecFailures_Z']:5}       |      "
                      f"{r['Avg_number_of_iterations_X']:5.2f}, {r['Avg_number_of_iterations_Z']:5.2f}")
+    return "\n".join(lines)
+
+
+def format_logical_results(p, results, shots):
+    """The logical option's table, printed after the reference's."""
+    lines = ["\n                  ===          LOGICAL ERROR RATES          ===\n",
+             "   Depolarizing probability | Logical block error rate |     95 % interval      | Logical errors (X,Z)",
+             "----------------------------+--------------------------+------------------------+----------------------"]
+    for pT, r in zip(p, results):
+        lo, hi = r["logical_error_rate_ci95"]
+        lines.append(f"         {pT:10.2e}         |         {r['logical_error_rate']:7.2e}         |  "
+                     f"[{lo:8.2e}, {hi:8.2e}]  |     {r['logicalErrors_X']:6},{r['logicalErrors_Z']:6}")
     return "\n".join(lines)
 
 
@@ -444,9 +594,14 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
              decIterations: int = 99, decSchedule: str = "F", OSDorder: int = -1,
              rngSeed: Optional[int] = None, *, batch_size: Optional[int] = None, verbose: bool = True,
              return_results: bool = False, sampler: Optional[str] = None,
-             resultsFile: Optional[str] = None, on_point=None):
+             resultsFile: Optional[str] = None, on_point=None, logical: bool = False):
     """p-sweep + results table (simulator.py:319-347). Returns None like the
     reference unless return_results=True.
+
+    logical (extension): simulate_p(logical=True) for every point; a second
+    table with the logical block error rate, its 95 % interval and the logical
+    errors per half follows the reference's. The results file's meta then
+    holds "logical": true (a file written without the option is refused).
 
     resultsFile (extension): a JSON file the sweep writes after every
     p-point; a rerun with the same arguments skips the points already there
@@ -462,6 +617,10 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
     meta = {"Hx": HxFile, "Hz": HzFile, "shots": shots, "decType": decType,
             "decIterations": decIterations, "decSchedule": decSchedule, "OSDorder": OSDorder,
             "rngSeed": rngSeed, "world": world, "sampler": sampler}
+    extra = {}
+    if logical:
+        meta["logical"] = True
+        extra["logical"] = True
     done = _load_results(resultsFile, meta)
     results = []
     for pT in p:
@@ -472,7 +631,7 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
         r = simulate_p(Hx, Hz, p=pT, shots=shots, rngSeed=rngSeed, decType=decType,
                        decIterations=decIterations, decSchedule=decSchedule,
                        OSDorder=OSDorder, batch_size=batch_size, verbose=verbose,
-                       sampler=sampler)
+                       sampler=sampler, **extra)
         if on_point is not None:
             on_point(pT, r, time.perf_counter() - t0)
         results.append(r)
@@ -481,6 +640,8 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
             _save_results(resultsFile, meta, done)
     if rank == 0:
         print(format_results(p, results, shots))
+        if logical:
+            print(format_logical_results(p, results, shots))
     return results if return_results else None
 
 
@@ -537,6 +698,9 @@ def main(argv=None):
                         help="Where shots are sampled and counted (default: device if present).")
     parser.add_argument("--results", default=None,
                         help="Resumable results file (JSON, written after every p-point).")
+    parser.add_argument("--logical", action="store_true",
+                        help="Also count logical errors (residuals tested against the CSS pair's logical "
+                             "operators) and print the logical block error rate with its 95 %% interval.")
     args = parser.parse_args(argv)
     own_group = _init_dist_from_env()              # torchrun: shots shard over the ranks
     _, rank, _ = _dist()
@@ -548,7 +712,7 @@ def main(argv=None):
         simulate(HxFile=args.Hx, HzFile=args.Hz, p=args.p, shots=args.shots, decType=args.decType,
                  decIterations=args.decIterations, decSchedule=args.decSchedule,
                  OSDorder=args.OSDorder, rngSeed=args.rngSeed, batch_size=args.batch,
-                 sampler=args.sampler, resultsFile=args.results)
+                 sampler=args.sampler, resultsFile=args.results, **({"logical": True} if args.logical else {}))
     finally:
         if own_group:
             import torch.distributed as dist
