@@ -414,6 +414,8 @@ int qldpc_timing_read(double *total_ms, int64_t *launches);
  * schedule. Names (default):
  *   "force_hbm" (0)           every code through the HBM-resident kernel
  *   "flood_generic" (0)       flooding MS through decode_kernel, not ms_flood_kernel
+ *   "flood_qc" (1)            flooding MS of a lift-16 QC code with generated tables: the
+ *                             register-resident ms_flood_kernel (0: its LDS twin, ms_flood_lds_kernel)
  *   "layered_generic" (0)     layered MS through decode_kernel, not ms_layered_kernel
  *   "ms_lanes_per_check" (0)  layered MS: one lanes-per-check width for every layer (0: per layer)
  *   "bp_wave" (0)             BP through the one-wave decode_kernel, not the team kernels

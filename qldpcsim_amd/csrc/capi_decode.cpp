@@ -6,6 +6,7 @@
 
 #include "capi_internal.h"
 #include "../../include/qldpc_libm.h"   // after hip_runtime.h
+#include "qc_tables.h"
 #include "tuning.h"
 
 using namespace capi;
@@ -47,16 +48,56 @@ static void team_layout(const qldpc_code* c, int w, DecodeArgs* a) {
   a->wave_bytes = off;
 }
 
+// H's CSR (np.where order: ascending columns within a row) against table T
+// expanded: row 16 b + r holds columns 16 cvar[b][e] + (r + cshift[b][e]) % 16
+template <typename T>
+static bool qc_table_matches(const qldpc_code* c) {
+  constexpr int lift = qldpc::qc::kLift;
+  if (c->m != lift * T::MB || c->n != lift * T::NB || c->E != lift * T::MB * T::DC) return false;
+  for (int b = 0; b < T::MB; ++b)
+    for (int r = 0; r < lift; ++r) {
+      const int row = lift * b + r;
+      if (c->row_ptr[row + 1] - c->row_ptr[row] != T::DC) return false;
+      int cols[T::DC];
+      for (int e = 0; e < T::DC; ++e) cols[e] = lift * T::cvar[b][e] + (r + T::cshift[b][e]) % lift;
+      std::sort(cols, cols + T::DC);
+      for (int e = 0; e < T::DC; ++e)
+        if (c->col_idx[c->row_ptr[row] + e] != cols[e]) return false;
+    }
+  return true;
+}
+
+int capi::qc_table_of(const qldpc_code* c) {
+#define QLDPC_QC_MATCH(ID, T, NAME) \
+  if (qc_table_matches<T>(c)) return ID;
+  QLDPC_QC_TABLES(QLDPC_QC_MATCH)
+#undef QLDPC_QC_MATCH
+  return -1;
+}
+
 KernelChoice capi::choose_kernel(const qldpc_schedule* s, int algo) {
   const qldpc_code* c = s->code;
   const int dc = fast_table_ok(c) ? c->uniform_deg : 0;
   KernelChoice k;
   k.max_waves = QLDPC_MAX_THREADS / 64;
   if (algo == QLDPC_ALGO_MS && !s->layered && dc > 0 && !s->flood_ms.empty() && !opt(&Options::flood_generic)) {
-    k.kernel = qldpc::select_ms_flood_kernel(dc, (c->m + 63) / 64, &k.name);
+    const int kc = (c->m + 63) / 64;
+    k.kernel = qldpc::select_ms_flood_kernel(dc, kc, &k.name);
     if (k.kernel) {
       k.family = FAM_MS_FLOOD;
-      k.max_waves = qldpc::ms_flood_max_waves((c->m + 63) / 64);
+      k.max_waves = qldpc::ms_flood_max_waves(kc);
+    }
+    if (k.kernel && qldpc::ms_flood_kernel_is_qc(dc, kc)) {
+      // this shape's ms_flood_kernel is the register-resident kernel of the
+      // generated tables: for a code that is exactly one of them (option
+      // flood_qc = 0: never); every other code of the shape runs the LDS twin
+      k.qc_table = opt(&Options::flood_qc) ? qc_table_of(c) : -1;
+      if (k.qc_table >= 0) {
+        k.family = FAM_MS_FLOOD_QC;
+      } else {
+        k.kernel = qldpc::select_ms_flood_lds_kernel(dc, kc, &k.name);
+        if (!k.kernel) k.family = FAM_GENERIC, k.max_waves = QLDPC_MAX_THREADS / 64;
+      }
     }
   }
   if (!k.kernel && algo == QLDPC_ALGO_MS && s->layered && dc > 0 && !s->layered_ms.empty() &&
@@ -104,6 +145,15 @@ KernelChoice capi::choose_kernel(const qldpc_schedule* s, int algo) {
 
 int capi::plan_static(const qldpc_schedule* s, int algo, const KernelChoice& k, DecodeArgs* a) {
   const qldpc_code* c = s->code;
+  if (k.family == FAM_MS_FLOOD_QC) {
+    // no tables and no LDS: the graph is compiled into the kernel, the state lives in registers
+    a->qc_table = k.qc_table;
+    a->m = c->m, a->n = c->n, a->E = c->E, a->n_layers = s->n_layers;
+    a->wm = (c->m + 63) / 64, a->wn = (c->n + 63) / 64;
+    a->vinv = c->d_vinv;                              // (unread: outputs are in original order)
+    a->wave_bytes = 0;
+    return 0;
+  }
   const TableImage& t = k.family == FAM_MS_FLOOD     ? s->flood_ms
                         : k.family == FAM_MS_LAYERED ? s->layered_ms
                         : k.family == FAM_BP_TEAM_LG ? s->layered_bp
@@ -166,6 +216,7 @@ static int build_plan(qldpc_schedule* s, int algo, LaunchPlan* p) {
   if (!p->hbm) {
     const KernelChoice k = choose_kernel(s, algo);
     p->kernel = k.kernel, p->name = k.name, p->team = k.team;
+    p->hs_per_wave = k.family == FAM_MS_FLOOD_QC ? 4 : 1;
     const int image_lds = plan_static(s, algo, k, &p->args);
     HIP_TRY(qldpc::configure_kernel(k.kernel, max_lds));
     int best_waves = 0, max_waves = k.max_waves;
@@ -455,7 +506,7 @@ extern "C" int qldpc_decode_device_ex(const qldpc_code* code, const qldpc_schedu
     a.queue = sched->d_queue + (sched->qnext.fetch_add(1) % qldpc_schedule::kQueueSlots);
     HIP_TRY(hipMemsetAsync(a.queue, 0, sizeof(uint32_t), st));
   }
-  const int64_t per_block = plan.team ? 1 : (int64_t)plan.waves;
+  const int64_t per_block = plan.team ? 1 : (int64_t)plan.waves * plan.hs_per_wave;
   const int64_t need = (batch + per_block - 1) / per_block;
   const int64_t resident = (int64_t)plan.blocks_per_cu * plan.cus;
   const int grid = (int)std::max<int64_t>(1, std::min(need, resident));

@@ -41,7 +41,7 @@ int fail(int code, const char* fmt, ...);
 struct Options {
   std::atomic<int64_t> force_hbm{0}, flood_generic{0}, layered_generic{0}, ms_lanes_per_check{0}, bp_wave{0},
       bp_lg{1}, bp_team_w{0}, static_sched{0}, waves_per_wg{0}, wg_per_cu{0}, osd_column{0}, osd_tickets{1},
-      osd_prof{0}, osd_hbm{0}, logical_tabs{0};
+      osd_prof{0}, osd_hbm{0}, logical_tabs{0}, flood_qc{1};
   std::atomic<uint32_t> gen{1};
 };
 extern Options g_opt;
@@ -120,7 +120,7 @@ struct TableImage {
 // Launch plan of (schedule, algo) under one option generation: everything a
 // decode launch needs that does not depend on the call (capi_decode.cpp)
 // ---------------------------------------------------------------------------
-enum KernelFamily { FAM_GENERIC, FAM_MS_FLOOD, FAM_MS_LAYERED, FAM_BP_TEAM, FAM_BP_TEAM_LG };
+enum KernelFamily { FAM_GENERIC, FAM_MS_FLOOD, FAM_MS_FLOOD_QC, FAM_MS_LAYERED, FAM_BP_TEAM, FAM_BP_TEAM_LG };
 
 struct KernelChoice {
   const void* kernel = nullptr;
@@ -129,6 +129,7 @@ struct KernelChoice {
   int team = 0;             // BP teams: waves per half-shot (one workgroup), 0 = wave kernels
   int lanes = 0;            // ms_layered_kernel: lanes per check, 0 = chosen per layer
   int max_waves = 0;        // most waves per workgroup the kernel was compiled for
+  int qc_table = -1;        // FAM_MS_FLOOD_QC: the generated table H expands from (qc_tables.h)
 };
 
 struct LaunchPlan {
@@ -137,6 +138,7 @@ struct LaunchPlan {
   const char* name = "";
   int waves = 0, blocks_per_cu = 0, lds = 0;   // LDS kernels: waves per workgroup, workgroups per CU, LDS bytes
   int team = 0, cus = 0;    // BP teams: waves per half-shot; compute units of the device
+  int hs_per_wave = 1;      // half-shots a wave decodes at a time (register-resident ms_flood_kernel: 4)
   qldpc::DecodeArgs args{};  // every static field filled (LDS kernels)
   qldpc::HbmArgs hargs{};    // the same for hbm_tile_kernel
   int hbm_tiles_cap = 0;    // CUs x resident 64-slot tiles per CU
@@ -268,6 +270,9 @@ struct Gf2Basis {
 // capi_decode.cpp. choose_kernel and plan_static call no HIP function: the
 // static kernel arguments can be checked on a machine without a device.
 KernelChoice choose_kernel(const qldpc_schedule* s, int algo);
+// The generated protograph table (qc_tables.h) whose expansion is exactly the
+// code's H, or -1: compared entry by entry, not by shape or hash
+int qc_table_of(const qldpc_code* c);
 // Fills every static DecodeArgs field but off_libm (plan_lds); returns the
 // LDS bytes the kernel keeps in front of the state slices.
 int plan_static(const qldpc_schedule* s, int algo, const KernelChoice& k, qldpc::DecodeArgs* a);

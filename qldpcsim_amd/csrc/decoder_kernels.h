@@ -54,6 +54,7 @@ struct DecodeArgs {
   // 2 atanh(1 - eps) and the |x| >= 19.5 high-word threshold (0x7ff00000: off)
   double bp_csat;
   uint32_t bp_sat_hi;
+  int qc_table;               // register-resident ms_flood_kernel: which generated table (qc_tables.h)
 };
 
 // `name` (nullable) receives the kernel's name as rocprofv3 reports it
@@ -61,6 +62,10 @@ const void* select_kernel(int algo, bool layered, int dc, const char** name);
 // flooding MS, uniform row degree: global tables (fblob), LDS = wave state only
 const void* select_ms_flood_kernel(int dc, int kc, const char** name);  // nullptr if no instantiation fits
 int ms_flood_max_waves(int kc);                      // waves per workgroup it was compiled for
+// ms_flood_kernel<dc, kc> is the register-resident kernel of the lift-16 QC
+// codes with generated tables (no LDS, four half-shots per wave); its LDS twin
+bool ms_flood_kernel_is_qc(int dc, int kc);
+const void* select_ms_flood_lds_kernel(int dc, int kc, const char** name);
 // layered MS, uniform row degree 7/8, G = 1/2/4/8 lanes per check (layer-table blob)
 const void* select_ms_layered_kernel(int dc, int g, const char** name);
 // layered BP teams, every graph table in global memory (gblob of the schedule)

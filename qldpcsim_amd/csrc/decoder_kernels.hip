@@ -32,7 +32,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <utility>
+
 #include "decoder_kernels.h"
+#include "qc_tables.h"
 #include "tuning.h"
 #include "kargs.h"
 #include "../../include/qldpc_libm.h"
@@ -1119,9 +1122,10 @@ constexpr int ms_flood_max_threads() { return KC >= 8 ? 512 : 256; }
 template <int KC>
 constexpr int ms_flood_wpe() { return KC >= 8 ? 2 : QLDPC_FLOOD_WPE; }
 
+// The LDS-resident body described above: ms_flood_kernel's for every shape
+// without generated protograph tables, ms_flood_lds_kernel's for all.
 template <int DC, int KC>
-__global__ void __launch_bounds__(ms_flood_max_threads<KC>()) __attribute__((amdgpu_waves_per_eu(ms_flood_wpe<KC>())))
-ms_flood_kernel(DecodeArgs a) {
+__device__ __forceinline__ void ms_flood_lds_body(const DecodeArgs& a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   static_assert(DC >= 2 && DC <= 8, "row degree 2..8");
   const FloodRuns* runs = (const FloodRuns*)a.blob;                     // global, uniform
@@ -1240,6 +1244,49 @@ ms_flood_kernel(DecodeArgs a) {
     }
     wave_sync();
   }
+}
+
+#include "ms_flood_qc.h"   // flood_qc_body: the register-resident body (lift-16 QC codes)
+
+// A (DC, KC) shape some generated table has: ms_flood_kernel<DC, KC> is then
+// the register-resident kernel (256 VGPRs, two waves per SIMD, no LDS) and
+// DecodeArgs::qc_table names the table; codes of that shape that match no
+// table, and option flood_qc = 0, run the twin ms_flood_lds_kernel<DC, KC>.
+template <typename T, int DC, int KC>
+constexpr bool qc_table_fits() { return T::DC == DC && (16 * T::MB + 63) / 64 == KC; }
+template <int DC, int KC>
+constexpr bool ms_flood_is_qc() {
+  bool any = false;
+#define QLDPC_QC_ANY(ID, T, NAME) any = any || qc_table_fits<T, DC, KC>();
+  QLDPC_QC_TABLES(QLDPC_QC_ANY)
+#undef QLDPC_QC_ANY
+  return any;
+}
+template <int DC, int KC>
+constexpr int ms_flood_wpe2() { return ms_flood_is_qc<DC, KC>() ? 2 : ms_flood_wpe<KC>(); }
+
+template <int DC, int KC>
+__global__ void __launch_bounds__(ms_flood_max_threads<KC>())
+__attribute__((amdgpu_waves_per_eu(ms_flood_wpe2<DC, KC>()))) ms_flood_kernel(DecodeArgs a) {
+  if constexpr (ms_flood_is_qc<DC, KC>()) {
+    switch (a.qc_table) {                              // wave-uniform, outside every loop
+#define QLDPC_QC_CASE(ID, T, NAME) \
+  case ID:                         \
+    if constexpr (qc_table_fits<T, DC, KC>()) flood_qc_body<T>(a); \
+    break;
+      QLDPC_QC_TABLES(QLDPC_QC_CASE)
+#undef QLDPC_QC_CASE
+      default: break;
+    }
+  } else {
+    ms_flood_lds_body<DC, KC>(a);
+  }
+}
+
+template <int DC, int KC>
+__global__ void __launch_bounds__(ms_flood_max_threads<KC>()) __attribute__((amdgpu_waves_per_eu(ms_flood_wpe<KC>())))
+ms_flood_lds_kernel(DecodeArgs a) {
+  ms_flood_lds_body<DC, KC>(a);
 }
 
 // ---------------------------------------------------------------------------
@@ -2404,6 +2451,18 @@ const void* select_ms_flood_kernel(int dc, int kc, const char** name) {
   if (dc == 8 && kc <= 4) QLDPC_NAMED((&ms_flood_kernel<8, 4>), "ms_flood_kernel<8, 4>");
   if (dc == 7 && kc <= 8) QLDPC_NAMED((&ms_flood_kernel<7, 8>), "ms_flood_kernel<7, 8>");
   if (dc == 8 && kc <= 8) QLDPC_NAMED((&ms_flood_kernel<8, 8>), "ms_flood_kernel<8, 8>");
+  return nullptr;
+}
+
+bool ms_flood_kernel_is_qc(int dc, int kc) {
+  if (dc == 7) return kc <= 2 ? ms_flood_is_qc<7, 2>() : kc <= 4 ? ms_flood_is_qc<7, 4>() : ms_flood_is_qc<7, 8>();
+  if (dc == 8) return kc <= 2 ? ms_flood_is_qc<8, 2>() : kc <= 4 ? ms_flood_is_qc<8, 4>() : ms_flood_is_qc<8, 8>();
+  return false;
+}
+
+const void* select_ms_flood_lds_kernel(int dc, int kc, const char** name) {
+  // the LDS twins of the register-resident shapes
+  if (dc == 8 && kc > 2 && kc <= 4) QLDPC_NAMED((&ms_flood_lds_kernel<8, 4>), "ms_flood_lds_kernel<8, 4>");
   return nullptr;
 }
 

@@ -1,0 +1,323 @@
+// ms_flood_qc.h — the register-resident body of ms_flood_kernel for lift-16
+// quasi-cyclic codes. Included by decoder_kernels.hip inside
+// namespace qldpc, after the check-node helpers it shares with the LDS body.
+//
+// A code whose 16 x 16 blocks are zero or weight-1 circulants (qc_tables.h)
+// maps onto the DPP rows of a wave: lane = 16 q + k, row q decodes one
+// half-shot, lane k owns position k of every check block and of every
+// variable block. Per lane: MB x DC float32 messages (check block b, edge e)
+// and NB float32 column sums S; posterior = L + (double)S as the LDS body
+// forms it. A message exchange between check block b and variable block c is
+// a rotation inside the DPP row by the block's shift s:
+//   check position r  <->  variable position (r + s) % 16.
+// row_ror:n gives lane i the value of lane (i - n) % 16 of its row, so a check
+// reads its variable's S with n = (16 - s) % 16 and a variable reads its
+// check's message with n = s. No LDS, no addresses, no wave barriers.
+//
+// The four rows of a wave advance independently: each has its own iteration
+// count and stop test (ballot bits 16 q .. 16 q + 15); a row that finishes
+// writes its outputs and takes the next half-shot under an exec mask while
+// the others go on. Rotations never leave a row, so masked rows are harmless.
+// The arithmetic is cn_ms_compute's and vn_sum's, bit for bit; a row starts
+// with the messages of iteration 0 (every v2c = float32(L)) written directly,
+// as the LDS body's it == 0 branch writes them.
+
+template <typename F, int... I>
+__device__ __forceinline__ void static_for_seq(F&& f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, typename F>
+__device__ __forceinline__ void static_for(F&& f) {
+  static_for_seq(f, std::make_integer_sequence<int, N>{});
+}
+
+// lane i of a DPP row takes x of lane (i - N) % 16 (row_ror:N)
+template <int N>
+__device__ __forceinline__ float row_ror_f32(float x) {
+  if constexpr ((N & 15) == 0) {
+    return x;
+  } else {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x120 + (N & 15),
+                                                                 0xf, 0xf, true));
+  }
+}
+
+// 16-bit slice of a ballot that belongs to this lane's row (rowsh = lane & 48)
+__device__ __forceinline__ uint32_t row_bits(uint64_t b, int rowsh) {
+  const uint32_t half = (rowsh & 32) ? (uint32_t)(b >> 32) : (uint32_t)b;
+  return (half >> (rowsh & 16)) & 0xffffu;
+}
+
+// Work hand-out to the rows of a wave, HalfShotQueue's discipline with rows
+// as the consumers: every row starts with one static half-shot (its global
+// row index); with a queue, further half-shots come from the ticket counter
+// in guided chunks (about remaining / (4 * rows), at most 64, at least 1),
+// the next chunk claimed when the last half-shot of the current one is handed
+// out, so the atomic's latency hides behind that half-shot's decode.
+struct RowQueue {
+  long long cur, end, rows, batch;
+  uint32_t* q;
+  uint32_t tk, tlen, seen;
+  __device__ __forceinline__ RowQueue(const DecodeArgs& a, long long rows_, int lane)
+      : cur(0), end(0), rows(rows_), batch(a.batch), q(a.queue), tk(0), tlen(1), seen(0) {
+    if (q) claim(lane);
+  }
+  __device__ __forceinline__ void claim(int lane) {
+    const long long rem = batch - rows - (long long)seen;
+    long long len = rem / (4 * rows);
+    len = len < 1 ? 1 : (len > 64 ? 64 : len);
+    tlen = (uint32_t)len;
+    if (lane == 0) tk = atomicAdd(q, tlen);
+  }
+  __device__ __forceinline__ long long take(int lane) {   // wave-uniform
+    if (cur == end) {
+      const uint32_t t = __builtin_amdgcn_readfirstlane(tk);
+      seen = t + tlen;
+      cur = uniform64(rows + (long long)t);
+      end = uniform64(cur + tlen);
+    }
+    const long long h = cur;
+    cur = uniform64(cur + 1);
+    if (cur == end) claim(lane);
+    return h;
+  }
+};
+
+// Min-sum update of check block B (decoders.py:155-169 for the lane's check):
+// cn_ms_compute with the posteriors rotated in from S and the messages in
+// registers. Returns the check's "unsatisfied" bit for the posteriors it read.
+template <typename T, int B>
+__device__ __forceinline__ uint32_t qc_check(const DecodeArgs& a, double L, float (&S)[T::NB],
+                                             float (&c2v)[T::MB][T::DC], uint32_t synb, int& fl) {
+  constexpr int DC = T::DC;
+  // one check block's working set at a time: the inputs are pinned behind the
+  // previous block's outputs (volatile asm statements keep their order), so no
+  // widened copy of a later block's operands is formed ahead of its turn
+  static_for<DC>([&](auto E) __attribute__((always_inline)) {
+    float &sx = S[T::cvar[B][E]], &cx = c2v[B][E];      // (named: asm operands alone do not capture)
+    asm volatile("" : "+v"(sx), "+v"(cx));
+  });
+  double v[DC];
+  uint32_t hv[DC], hp[DC];
+  static_for<DC>([&](auto E) __attribute__((always_inline)) {
+    constexpr int e = E, c = T::cvar[B][e], s = T::cshift[B][e];
+    const double post = L + (double)row_ror_f32<(16 - s) & 15>(S[c]);
+    v[e] = post - (double)c2v[B][e];                      // v2c = post - c2v (:177)
+    hv[e] = hi_word(v[e]);
+    hp[e] = hi_word(post);
+  });
+  double min1, min2;                                      // first min / min of the rest (:160-164)
+  min12_tree<DC>(v, min1, min2);
+  const uint32_t ph = xor_tree<DC>(hp);                   // hard-decision parity (:174)
+  const uint32_t sh = xor_tree<DC>(hv);                   // np.sign product (:157-159)
+  double m1 = min1, m2 = min2;
+  if (__builtin_expect(ballot((min1 == 0.0) | (min2 == __builtin_inf())) != 0, 0)) {
+    m1 = __builtin_isinf(min1) ? 0.0 : min1;              // (:165)
+    m2 = __builtin_isinf(min2) ? 0.0 : min2;              // (:166)
+    if (m1 == 0.0) fl |= FLAG_MIN_ZERO;
+  }
+  const uint32_t npm = ((sh >> 31) ^ synb) << 31;
+  const uint32_t c1n = opaque_always(__builtin_bit_cast(uint32_t, (float)(a.beta * m1)) ^ npm);
+  const uint32_t c2n = opaque_always(__builtin_bit_cast(uint32_t, (float)(a.beta * m2)) ^ npm);
+  static_for<DC>([&](auto E) __attribute__((always_inline)) {
+    constexpr int e = E;
+    const uint32_t c = (__builtin_fabs(v[e]) == min1) ? c2n : c1n;
+    c2v[B][e] = __builtin_bit_cast(float, c ^ (hv[e] & 0x80000000u));
+  });
+  uint32_t unsat = (ph >> 31) ^ synb;
+  static_for<DC>([&](auto E) __attribute__((always_inline)) {
+    float& cx = c2v[B][E];
+    asm volatile("" : "+v"(cx));
+  });
+  asm volatile("" : "+v"(unsat));
+  return unsat;
+}
+
+// lane i of a DPP row takes x of lane (i - N) % 16 (row_ror:N)
+template <int N>
+__device__ __forceinline__ uint32_t row_ror_u32(uint32_t x) {
+  if constexpr ((N & 15) == 0) {
+    return x;
+  } else {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x120 + (N & 15), 0xf, 0xf, true);
+  }
+}
+
+// parity of check block B's hard decisions XOR its syndrome bit (the stop
+// test after the last iteration, decoders.py:174-176); hw: this lane's hard
+// decisions, bit c & 31 of word c >> 5 for variable block c
+template <typename T, int B>
+__device__ __forceinline__ uint32_t qc_parity(const uint32_t (&hw)[(T::NB + 31) / 32], uint32_t synb) {
+  uint32_t ph = synb;
+  static_for<T::DC>([&](auto E) __attribute__((always_inline)) {
+    constexpr int e = E, c = T::cvar[B][e], s = T::cshift[B][e];
+    ph ^= row_ror_u32<(16 - s) & 15>(hw[c >> 5]) >> (c & 31);
+  });
+  ph &= 1u;
+  asm volatile("" : "+v"(ph));                            // one check block at a time
+  return ph;
+}
+
+// S_c = sum of variable block C's messages in ascending check order, float32,
+// starting from the first term (vn_sum)
+template <typename T, int C>
+__device__ __forceinline__ float qc_colsum(const float (&c2v)[T::MB][T::DC]) {
+  float s = row_ror_f32<T::vshift[C][0]>(c2v[T::vchk[C][0]][T::vslot[C][0]]);
+  static_for<T::vdeg[C] - 1>([&](auto I) __attribute__((always_inline)) {
+    constexpr int t = I + 1;
+    s = s + row_ror_f32<T::vshift[C][t]>(c2v[T::vchk[C][t]][T::vslot[C][t]]);
+  });
+  return s;
+}
+
+template <typename T>
+__device__ __forceinline__ void flood_qc_body(const DecodeArgs& a) {
+  constexpr int MB = T::MB, NB = T::NB, DC = T::DC;
+  static_assert(qc::kLift == 16, "one DPP row per half-shot");
+  const int lane = threadIdx.x & 63;
+  const int k = lane & 15, q = lane >> 4, rowsh = lane & 48;
+  const int waves = blockDim.x >> 6;
+  const long long rows = 4ll * gridDim.x * waves;
+  const long long batch = a.batch;
+  constexpr int n = 16 * NB, m = 16 * MB;
+  constexpr int wn = (n + 63) / 64;
+
+  float c2v[MB][DC], S[NB];
+  int it = 0, fl = 0;
+  uint32_t synreg = 0;
+  long long hs = 4ll * ((long long)blockIdx.x * waves + (threadIdx.x >> 6)) + q;
+  RowQueue Q(a, rows, lane);
+  // One trip: finished rows write their outputs, take their next half-shot and
+  // start it (the messages of iteration 0); then every live row's VN pass; then
+  // the CN pass with the stop test. A row that reaches max_iter in its VN pass
+  // sits out that trip's CN pass; either way a finished row joins the next VN
+  // pass with its new half-shot, so a half-shot of i iterations costs i trips.
+  bool live = false, fin = true;         // fin: rows to (re)start; at first all, on their static half-shot
+  bool conv = false;
+  int iters = 0;
+  bool started = false;                  // wave-uniform
+
+  for (;;) {
+    const uint64_t finb = ballot_b(fin);
+    if (finb != 0) {
+      if (started) {
+        if (fin) {
+          // outputs in original variable order: column 16 c + k is this lane's S[c].
+          // Arguments and lane offsets used only here are formed here: read afresh
+          // (kargs_fresh) and behind an opaque lane, they hold no registers in the loop
+          const DecodeArgs& f = kargs_fresh();
+          int kl = k, rsh = rowsh;
+          asm volatile("" : "+v"(kl), "+v"(rsh));
+          // (each posterior formed where it is used: NB doubles at once do not fit the registers)
+          if (f.eh_bits) {
+            // word w of this row: blocks 4 w .. 4 w + 3, 16 ballot bits each; lane k = w stores it
+            uint32_t lo = 0, hi = 0;
+            static_for<wn>([&](auto W) __attribute__((always_inline)) {
+              uint32_t r[4] = {0, 0, 0, 0};
+              static_for<4>([&](auto I) __attribute__((always_inline)) {
+                constexpr int c = 4 * W + I;
+                if constexpr (c < NB) r[I] = row_bits(ballot_b(a.L + (double)S[c] < 0.0), rsh);
+              });
+              if (kl == W) lo = r[0] | (r[1] << 16), hi = r[2] | (r[3] << 16);
+            });
+            if (kl < wn) ((uint64_t*)f.ehat)[hs * wn + kl] = ((uint64_t)hi << 32) | lo;
+          } else {
+            uint8_t* eo = f.ehat + hs * (long long)n + kl;
+            static_for<NB>([&](auto C) __attribute__((always_inline)) {
+              eo[16 * C] = (uint8_t)(a.L + (double)S[C] < 0.0);
+            });
+          }
+          if (f.post) {
+            double* po = f.post + hs * (long long)n + kl;
+            static_for<NB>([&](auto C) __attribute__((always_inline)) { po[16 * C] = a.L + (double)S[C]; });
+          }
+          const bool mz = row_bits(ballot_b((fl & FLAG_MIN_ZERO) != 0), rsh) != 0;
+          if (kl == 0) {
+            f.iters[hs] = iters;
+            if (f.flags) f.flags[hs] = (int32_t)((mz ? FLAG_MIN_ZERO : 0) | (conv ? FLAG_CONVERGED : 0));
+          }
+        }
+        // the finished rows' next half-shots
+        if (Q.q) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            if ((finb >> (16 * r)) & 1u) {
+              const long long h = Q.take(lane);
+              if (q == r) hs = h;
+            }
+          }
+        } else if (fin) {
+          hs += rows;
+        }
+      }
+      started = true;
+      if (fin) {
+        // start this row on half-shot hs with the messages of iteration 0:
+        // every v2c = float32(L) (decoders.py:148-149), one value per check
+        live = hs < batch;
+        it = 0, synreg = 0;
+        if (live) {
+          const DecodeArgs& f = kargs_fresh();
+          int kl = k;
+          asm volatile("" : "+v"(kl));
+          if (f.syn_bits) {              // 64-bit words: check 16 b + k is bit 16 (b & 1) + k of half-word b >> 1
+            const uint32_t* row = (const uint32_t*)((const uint64_t*)f.syn + hs * f.wm);
+            uint32_t w[(MB + 1) / 2];
+#pragma unroll
+            for (int i = 0; i < (MB + 1) / 2; ++i) w[i] = row[i];
+#pragma unroll
+            for (int b = 0; b < MB; ++b) synreg |= ((w[b >> 1] >> (16 * (b & 1) + kl)) & 1u) << b;
+          } else {
+            const uint8_t* row = f.syn + hs * (long long)m + kl;
+            uint32_t w[MB];
+#pragma unroll
+            for (int b = 0; b < MB; ++b) w[b] = row[16 * b];
+#pragma unroll
+            for (int b = 0; b < MB; ++b) synreg |= (w[b] & 1u) << b;
+          }
+        }
+        const double vf = (double)a.L32;
+        const double av = __builtin_fabs(vf);
+        const uint32_t cb = __builtin_bit_cast(uint32_t, (float)(a.beta * av));
+        const uint32_t neg = (uint32_t)(vf < 0.0);
+        fl = av == 0.0 ? FLAG_MIN_ZERO : 0;
+        static_for<MB>([&](auto B) __attribute__((always_inline)) {
+          const uint32_t negprod = ((neg * DC) ^ (synreg >> B)) & 1u;
+          const float val = __builtin_bit_cast(float, cb | ((neg ^ negprod) << 31));
+          static_for<DC>([&](auto E) __attribute__((always_inline)) { c2v[B][E] = val; });
+        });
+        fin = false;
+      }
+    }
+    if (ballot_b(live) == 0) break;
+
+    if (live) {
+      static_for<NB>([&](auto C) __attribute__((always_inline)) {
+        float& sc = S[C];
+        sc = qc_colsum<T, C>(c2v);
+        asm volatile("" : "+v"(sc));                      // one variable block at a time
+      });
+      it += 1;
+      if (it == a.max_iter) {
+        uint32_t hw[(NB + 31) / 32] = {};
+        static_for<NB>([&](auto C) __attribute__((always_inline)) {
+          hw[C / 32] |= (hi_word(a.L + (double)S[C]) >> 31) << (C % 32);
+        });
+        uint32_t un = 0;
+        static_for<MB>([&](auto B) __attribute__((always_inline)) {
+          un |= qc_parity<T, B>(hw, (synreg >> B) & 1u);
+        });
+        fin = true, iters = it;
+        conv = row_bits(ballot_b(un != 0), rowsh) == 0;
+      }
+    }
+    if (live && !fin) {
+      uint32_t unsat = 0;
+      static_for<MB>([&](auto B) __attribute__((always_inline)) {
+        unsat |= qc_check<T, B>(a, a.L, S, c2v, (synreg >> B) & 1u, fl);
+      });
+      // stop test of iteration it - 1 (decoders.py:175-176)
+      if (row_bits(ballot_b(unsat != 0), rowsh) == 0) fin = true, conv = true, iters = it;
+    }
+  }
+}

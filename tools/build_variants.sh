@@ -5,6 +5,10 @@ set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 while [ $# -ge 2 ]; do
   name=$1; flags=$2; shift 2
+  # a variant links objects of its own (the BP team and flooding min-sum
+  # translation units): stale ones from an earlier build under the same name
+  # would be reused, archived sources carrying old mtimes
+  rm -f "$ROOT/qldpcsim_amd/_build/var_${name}_ms_flood.o" "$ROOT/qldpcsim_amd/_build/var_${name}_bp_team.o"
   if [ "$flags" = "HEAD" ]; then
     tmp=$(mktemp -d)
     (cd "$ROOT" && git archive HEAD qldpcsim_amd/csrc include) | tar -x -C "$tmp"
