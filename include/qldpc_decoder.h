@@ -166,6 +166,42 @@ int qldpc_decode_host(const qldpc_code *code, const qldpc_schedule *sched, int a
                       double eps, uint8_t *h_ehat, int32_t *h_iters, double *h_post,
                       int32_t *h_flags);
 
+/* qldpc_decode_device_ex with a two-level prior per half-shot (correlated
+ * X/Z decoding of depolarizing noise: the first half's estimate is the second
+ * half's mask). No reference counterpart.
+ *   d_mask   one bit per variable, original column order, in mask_format:
+ *            uint8 [batch][n] (0/1) or uint64 [batch][ceil(n/64)], the layouts
+ *            of d_ehat; it may be an earlier decode's d_ehat, not this call's
+ *   p0, p1   variable j decodes with the prior L0 = log((1-p0)/max(p0, eps))
+ *            where its mask bit is 0 and L1 (of p1) where it is 1; both must
+ *            lie in [0, 1] (QLDPC_EINVAL otherwise; p1 = 0.5 gives L1 = +0.0:
+ *            min-sum then sets QLDPC_FLAG_MIN_ZERO, BP divides 0 by 0 as the
+ *            reference would and sets QLDPC_FLAG_NONFINITE)
+ * The arithmetic is the scalar decode's with L replaced by the variable's own
+ * L_j everywhere (the float32(L_j) first pass of min-sum included); with
+ * p0 == p1 every output equals the scalar decode's bit for bit, whatever the
+ * mask. Runs decode_prior_kernel, the generic LDS kernel's twin: QLDPC_EUNSUP,
+ * before any launch, for a code that kernel cannot hold (m, n or edges >
+ * 65535, MS row degree > 32, BP column degree > 128, state past the LDS) or
+ * with option "force_hbm" set; there is no HBM-resident variant. Arguments are
+ * checked before any HIP call. */
+int qldpc_decode_device_prior(const qldpc_code *code, const qldpc_schedule *sched, int algo, const void *d_syn,
+                              int syn_format, int64_t batch, double p0, double p1, const void *d_mask,
+                              int mask_format, int max_iter, double beta, double eps, void *d_ehat,
+                              int ehat_format, int32_t *d_iters, double *d_post, int32_t *d_flags, void *stream);
+
+/* Same with host buffers and a byte mask (uint8 [batch][n]), staged like
+ * qldpc_decode_host. */
+int qldpc_decode_host_prior(const qldpc_code *code, const qldpc_schedule *sched, int algo, const uint8_t *h_syn,
+                            int64_t batch, double p0, double p1, const uint8_t *h_mask, int max_iter,
+                            double beta, double eps, uint8_t *h_ehat, int32_t *h_iters, double *h_post,
+                            int32_t *h_flags);
+
+/* Name of the kernel qldpc_decode_device_prior launches, as rocprofv3 reports
+ * it (e.g. "decode_prior_kernel<0, false, 8>"); needs no device. */
+int qldpc_decode_prior_kernel_name(const qldpc_code *code, const qldpc_schedule *sched, int algo, char *buf,
+                                   int len);
+
 /* The hard-decision decoders, batched, device pointers, asynchronous on
  * `stream`. Replaces `batch` calls of NG_decoder(H, syndrome)
  * (decoders.py:27-66) or BF_decoder(H, syndrome, max_iter) (:74-102) — what

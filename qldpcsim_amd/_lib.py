@@ -27,6 +27,7 @@ EXPORTS = (
     "qldpc_schedule_create", "qldpc_schedule_destroy", "qldpc_schedule_release_workspace",
     "qldpc_decode_device", "qldpc_decode_device_ex", "qldpc_decode_host", "qldpc_decode_kernel_name",
     "qldpc_decode_launch_info",
+    "qldpc_decode_device_prior", "qldpc_decode_host_prior", "qldpc_decode_prior_kernel_name",
     "qldpc_hard_decode_device", "qldpc_hard_decode_host", "qldpc_hard_kernel_name", "qldpc_hard_launch_info",
     "qldpc_osd_decode", "qldpc_osd_decode_batch", "qldpc_osd_device", "qldpc_osd_order_device",
     "qldpc_osd_device_ordered", "qldpc_osd_device_ordered_ex", "qldpc_cpython_setdiff_first",
@@ -75,6 +76,9 @@ def _load():
         "qldpc_decode_host": ([P, P, I, P, I64, D, I, D, D, P, P, P, P], I),
         "qldpc_decode_kernel_name": ([P, P, I, ctypes.c_char_p, I], I),
         "qldpc_decode_launch_info": ([P, P, I, ctypes.POINTER(I), ctypes.POINTER(I), ctypes.POINTER(I)], I),
+        "qldpc_decode_device_prior": ([P, P, I, P, I, I64, D, D, P, I, I, D, D, P, I, P, P, P, P], I),
+        "qldpc_decode_host_prior": ([P, P, I, P, I64, D, D, P, I, D, D, P, P, P, P], I),
+        "qldpc_decode_prior_kernel_name": ([P, P, I, ctypes.c_char_p, I], I),
         "qldpc_hard_decode_device": ([P, I, P, I, I64, I, P, I, P, P, P], I),
         "qldpc_hard_decode_host": ([P, I, P, I64, I, P, P, P], I),
         "qldpc_hard_kernel_name": ([P, I, ctypes.c_char_p, I], I),
@@ -295,6 +299,16 @@ def kernel_name(H, layer_ptr, layer_rows, algo, device_index=None):
     sched = code.schedule(layer_ptr, layer_rows)
     buf = ctypes.create_string_buffer(128)
     check(lib.qldpc_decode_kernel_name(code.handle, sched.handle, ALGO[algo], buf, 128))
+    return buf.value.decode()
+
+
+def prior_kernel_name(H, layer_ptr, layer_rows, algo, device_index=None):
+    """Name of the kernel a decode with prior_mask launches for (H, schedule,
+    algo): decode_prior_kernel<...> (NotImplementedError where it cannot run)."""
+    code = code_for(H, device_index)
+    sched = code.schedule(layer_ptr, layer_rows)
+    buf = ctypes.create_string_buffer(128)
+    check(lib.qldpc_decode_prior_kernel_name(code.handle, sched.handle, ALGO[algo], buf, 128))
     return buf.value.decode()
 
 

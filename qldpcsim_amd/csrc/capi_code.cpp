@@ -75,6 +75,7 @@ extern "C" int qldpc_code_create(const uint8_t* h_H, int m, int n, qldpc_code** 
     hipError_t e1 = hipSuccess;
     auto up = [&](auto& d, const auto& h) { e1 = e1 == hipSuccess ? d.upload(h) : e1; };
     if (c->lds_ok) up(c->d_vinv, std::vector<uint16_t>(c->vinv.begin(), c->vinv.end()));
+    if (c->lds_ok) up(c->d_vperm, std::vector<uint16_t>(c->vperm.begin(), c->vperm.end()));
     {  // HBM-resident kernel tables
       std::vector<int32_t> rv(c->E), rp(c->E);
       for (int e = 0; e < c->E; ++e) {

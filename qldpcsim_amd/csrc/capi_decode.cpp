@@ -18,8 +18,9 @@ using qldpc::DecodeArgs;
 // per-wave state slice: post f64[n] | c2v (f32|f64)[E] | syn words | parity words
 // (ms_layered_kernel, colsum_f32: the "parity words" slot holds the syndrome
 // bits in layer order instead, 2 ceil(synl_rows / 64) words; the lane-group
-// instance <DC, 0> only)
-static void wave_layout(const qldpc_code* c, bool layered, int algo, bool colsum_f32, int synl_rows, DecodeArgs* a) {
+// instance <DC, 0> only; decode_prior_kernel: selector words behind them)
+static void wave_layout(const qldpc_code* c, bool layered, int algo, bool colsum_f32, int synl_rows, bool prior,
+                        DecodeArgs* a) {
   int off = align16((colsum_f32 ? 4 : 8) * c->n);   // post f64, or ms_layered_kernel's float32 sums
   a->off_c2v = off;
   off = align16(off + (algo == QLDPC_ALGO_MS ? 4 : 8) * (c->E + 8));  // +8: VN over-read pad
@@ -29,6 +30,8 @@ static void wave_layout(const qldpc_code* c, bool layered, int algo, bool colsum
   a->off_parw = off;
   if (layered && !colsum_f32) off = align16(off + 4 * words);
   if (layered && colsum_f32) off = align16(off + 4 * 2 * ((synl_rows + 63) / 64));
+  a->off_selw = off;
+  if (prior) off = align16(off + 4 * 2 * ((c->n + 63) / 64));
   a->wave_bytes = std::max(off, 16);
 }
 
@@ -143,6 +146,24 @@ KernelChoice capi::choose_kernel(const qldpc_schedule* s, int algo) {
   return k;
 }
 
+int capi::choose_prior_kernel(const qldpc_schedule* s, int algo, KernelChoice* k) {
+  const qldpc_code* c = s->code;
+  if (!s->lds_ok)
+    return fail(QLDPC_EUNSUP, "two-level priors: %d x %d with %d edges is past the LDS kernels' 16-bit tables "
+                "(m, n, edges, layer rows <= 65535); there is no HBM-resident variant", c->m, c->n, c->E);
+  if (algo == QLDPC_ALGO_MS && c->max_row_deg > 32)
+    return fail(QLDPC_EUNSUP, "two-level priors: MS row degree %d > 32 has no LDS kernel", c->max_row_deg);
+  if (algo == QLDPC_ALGO_BP && c->max_col_deg > 128)
+    return fail(QLDPC_EUNSUP, "two-level priors: BP column degree %d > 128 has no LDS kernel", c->max_col_deg);
+  if (opt(&Options::force_hbm) != 0)
+    return fail(QLDPC_EUNSUP, "two-level priors: option force_hbm is set and there is no HBM-resident variant");
+  *k = KernelChoice{};
+  k->max_waves = QLDPC_MAX_THREADS / 64;
+  k->prior = true;
+  k->kernel = qldpc::select_prior_kernel(algo, s->layered, fast_table_ok(c) ? c->uniform_deg : 0, &k->name);
+  return QLDPC_OK;
+}
+
 int capi::plan_static(const qldpc_schedule* s, int algo, const KernelChoice& k, DecodeArgs* a) {
   const qldpc_code* c = s->code;
   if (k.family == FAM_MS_FLOOD_QC) {
@@ -172,11 +193,12 @@ int capi::plan_static(const qldpc_schedule* s, int algo, const KernelChoice& k, 
   a->off_vn_chk = t.off.vn_chk, a->off_lay_ptr = t.off.lay_ptr, a->off_lay_rows = t.off.lay_rows;
   a->off_adj_ptr = t.off.adj_ptr, a->off_adj_vars = t.off.adj_vars, a->off_chunk_dmax = t.off.chunk_dmax;
   const bool msl = k.family == FAM_MS_LAYERED;
-  wave_layout(c, s->layered, algo, msl, msl && k.lanes == 0 ? (int)s->h_lay_rows.size() : 0, a);
+  wave_layout(c, s->layered, algo, msl, msl && k.lanes == 0 ? (int)s->h_lay_rows.size() : 0, k.prior, a);
   if (k.team) team_layout(c, k.team, a);
   a->m = c->m, a->n = c->n, a->E = c->E, a->n_layers = s->n_layers;
   a->wm = (c->m + 63) / 64, a->wn = (c->n + 63) / 64;
   a->vinv = c->d_vinv, a->wc = c->d_wc, a->rtab = c->d_rtab, a->avar = c->d_avar;
+  a->vperm = c->d_vperm;
   a->filt_all = c->filt_all;
   return image_lds;
 }
@@ -202,7 +224,7 @@ void capi::plan_static_hbm(const qldpc_schedule* s, qldpc::HbmArgs* a) {
 // ---------------------------------------------------------------------------
 // launch plan, device half: occupancy, and the cache under the schedule's lock
 // ---------------------------------------------------------------------------
-static int build_plan(qldpc_schedule* s, int algo, LaunchPlan* p) {
+static int build_plan(qldpc_schedule* s, int algo, bool prior, LaunchPlan* p) {
   const qldpc_code* c = s->code;
   int dev = 0, max_lds = 0;
   HIP_TRY(hipGetDevice(&dev));
@@ -213,8 +235,13 @@ static int build_plan(qldpc_schedule* s, int algo, LaunchPlan* p) {
   // HBM kernel for any code (tests: the two families agree bit for bit).
   p->hbm = !s->lds_ok || opt(&Options::force_hbm) != 0 || (algo == QLDPC_ALGO_MS && c->max_row_deg > 32) ||
            (algo == QLDPC_ALGO_BP && c->max_col_deg > 128);
+  KernelChoice pk;
+  if (prior) {                                        // decode_prior_kernel or nothing
+    if (int rc = choose_prior_kernel(s, algo, &pk)) return rc;
+    p->hbm = false;
+  }
   if (!p->hbm) {
-    const KernelChoice k = choose_kernel(s, algo);
+    const KernelChoice k = prior ? pk : choose_kernel(s, algo);
     p->kernel = k.kernel, p->name = k.name, p->team = k.team;
     p->hs_per_wave = k.family == FAM_MS_FLOOD_QC ? 4 : 1;
     const int image_lds = plan_static(s, algo, k, &p->args);
@@ -254,6 +281,9 @@ static int build_plan(qldpc_schedule* s, int algo, LaunchPlan* p) {
     // no LDS kernel holds the graph's per-half-shot state and tables: the
     // HBM-resident kernel decodes it; decided once per plan, not per launch
     p->hbm = best_waves == 0;
+    if (prior && p->hbm)
+      return fail(QLDPC_EUNSUP, "two-level priors: the tables and one wave's state (%d + %d B) do not fit the %d B "
+                  "of LDS; there is no HBM-resident variant", image_lds, p->args.wave_bytes, max_lds);
   }
   if (p->hbm) {
     p->kernel = qldpc::select_hbm_kernel(algo, c->max_row_deg, &p->name);
@@ -269,21 +299,22 @@ static int build_plan(qldpc_schedule* s, int algo, LaunchPlan* p) {
 // The one validating way to a plan: copied into *out under the schedule's
 // lock, so a launch keeps its own consistent snapshot even if an option change
 // (qldpc_set_option) rebuilds the cached one meanwhile.
-static int resolve_plan(const qldpc_code* code, qldpc_schedule* s, int algo, LaunchPlan* out) {
+static int resolve_plan(const qldpc_code* code, qldpc_schedule* s, int algo, LaunchPlan* out, bool prior = false) {
   if (algo != QLDPC_ALGO_MS && algo != QLDPC_ALGO_BP) return fail(QLDPC_EINVAL, "Unrecognized decoder type.");
   if (code->device < 0 || !s->generic.dev)
     return fail(QLDPC_EHIP, "no HIP device was visible when the code/schedule was created");
   std::lock_guard<std::mutex> lk(s->mu);
   const uint32_t gen = g_opt.gen.load();
-  if (!s->plan[algo].ok || s->plan[algo].gen != gen) {
+  LaunchPlan& slot = prior ? s->prior_plan[algo] : s->plan[algo];
+  if (!slot.ok || slot.gen != gen) {
     LaunchPlan p{};                                   // built aside, published whole
-    const int rc = build_plan(s, algo, &p);
+    const int rc = build_plan(s, algo, prior, &p);
     if (rc) return rc;
     p.ok = true;
     p.gen = gen;
-    s->plan[algo] = p;
+    slot = p;
   }
-  *out = s->plan[algo];
+  *out = slot;
   return QLDPC_OK;
 }
 
@@ -452,10 +483,34 @@ static void bp_saturation(double eps, double* csat, uint32_t* sat_hi) {
   *sat_hi = on ? 0x40338000u : 0x7ff00000u;            // |x| >= 19.5 (high word, sign cleared)
 }
 
-extern "C" int qldpc_decode_device_ex(const qldpc_code* code, const qldpc_schedule* sched_c, int algo,
-                                      const void* d_syn, int syn_format, int64_t batch, double p, int max_iter,
-                                      double beta, double eps, void* d_ehat, int ehat_format, int32_t* d_iters,
-                                      double* d_post, int32_t* d_flags, void* stream) {
+// the two-level prior of qldpc_decode_device_prior: variables whose mask bit is
+// set take p1 (the others the call's p)
+struct PriorCall {
+  double p1;
+  const void* mask;
+  int mask_format;
+};
+
+// everything qldpc_decode_device_prior checks on top of the scalar entry,
+// before any HIP call
+static int validate_prior(const qldpc_code* code, const qldpc_schedule* sched, int algo, int64_t batch, double p0,
+                          const PriorCall& pr) {
+  if (pr.mask_format != QLDPC_FMT_BYTES && pr.mask_format != QLDPC_FMT_BITS)
+    return fail(QLDPC_EINVAL, "unknown mask format");
+  if (!(p0 >= 0.0 && p0 <= 1.0) || !(pr.p1 >= 0.0 && pr.p1 <= 1.0))
+    return fail(QLDPC_EINVAL, "two-level priors: p0 and p1 must be probabilities (0 <= p <= 1)");
+  if (batch > 0 && !pr.mask) return fail(QLDPC_EINVAL, "null mask");
+  if (code && sched && sched->code == code && (algo == QLDPC_ALGO_MS || algo == QLDPC_ALGO_BP)) {
+    KernelChoice k;
+    if (int rc = choose_prior_kernel(sched, algo, &k)) return rc;
+  }
+  return QLDPC_OK;
+}
+
+static int decode_device(const qldpc_code* code, const qldpc_schedule* sched_c, int algo,
+                         const void* d_syn, int syn_format, int64_t batch, double p, int max_iter,
+                         double beta, double eps, void* d_ehat, int ehat_format, int32_t* d_iters,
+                         double* d_post, int32_t* d_flags, void* stream, const PriorCall* pr) {
   auto* sched = const_cast<qldpc_schedule*>(sched_c);
   if ((syn_format != QLDPC_FMT_BYTES && syn_format != QLDPC_FMT_BITS) ||
       (ehat_format != QLDPC_FMT_BYTES && ehat_format != QLDPC_FMT_BITS))
@@ -465,6 +520,8 @@ extern "C" int qldpc_decode_device_ex(const qldpc_code* code, const qldpc_schedu
   if (algo != QLDPC_ALGO_MS && algo != QLDPC_ALGO_BP) return fail(QLDPC_EINVAL, "Unrecognized decoder type.");
   if (batch < 0) return fail(QLDPC_EINVAL, "negative batch");
   if (max_iter < 1) return fail(QLDPC_EINVAL, "max_iter must be >= 1 (the reference leaves e_hat unbound)");
+  if (pr)
+    if (int rc = validate_prior(code, sched, algo, batch, p, *pr)) return rc;
   if (batch == 0) return QLDPC_OK;
   if (!d_syn || !d_ehat || !d_iters) return fail(QLDPC_EINVAL, "null device buffer");
   if (code->device < 0 || !sched->generic.dev)
@@ -473,7 +530,7 @@ extern "C" int qldpc_decode_device_ex(const qldpc_code* code, const qldpc_schedu
   HIP_TRY(hipGetDevice(&dev));
   if (dev != code->device) return fail(QLDPC_EINVAL, "code lives on device %d, current device is %d", code->device, dev);
   LaunchPlan plan;
-  if (int rc = resolve_plan(code, sched, algo, &plan)) return rc;
+  if (int rc = resolve_plan(code, sched, algo, &plan, pr != nullptr)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (plan.hbm)
     return decode_hbm(code, sched, algo, plan,
@@ -490,6 +547,11 @@ extern "C" int qldpc_decode_device_ex(const qldpc_code* code, const qldpc_schedu
   // the last bit for ~0.2 % of priors
   a.L = qldpc_prior_llr(p, eps);
   a.L32 = (float)a.L;
+  if (pr) {
+    a.L1 = qldpc_prior_llr(pr->p1, eps);
+    a.pmask = pr->mask;
+    a.pmask_bits = pr->mask_format == QLDPC_FMT_BITS;
+  }
   a.beta = beta, a.eps = eps;
   bp_saturation(eps, &a.bp_csat, &a.bp_sat_hi);
   a.max_iter = max_iter;
@@ -514,6 +576,35 @@ extern "C" int qldpc_decode_device_ex(const qldpc_code* code, const qldpc_schedu
   if (int rc = timing_begin(&t, st)) return rc;
   HIP_TRY(qldpc::launch_decode(plan.kernel, a, grid, 64 * plan.waves, plan.lds, st));
   return timing_end(&t, st);
+}
+
+extern "C" int qldpc_decode_device_ex(const qldpc_code* code, const qldpc_schedule* sched, int algo,
+                                      const void* d_syn, int syn_format, int64_t batch, double p, int max_iter,
+                                      double beta, double eps, void* d_ehat, int ehat_format, int32_t* d_iters,
+                                      double* d_post, int32_t* d_flags, void* stream) {
+  return decode_device(code, sched, algo, d_syn, syn_format, batch, p, max_iter, beta, eps, d_ehat, ehat_format,
+                       d_iters, d_post, d_flags, stream, nullptr);
+}
+
+extern "C" int qldpc_decode_device_prior(const qldpc_code* code, const qldpc_schedule* sched, int algo,
+                                         const void* d_syn, int syn_format, int64_t batch, double p0, double p1,
+                                         const void* d_mask, int mask_format, int max_iter, double beta, double eps,
+                                         void* d_ehat, int ehat_format, int32_t* d_iters, double* d_post,
+                                         int32_t* d_flags, void* stream) {
+  const PriorCall pr{p1, d_mask, mask_format};
+  return decode_device(code, sched, algo, d_syn, syn_format, batch, p0, max_iter, beta, eps, d_ehat, ehat_format,
+                       d_iters, d_post, d_flags, stream, &pr);
+}
+
+extern "C" int qldpc_decode_prior_kernel_name(const qldpc_code* code, const qldpc_schedule* sched, int algo,
+                                              char* buf, int len) {
+  if (!code || !sched || !buf || len <= 0) return fail(QLDPC_EINVAL, "null argument");
+  if (sched->code != code) return fail(QLDPC_EINVAL, "schedule was built for a different code");
+  if (algo != QLDPC_ALGO_MS && algo != QLDPC_ALGO_BP) return fail(QLDPC_EINVAL, "Unrecognized decoder type.");
+  KernelChoice k;                                     // (no device needed: the name depends on the code alone)
+  if (int rc = choose_prior_kernel(sched, algo, &k)) return rc;
+  snprintf(buf, (size_t)len, "%s", k.name);
+  return QLDPC_OK;
 }
 
 extern "C" int qldpc_decode_kernel_name(const qldpc_code* code, const qldpc_schedule* sched_c, int algo,
@@ -567,13 +658,18 @@ int capi::ws_reserve(qldpc_code* code, int64_t batch, bool want_post) {
   return QLDPC_OK;
 }
 
-extern "C" int qldpc_decode_host(const qldpc_code* code_c, const qldpc_schedule* sched, int algo,
-                                 const uint8_t* h_syn, int64_t batch, double p, int max_iter,
-                                 double beta, double eps, uint8_t* h_ehat, int32_t* h_iters,
-                                 double* h_post, int32_t* h_flags) {
+// qldpc_decode_host, and with `pr` (a host byte mask) qldpc_decode_host_prior
+static int decode_host(const qldpc_code* code_c, const qldpc_schedule* sched, int algo,
+                       const uint8_t* h_syn, int64_t batch, double p, int max_iter,
+                       double beta, double eps, uint8_t* h_ehat, int32_t* h_iters,
+                       double* h_post, int32_t* h_flags, const PriorCall* pr) {
   auto* code = const_cast<qldpc_code*>(code_c);
   if (!code) return fail(QLDPC_EINVAL, "code is null");
   if (batch < 0) return fail(QLDPC_EINVAL, "negative batch");
+  if (pr) {
+    if (!sched) return fail(QLDPC_EINVAL, "code/schedule is null");
+    if (int rc = validate_prior(code, sched, algo, batch, p, *pr)) return rc;
+  }
   if (batch == 0) return QLDPC_OK;
   if (!h_syn || !h_ehat || !h_iters) return fail(QLDPC_EINVAL, "null host buffer");
   if (code->device < 0) return fail(QLDPC_EHIP, "no HIP device was visible when the code was created");
@@ -585,9 +681,24 @@ extern "C" int qldpc_decode_host(const qldpc_code* code_c, const qldpc_schedule*
     memcpy(code->hp_syn, h_syn, batch * m);
     HIP_TRY(hipMemcpyAsync(code->ws_syn, code->hp_syn, batch * m, hipMemcpyHostToDevice, st));
   }
-  int rc = qldpc_decode_device(code, sched, algo, code->ws_syn, batch, p, max_iter, beta, eps,
-                               code->ws_ehat, code->ws_iters, h_post ? code->ws_post.p : nullptr,
-                               code->ws_flags, st);
+  PriorCall dpr{};
+  if (pr) {
+    // the mask goes through the workspace's mask buffers, grown with it
+    if (code->ws_mask_cap < code->ws_cap) {
+      const size_t cn = std::max<int64_t>(1, code->ws_cap * n);
+      HIP_TRY(code->ws_mask.alloc(cn));
+      HIP_TRY(code->hp_mask.alloc(cn));
+      code->ws_mask_cap = code->ws_cap;
+    }
+    if (batch * n) {
+      memcpy(code->hp_mask, pr->mask, batch * n);
+      HIP_TRY(hipMemcpyAsync(code->ws_mask, code->hp_mask, batch * n, hipMemcpyHostToDevice, st));
+    }
+    dpr = PriorCall{pr->p1, code->ws_mask.p, QLDPC_FMT_BYTES};
+  }
+  int rc = decode_device(code, sched, algo, code->ws_syn, QLDPC_FMT_BYTES, batch, p, max_iter, beta, eps,
+                         code->ws_ehat, QLDPC_FMT_BYTES, code->ws_iters, h_post ? code->ws_post.p : nullptr,
+                         code->ws_flags, st, pr ? &dpr : nullptr);
   if (rc) return rc;
   if (batch * n) HIP_TRY(hipMemcpyAsync(code->hp_ehat, code->ws_ehat, batch * n, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(code->hp_iters, code->ws_iters, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, st));
@@ -600,4 +711,21 @@ extern "C" int qldpc_decode_host(const qldpc_code* code_c, const qldpc_schedule*
   if (h_flags) memcpy(h_flags, code->hp_flags, sizeof(int32_t) * batch);
   if (h_post && batch * n) memcpy(h_post, code->hp_post, sizeof(double) * batch * n);
   return QLDPC_OK;
+}
+
+extern "C" int qldpc_decode_host(const qldpc_code* code, const qldpc_schedule* sched, int algo,
+                                 const uint8_t* h_syn, int64_t batch, double p, int max_iter,
+                                 double beta, double eps, uint8_t* h_ehat, int32_t* h_iters,
+                                 double* h_post, int32_t* h_flags) {
+  return decode_host(code, sched, algo, h_syn, batch, p, max_iter, beta, eps, h_ehat, h_iters, h_post, h_flags,
+                     nullptr);
+}
+
+extern "C" int qldpc_decode_host_prior(const qldpc_code* code, const qldpc_schedule* sched, int algo,
+                                       const uint8_t* h_syn, int64_t batch, double p0, double p1,
+                                       const uint8_t* h_mask, int max_iter, double beta, double eps,
+                                       uint8_t* h_ehat, int32_t* h_iters, double* h_post, int32_t* h_flags) {
+  const PriorCall pr{p1, h_mask, QLDPC_FMT_BYTES};
+  return decode_host(code, sched, algo, h_syn, batch, p0, max_iter, beta, eps, h_ehat, h_iters, h_post, h_flags,
+                     &pr);
 }

@@ -130,6 +130,7 @@ struct KernelChoice {
   int lanes = 0;            // ms_layered_kernel: lanes per check, 0 = chosen per layer
   int max_waves = 0;        // most waves per workgroup the kernel was compiled for
   int qc_table = -1;        // FAM_MS_FLOOD_QC: the generated table H expands from (qc_tables.h)
+  bool prior = false;       // decode_prior_kernel: the wave slice also holds the selector bits
 };
 
 struct LaunchPlan {
@@ -182,6 +183,7 @@ struct qldpc_code {
   int mw = 0;                                // 64-bit words per column bit-vector
   mutable std::vector<uint64_t> col_bits;    // [n][mw] column j of H (OSD)
   capi::DevBuf<uint16_t> d_vinv;
+  capi::DevBuf<uint16_t> d_vperm;            // relabeled -> original (decode_prior_kernel's mask gather)
   // HBM-resident kernel: 32-bit graph tables (relabeled variables)
   capi::DevBuf<int32_t> d_row_var, d_row_pos, d_col_ptr, d_vinv32;
   capi::DevBuf<int32_t> d_row_ptr, d_col_idx;  // CSR for the GPU OSD
@@ -202,6 +204,9 @@ struct qldpc_code {
   capi::PinBuf<uint8_t> hp_syn, hp_ehat;
   capi::PinBuf<int32_t> hp_iters, hp_flags;
   capi::PinBuf<double> hp_post;
+  int64_t ws_mask_cap = 0;               // half-shots the mask buffers hold (qldpc_decode_host_prior)
+  capi::DevBuf<uint8_t> ws_mask;
+  capi::PinBuf<uint8_t> hp_mask;
   hipStream_t ws_stream = nullptr;
   // hard-decision decoders (capi_hard.cpp), under hard_mu: 16-bit CSR / CSC
   // tables in original variable labels (row_ell | col_ell | row_ptr | row_var |
@@ -229,6 +234,7 @@ struct qldpc_schedule {
   capi::TableImage layered_bp;   // bp_team_lg_kernel: layer pointers in LDS, every table global
   capi::TableImage flood_ms;     // ms_flood_kernel, uniform degree: global tables, no LDS image
   capi::LaunchPlan plan[2];   // per algo, under mu
+  capi::LaunchPlan prior_plan[2];   // the same for decode_prior_kernel (qldpc_decode_device_prior)
   std::mutex mu;
   // HBM-resident kernel (hbm_kernels.hip): 32-bit layer tables and a grow-only
   // slot-major workspace; hbm_ev orders launches that share the workspace
@@ -270,6 +276,10 @@ struct Gf2Basis {
 // capi_decode.cpp. choose_kernel and plan_static call no HIP function: the
 // static kernel arguments can be checked on a machine without a device.
 KernelChoice choose_kernel(const qldpc_schedule* s, int algo);
+// decode_prior_kernel for (schedule, algo): QLDPC_EUNSUP where the generic LDS
+// kernel cannot run the code (16-bit tables, MS row degree > 32, BP column
+// degree > 128) or option force_hbm is set; calls no HIP function
+int choose_prior_kernel(const qldpc_schedule* s, int algo, KernelChoice* k);
 // The generated protograph table (qc_tables.h) whose expansion is exactly the
 // code's H, or -1: compared entry by entry, not by shape or hash
 int qc_table_of(const qldpc_code* c);

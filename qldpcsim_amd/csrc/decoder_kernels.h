@@ -55,10 +55,19 @@ struct DecodeArgs {
   double bp_csat;
   uint32_t bp_sat_hi;
   int qc_table;               // register-resident ms_flood_kernel: which generated table (qc_tables.h)
+  // decode_prior_kernel: variable j's prior is L where its mask bit is 0 and
+  // L1 where it is 1 (other kernels read none of these)
+  const void* pmask;          // uint64 [batch][wn] words or uint8 [batch][n], original column order
+  const uint16_t* vperm;      // [n] relabeled variable -> original column (global)
+  double L1;                  // log((1-p1)/max(p1,eps))
+  int pmask_bits;             // the mask's format, as syn_bits
+  int off_selw;               // inside a wave slice: selector bits, relabeled order (2 ceil(n/64) words)
 };
 
 // `name` (nullable) receives the kernel's name as rocprofv3 reports it
 const void* select_kernel(int algo, bool layered, int dc, const char** name);
+// its two-level-prior twin decode_prior_kernel (same template arguments)
+const void* select_prior_kernel(int algo, bool layered, int dc, const char** name);
 // flooding MS, uniform row degree: global tables (fblob), LDS = wave state only
 const void* select_ms_flood_kernel(int dc, int kc, const char** name);  // nullptr if no instantiation fits
 int ms_flood_max_waves(int kc);                      // waves per workgroup it was compiled for

@@ -646,19 +646,50 @@ __device__ __forceinline__ uint32_t cn_ms_uniform(const DecodeArgs& a, const uin
   }
 }
 
+// Two-level priors (decode_prior_kernel): bit j of `selw` (this wave's LDS
+// slice, relabeled variable order) picks variable j's prior, L (bit 0) or L1
+// (bit 1). Without PRI every variable's prior is the scalar a.L.
+template <bool PRI>
+__device__ __forceinline__ double prior_of(const DecodeArgs& a, const uint32_t* selw, int j) {
+  if constexpr (PRI) return ((selw[j >> 5] >> (j & 31)) & 1u) ? a.L1 : a.L;
+  return a.L;
+}
+// Mask bit of original column jo of half-shot hs (DecodeArgs::pmask)
+__device__ __forceinline__ uint32_t pmask_bit(const DecodeArgs& a, long long hs, int jo) {
+  if (a.pmask_bits) return (uint32_t)(((const uint64_t*)a.pmask)[hs * a.wn + (jo >> 6)] >> (jo & 63)) & 1u;
+  return ((const uint8_t*)a.pmask)[hs * (long long)a.n + jo] & 1u;
+}
+
 // Check-node update of one check `c` (lane-local), any degree.
 //   MS: decoders.py:155-169.  BP: decoders.py:249-262.
 // Returns the check's current parity XOR syndrome bit ("unsatisfied"),
 // computed from the hard decisions of the posteriors it reads (only
 // meaningful when !first).
 // ---------------------------------------------------------------------------
-template <int ALGO, int DC>
+template <int ALGO, int DC, bool PRI = false>
 __device__ __forceinline__ uint32_t cn_update(const DecodeArgs& a, const LdsView& g, int c,
                                               uint32_t synb, bool first, const double* post,
-                                              void* c2v_raw, int& fl) {
+                                              void* c2v_raw, int& fl, const uint32_t* selw = nullptr) {
   if constexpr (ALGO == ALGO_MS && DC > 0) {
     uint32_t t[1][8];
     load_row8(g.cn_tab + c * 8, t[0]);
+    if constexpr (PRI) {
+      if (first) {
+        // v_e = float32(L_j) differs per edge: the general check node on those
+        // values (c2v = 0) instead of the uniform closed form; parity unused
+        CnLoad<DC> L;
+        uint32_t ca[DC];
+        const uint32_t cb = lds_addr(c2v_raw);
+#pragma unroll
+        for (int k = 0; k < DC; ++k) {
+          L.pj[k] = (double)(float)prior_of<true>(a, selw, tab_var<DC>(t[0][k]));
+          L.cv[k] = 0.0f;
+          ca[k] = cb + (t[0][k] >> 16);
+        }
+        (void)cn_ms_compute<DC>(a, L, ca, synb, 1u, fl);
+        return 0;
+      }
+    }
     const uint32_t sb[1] = {synb};
     const bool live[1] = {true};
     if (first) return cn_ms_uniform<DC, true, 1>(a, t, sb, live, (const unsigned char*)post, (unsigned char*)c2v_raw, fl);
@@ -678,7 +709,7 @@ __device__ __forceinline__ uint32_t cn_update(const DecodeArgs& a, const LdsView
       const int j = tab_var<DC>(t), pos = tab_pos<DC>(t);
       double v;
       if (first) {
-        v = vfirst;                                   // float32(L) (:148-149)
+        v = PRI ? (double)(float)prior_of<PRI>(a, selw, j) : vfirst;   // float32(L) (:148-149)
       } else {
         const double pj = post[j];
         par ^= (uint32_t)(pj < 0.0);                  // hard decision (:174)
@@ -789,9 +820,10 @@ __device__ __forceinline__ float ms_colsum_sw(const float* c, int d, int dmax) {
 
 // dmax: wave-uniform upper bound of the degrees of the variables this pass
 // covers (per 64-variable chunk, from the host), so the loads are unrolled.
-template <int ALGO>
+template <int ALGO, bool PRI = false>
 __device__ __forceinline__ double vn_post(const DecodeArgs& a, const LdsView& g, int j,
-                                          const void* c2v_raw, int dmax) {
+                                          const void* c2v_raw, int dmax, const uint32_t* selw = nullptr) {
+  const double Lj = prior_of<PRI>(a, selw, j);
   const uint32_t info = g.vn_info[j];
   const int p0 = (int)(info & 0xffffu), d = (int)(info >> 16);
   if constexpr (ALGO == ALGO_MS) {
@@ -811,211 +843,30 @@ __device__ __forceinline__ double vn_post(const DecodeArgs& a, const LdsView& g,
         s = 0.0f;
         for (int t = 0; t < d; ++t) s += c[t];
     }
-    return a.L + (double)s;
+    return Lj + (double)s;
   } else {
     const double* c2v = (const double*)c2v_raw;
     const double t = np_sum_col(c2v + p0, d);
-    return d == 0 ? a.L : a.L + t;                   // L_post[j] = L0 (:277-278)
+    return d == 0 ? Lj : Lj + t;                     // L_post[j] = L0 (:277-278)
   }
 }
 
+// decode_kernel and its two-level-prior twin decode_prior_kernel (PRI:
+// DecodeArgs::pmask / L1; instantiated in
+// decode_prior_kernels.hip) share one body, decode_kernel_body.inc, included
+// into each kernel: as a __device__ function taking the arguments, the same
+// text compiled to different code for decode_kernel (register allocation of
+// the by-value kernel arguments), and its code must stay what it was.
 template <int ALGO, bool LAYERED, int DC>
 __global__ void __launch_bounds__(QLDPC_MAX_THREADS) decode_kernel(DecodeArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  constexpr bool PRI = false;
+#include "decode_kernel_body.inc"
+}
 
-  // Stage the read-only graph blob into LDS (16-byte vector copies).
-  {
-    const uint4* src = (const uint4*)a.blob;
-    uint4* dst = (uint4*)lds;
-    const int nvec = a.blob_bytes >> 4;
-    for (int i = threadIdx.x; i < nvec; i += blockDim.x) dst[i] = src[i];
-  }
-  __syncthreads();
-
-  LdsView g;
-  g.cn_tab = (const uint32_t*)(lds + a.off_cn_tab);
-  g.row_ptr = (const uint16_t*)(lds + a.off_row_ptr);
-  g.vn_info = (const uint32_t*)(lds + a.off_vn_ptr);
-  g.chunk_dmax = (const uint8_t*)(lds + a.off_chunk_dmax);
-  g.vn_chk = (const uint16_t*)(lds + a.off_vn_chk);
-  g.lay_ptr = (const uint16_t*)(lds + a.off_lay_ptr);
-  g.lay_rows = (const uint16_t*)(lds + a.off_lay_rows);
-  g.adj_ptr = (const uint16_t*)(lds + a.off_adj_ptr);
-  g.adj_vars = (const uint16_t*)(lds + a.off_adj_vars);
-  g.lt = nullptr;
-  if constexpr (ALGO == ALGO_BP) {
-    g.lt = stage_libm(lds, a.off_libm);
-    __syncthreads();
-  }
-
-  const int lane = threadIdx.x & 63;
-  const int wid = threadIdx.x >> 6;
-  const int waves = blockDim.x >> 6;
-  unsigned char* ws = lds + a.blob_bytes + wid * a.wave_bytes;
-  double* post = (double*)ws;
-  void* c2v = (void*)(ws + a.off_c2v);
-  uint32_t* synw = (uint32_t*)(ws + a.off_synw);
-  uint32_t* parw = (uint32_t*)(ws + a.off_parw);
-
-  const int m = a.m, n = a.n;
-  const int nwords = (m + 31) >> 5;
-
-  for (HalfShotQueue Q(a, waves, wid); Q.hs < a.batch; Q.advance()) {
-    const long long hs = Q.hs;
-    Q.prefetch(threadIdx.x & 63);
-    int fl = 0;
-    int iters = a.max_iter;
-    bool conv = false;
-
-    if constexpr (!LAYERED) {
-      // ---------------- flooding: one layer holding every check ------------
-      uint32_t synreg = 0;  // bit i = syndrome of check lane + 64 i
-      for (int i = 0, c = lane; c < m; ++i, c += 64) synreg |= syn_bit(a, hs, c) << i;
-      if constexpr (ALGO == ALGO_BP) {
-        // BP's first check-node pass reads v2c = L0 (decoders.py:235):
-        // post = L0, c2v = 0. (MS's first pass reads float32(L) directly.)
-        for (int j = lane; j < n; j += 64) post[j] = a.L;
-        double* cz = (double*)c2v;
-        for (int p = lane; p < a.E; p += 64) cz[p] = 0.0;
-        wave_sync();
-      }
-      for (int it = 0;; ++it) {
-        // CN over all checks; its parity pass is the stop test of iteration it-1
-        // (decoders.py:175-176 — checks read the posteriors the last VN wrote).
-        uint32_t unsat = 0;
-        if constexpr (QLDPC_ABLATE == 2) {
-          unsat = 1;
-        } else if constexpr (ALGO == ALGO_MS && DC > 0) {
-          for (int i = 0, c = lane; c < m; ++i, c += 64) {
-            uint32_t t[1][8];
-            load_row8(g.cn_tab + c * 8, t[0]);
-            const uint32_t sb[1] = {(synreg >> i) & 1u};
-            const bool live[1] = {true};
-            if (it == 0)
-              (void)cn_ms_uniform<DC, true, 1>(a, t, sb, live, (const unsigned char*)post, (unsigned char*)c2v, fl);
-            else
-              unsat |= cn_ms_uniform<DC, false, 1>(a, t, sb, live, (const unsigned char*)post, (unsigned char*)c2v, fl);
-          }
-        } else if (it == 0) {
-          for (int i = 0, c = lane; c < m; ++i, c += 64)
-            (void)cn_update<ALGO, DC>(a, g, c, (synreg >> i) & 1u, true, post, c2v, fl);
-        } else {
-          for (int i = 0, c = lane; c < m; ++i, c += 64)
-            unsat |= cn_update<ALGO, DC>(a, g, c, (synreg >> i) & 1u, false, post, c2v, fl);
-        }
-        if (it > 0 && ballot(unsat != 0) == 0) {
-          iters = it;
-          conv = true;
-          break;
-        }
-        wave_sync();
-        if constexpr (QLDPC_ABLATE != 1) {
-          for (int j0 = 0; j0 < n; j0 += 64) {
-            const int dmax = __builtin_amdgcn_readfirstlane((int)g.chunk_dmax[j0 >> 6]);
-            const int j = j0 + lane;
-            if (j < n) post[j] = vn_post<ALGO>(a, g, j, c2v, dmax);
-          }
-        }
-        wave_sync();
-        if (it + 1 == a.max_iter) {
-          // final stop test after the last VN (its result only sets the flag:
-          // both branches of the reference return max_iter, :176 / :182)
-          uint32_t un = 0;
-          for (int i = 0, c = lane; c < m; ++i, c += 64) {
-            const int e0 = DC ? c * 8 : (int)g.row_ptr[c];
-            const int deg = DC ? DC : (int)g.row_ptr[c + 1] - e0;
-            uint32_t par = 0;
-            for (int k = 0; k < deg; ++k) par ^= (uint32_t)(post[tab_var<DC>(g.cn_tab[e0 + k])] < 0.0);
-            un |= par ^ ((synreg >> i) & 1u);
-          }
-          conv = ballot(un != 0) == 0;
-          break;
-        }
-      }
-    } else {
-      // ---------------- layered / serial: explicit row lists ----------------
-      // State starts at c2v = 0, post = L (msg_v2c = L, :148-149 / :235).
-      const double L = a.L;
-      for (int j = lane; j < n; j += 64) post[j] = L;
-      if constexpr (ALGO == ALGO_MS) {
-        float* c = (float*)c2v;
-        for (int p = lane; p < a.E; p += 64) c[p] = 0.0f;
-      } else {
-        double* c = (double*)c2v;
-        for (int p = lane; p < a.E; p += 64) c[p] = 0.0;
-      }
-      // syndrome bits and the parity of the initial hard decisions (all = L<0)
-      for (int c0 = 0; c0 < m; c0 += 64) {
-        const int c = c0 + lane;
-        const int in = c < m;
-        store_bits64(synw, c0, in ? (int)syn_bit(a, hs, c) : 0, lane);
-        int deg = 0;
-        if (in) deg = DC ? DC : (int)g.row_ptr[c + 1] - (int)g.row_ptr[c];
-        store_bits64(parw, c0, in && (L < 0.0) && (deg & 1), lane);
-      }
-      wave_sync();
-      bool first = true;
-      for (int it = 0; it < a.max_iter && !conv; ++it) {
-        for (int l = 0; l < a.n_layers; ++l) {
-          // CN over the layer's rows (Jacobi: all read the same posteriors)
-          const int q0 = g.lay_ptr[l], q1 = g.lay_ptr[l + 1];
-          for (int q = q0 + lane; q < q1; q += 64) {
-            const int c = g.lay_rows[q];
-            const uint32_t sb = (synw[c >> 5] >> (c & 31)) & 1u;
-            (void)cn_update<ALGO, DC>(a, g, c, sb, first, post, c2v, fl);
-          }
-          first = false;
-          wave_sync();
-          // VN over the variables adjacent to the layer (others are unchanged,
-          // so recomputing every column as decoders.py:172 / :265 does is
-          // bit-identical); hard-decision flips toggle check parities.
-          const int v0 = g.adj_ptr[l], v1 = g.adj_ptr[l + 1];
-          for (int q = v0 + lane; q < v1; q += 64) {
-            const int j = g.adj_vars[q];
-            const double old = post[j];
-            const double nw = vn_post<ALGO>(a, g, j, c2v, -1);
-            post[j] = nw;
-            if ((old < 0.0) != (nw < 0.0)) {
-              const uint32_t info = g.vn_info[j];
-              for (int p = (int)(info & 0xffffu), pe = p + (int)(info >> 16); p < pe; ++p) {
-                const int c = g.vn_chk[p];
-                atomicXor(&parw[c >> 5], 1u << (c & 31));
-              }
-            }
-          }
-          wave_sync();
-          // stop test after every layer (:175-176 / :283-285)
-          uint32_t un = 0;
-          for (int w = lane; w < nwords; w += 64) un |= parw[w] ^ synw[w];
-          if (ballot(un != 0) == 0) {
-            iters = it + 1;
-            conv = true;
-            break;
-          }
-        }
-      }
-    }
-
-    // ---------------- outputs (original column order) ----------------------
-    double* po = a.post ? a.post + hs * (long long)n : nullptr;
-    for (int jo = lane; jo < n; jo += 64) {
-      const double pv = post[a.vinv[jo]];
-      put_ehat(a, hs, jo, pv < 0.0);                  // e_hat = post < 0 (:174 / :280)
-      if (po) po[jo] = pv;
-    }
-    // OR the lane-local flags across the wave
-    uint32_t fall = 0;
-    {
-      const uint64_t b1 = ballot((fl & FLAG_MIN_ZERO) != 0);
-      const uint64_t b2 = ballot((fl & FLAG_NONFINITE) != 0);
-      fall = (b1 ? FLAG_MIN_ZERO : 0) | (b2 ? FLAG_NONFINITE : 0) | (conv ? FLAG_CONVERGED : 0);
-    }
-    if (lane == 0) {
-      a.iters[hs] = iters;
-      if (a.flags) a.flags[hs] = (int32_t)fall;
-    }
-    wave_sync();  // the next half-shot reuses this wave's LDS slice
-  }
+template <int ALGO, bool LAYERED, int DC>
+__global__ void __launch_bounds__(QLDPC_MAX_THREADS) decode_prior_kernel(DecodeArgs a) {
+  constexpr bool PRI = true;
+#include "decode_kernel_body.inc"
 }
 
 // ---------------------------------------------------------------------------
@@ -2388,8 +2239,35 @@ __global__ void __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))
 // The BP team kernels and the flooding min-sum kernel are instantiated in
 // translation units of their own (bp_team_kernels.hip, built without SLP
 // vectorization; ms_flood_kernels.hip, built with the max-ILP machine
-// scheduler); every other kernel here.
-#if !defined(QLDPC_TU_BP_TEAM) && !defined(QLDPC_TU_FLOOD)
+// scheduler), and so are the two-level-prior kernels
+// (decode_prior_kernels.hip); every other kernel here.
+#if defined(QLDPC_TU_PRIOR)
+
+const void* select_prior_kernel(int algo, bool layered, int dc, const char** name) {
+  static const char* names[2][2][3] = {
+      {{"decode_prior_kernel<0, false, 0>", "decode_prior_kernel<0, false, 7>", "decode_prior_kernel<0, false, 8>"},
+       {"decode_prior_kernel<0, true, 0>", "decode_prior_kernel<0, true, 7>", "decode_prior_kernel<0, true, 8>"}},
+      {{"decode_prior_kernel<1, false, 0>", "decode_prior_kernel<1, false, 7>", "decode_prior_kernel<1, false, 8>"},
+       {"decode_prior_kernel<1, true, 0>", "decode_prior_kernel<1, true, 7>", "decode_prior_kernel<1, true, 8>"}}};
+  if (name) *name = names[algo == ALGO_MS ? 0 : 1][layered ? 1 : 0][dc == 7 ? 1 : (dc == 8 ? 2 : 0)];
+#define QLDPC_PICK(ALG)                                                                                       \
+  switch (dc) {                                                                                               \
+    case 7: return layered ? (const void*)&decode_prior_kernel<ALG, true, 7>                                  \
+                           : (const void*)&decode_prior_kernel<ALG, false, 7>;                                \
+    case 8: return layered ? (const void*)&decode_prior_kernel<ALG, true, 8>                                  \
+                           : (const void*)&decode_prior_kernel<ALG, false, 8>;                                \
+    default: return layered ? (const void*)&decode_prior_kernel<ALG, true, 0>                                 \
+                            : (const void*)&decode_prior_kernel<ALG, false, 0>;                               \
+  }
+  if (algo == ALGO_MS) {
+    QLDPC_PICK(ALGO_MS)
+  } else {
+    QLDPC_PICK(ALGO_BP)
+  }
+#undef QLDPC_PICK
+}
+
+#elif !defined(QLDPC_TU_BP_TEAM) && !defined(QLDPC_TU_FLOOD)
 template <int ALGO, bool LAYERED, int DC>
 static const void* kernel_ptr() {
   return (const void*)&decode_kernel<ALGO, LAYERED, DC>;

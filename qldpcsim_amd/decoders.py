@@ -93,7 +93,7 @@ def unpack_bits(words, k):
 
 def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, eps=1e-9,
                  want_post=False, osd_order=-1, layer_ptr=None, layer_rows=None, stream=None,
-                 out=None, ehat_bits=False):
+                 out=None, ehat_bits=False, prior_mask=None, p_masked=None):
     """Decode a batch of syndromes of one matrix on the GPU.
 
     syndromes: uint8 [B, m] NumPy array (host; staged, synchronous) or a
@@ -108,10 +108,23 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
     `algo`: "MS", "BP", or the hard-decision "NG" / "BF", which take only H,
     the syndromes and (BF) `max_iter`: p, layers, beta and eps are ignored,
     want_post / osd_order >= 0 raise ValueError, and the result's post is None.
+    `prior_mask`, `p_masked` (MS / BP; both or neither): a two-level prior per
+    shot. Variable j of shot b decodes with the prior of `p_masked` where
+    prior_mask[b, j] is set and with the prior of `p` elsewhere (correlated
+    X/Z decoding: the other half's estimate is the mask). Device path: a
+    tensor on the syndromes' device, uint8 [B, n] or int64 words
+    [B, ceil(n/64)] (an earlier decode's ehat as it is; not this call's out);
+    host path: a uint8 [B, n] array. Runs decode_prior_kernel, the generic LDS
+    kernel's twin: NotImplementedError for a code it cannot hold or with
+    option force_hbm. With p_masked == p the result is the scalar decode's.
     """
     if algo not in _lib.ALGO:
         raise ValueError("Unrecognized decoder type.")
+    if (prior_mask is None) != (p_masked is None):
+        raise ValueError("prior_mask and p_masked go together: give both or neither")
     if algo in _lib.HARD_ALGOS:
+        if prior_mask is not None:
+            raise ValueError(f"{algo} is a hard-decision decoder: it takes no prior (prior_mask)")
         return _decode_batch_hard(H, syndromes, max_iter, algo, want_post, osd_order, stream, out, ehat_bits)
     if algo == "BP" and "libm" not in _PINNED:
         numpy_libm_pinned()                   # once: warns if BP cannot be bit-exact on this NumPy
@@ -135,6 +148,17 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
         else:
             raise ValueError(f"syndromes must be uint8 [B, {m}] or int64 words [B, {wm}]")
         B = syn.shape[0]
+        mask_fmt = None
+        if prior_mask is not None:
+            if not (_is_torch(prior_mask) and prior_mask.device == dev and prior_mask.dim() == 2):
+                raise ValueError("prior_mask must be a 2-D tensor on the syndromes' device")
+            prior_mask = prior_mask.contiguous()
+            if prior_mask.dtype == torch.uint8 and tuple(prior_mask.shape) == (B, n):
+                mask_fmt = _lib.FMT_BYTES
+            elif prior_mask.dtype == torch.int64 and tuple(prior_mask.shape) == (B, wn):
+                mask_fmt = _lib.FMT_BITS
+            else:
+                raise ValueError(f"prior_mask must be uint8 [{B}, {n}] or int64 words [{B}, {wn}]")
         e_shape, e_dtype = ((B, wn), torch.int64) if ehat_bits else ((B, n), torch.uint8)
         if out is not None:
             ehat, iters, flags, post = out.ehat, out.iters, out.flags, out.post if want_post else None
@@ -153,10 +177,17 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
             flags = torch.empty(B, dtype=torch.int32, device=dev)
             post = torch.empty((B, n), dtype=torch.float64, device=dev) if want_post else None
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(_lib.lib.qldpc_decode_device_ex(
-            code.handle, sched.handle, _lib.ALGO[algo], syn.data_ptr(), syn_fmt, B, float(p), int(max_iter),
-            float(beta), float(eps), ehat.data_ptr(), _lib.FMT_BITS if ehat_bits else _lib.FMT_BYTES,
-            iters.data_ptr(), post.data_ptr() if post is not None else None, flags.data_ptr(), st))
+        e_fmt = _lib.FMT_BITS if ehat_bits else _lib.FMT_BYTES
+        post_p = post.data_ptr() if post is not None else None
+        if prior_mask is not None:
+            _lib.check(_lib.lib.qldpc_decode_device_prior(
+                code.handle, sched.handle, _lib.ALGO[algo], syn.data_ptr(), syn_fmt, B, float(p), float(p_masked),
+                prior_mask.data_ptr(), mask_fmt, int(max_iter), float(beta), float(eps), ehat.data_ptr(), e_fmt,
+                iters.data_ptr(), post_p, flags.data_ptr(), st))
+        else:
+            _lib.check(_lib.lib.qldpc_decode_device_ex(
+                code.handle, sched.handle, _lib.ALGO[algo], syn.data_ptr(), syn_fmt, B, float(p), int(max_iter),
+                float(beta), float(eps), ehat.data_ptr(), e_fmt, iters.data_ptr(), post_p, flags.data_ptr(), st))
         return DecodeResult(ehat, iters, post, flags)
 
     syn = np.ascontiguousarray(syndromes)
@@ -166,6 +197,15 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
         raise ValueError("syndrome entries must be 0 or 1")
     syn = syn.astype(np.uint8, copy=False)
     B = syn.shape[0]
+    if prior_mask is not None:
+        if _is_torch(prior_mask):
+            raise ValueError("prior_mask must be a NumPy array on the host path (the syndromes are)")
+        prior_mask = np.ascontiguousarray(prior_mask)
+        if prior_mask.shape != (B, n):
+            raise ValueError(f"prior_mask must be [{B}, {n}]")
+        if prior_mask.size and (prior_mask.min() < 0 or prior_mask.max() > 1):
+            raise ValueError("prior_mask entries must be 0 or 1")
+        prior_mask = prior_mask.astype(np.uint8, copy=False)
     code = _lib.code_for(H)
     sched = code.schedule(layer_ptr, layer_rows)
     ehat = np.zeros((B, n), np.uint8)
@@ -173,9 +213,15 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
     flags = np.zeros(B, np.int32)
     need_post = want_post or osd_order >= 0
     post = np.zeros((B, n), np.float64) if need_post else None
-    _lib.check(_lib.lib.qldpc_decode_host(
-        code.handle, sched.handle, _lib.ALGO[algo], _lib.ptr(syn), B, float(p), int(max_iter),
-        float(beta), float(eps), _lib.ptr(ehat), _lib.ptr(iters), _lib.ptr(post), _lib.ptr(flags)))
+    if prior_mask is not None:
+        _lib.check(_lib.lib.qldpc_decode_host_prior(
+            code.handle, sched.handle, _lib.ALGO[algo], _lib.ptr(syn), B, float(p), float(p_masked),
+            _lib.ptr(prior_mask), int(max_iter), float(beta), float(eps), _lib.ptr(ehat), _lib.ptr(iters),
+            _lib.ptr(post), _lib.ptr(flags)))
+    else:
+        _lib.check(_lib.lib.qldpc_decode_host(
+            code.handle, sched.handle, _lib.ALGO[algo], _lib.ptr(syn), B, float(p), int(max_iter),
+            float(beta), float(eps), _lib.ptr(ehat), _lib.ptr(iters), _lib.ptr(post), _lib.ptr(flags)))
     res = DecodeResult(ehat, iters, post if want_post else None, flags)
     if osd_order >= 0:
         apply_osd(H, syn, ehat, post, flags, osd_order)

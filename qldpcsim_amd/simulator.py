@@ -356,7 +356,7 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
                decIterations: int = 99, decSchedule: str = "F", OSDorder: int = -1,
                rngSeed: Optional[int] = None, *, batch_size: Optional[int] = None,
                verbose: bool = True, samples=None, sampler: Optional[str] = None,
-               logical: bool = False) -> dict:
+               logical: bool = False, correlated: Optional[str] = None, correlated_q1: float = 0.49) -> dict:
     """One depolarizing probability: sample, decode both halves, count.
 
     Returns the reference's dict (simulator.py:308-315). `samples`, if given,
@@ -372,6 +372,20 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
     interval `logical_error_rate_ci95` = [lo, hi]. Raises ValueError if
     (Hx, Hz) is not a CSS pair. With `samples`, sy = H·err is the caller's
     contract.
+
+    `correlated` (extension; MS and BP): "XZ" or "ZX" decodes the halves in
+    that order and gives the second one a two-level prior from the first one's
+    final estimate (after OSD, if any): under depolarizing noise a qubit that
+    carries an X component carries a Z component with probability 1/2 (a Y
+    error), one that does not with (p/3)/(1 - 2p/3), and the same with X and Z
+    exchanged. The first half is decoded exactly as without the option (prior
+    p/3); the second with decode_batch(prior_mask=first estimate,
+    p=(p/3)/(1 - 2p/3), p_masked=correlated_q1). `correlated_q1` (0 < q1 <=
+    0.5) stands for the 1/2, whose LLR is exactly 0: BP then divides 0 by 0
+    (allowed, flagged NONFINITE) and min-sum sets FLAG_MIN_ZERO on almost
+    every shot, so the default is 0.49 (LLR 0.04), which decodes as well.
+    The second half runs the generic LDS kernel's twin, and with OSD the two
+    halves' OSD steps are not pipelined.
     """
     if rngSeed is not None:
         np.random.seed(rngSeed)                    # reference side effect (:187-188)
@@ -384,6 +398,15 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
     layersX, layersZ = select_layers(Hx, Hz, decSchedule)   # raises ValueError (:236)
     if decType not in _lib.ALGO:
         raise ValueError("Unrecognized decoder type.")
+    if correlated not in (None, "XZ", "ZX"):
+        raise ValueError("correlated must be 'XZ', 'ZX' or None")
+    if correlated is not None:
+        if decType in _lib.HARD_ALGOS:
+            raise ValueError(f"correlated decoding needs a prior: {decType} is a hard-decision decoder")
+        if not (0.0 < float(correlated_q1) <= 0.5):
+            raise ValueError("correlated_q1 must lie in (0, 0.5]")
+        q1 = float(correlated_q1)
+        p0c = (p / 3) / (1 - 2 * p / 3)            # P(second component | no first component)
     # the reference never passes OSDorder to BP_decoder (:281-282); NG and BF
     # get (H, syndrome) alone (:270-276): no prior, no decIterations (BF runs
     # its default 50), no OSD
@@ -422,7 +445,41 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
         import torch
         dev = torch.device("cuda", torch.cuda.current_device())
         ch = DeviceChannel(Hx, Hz, dev, np.random.SeedSequence(seed).generate_state(1, np.uint64)[0])
-    if use_dev:
+    if use_dev and correlated is not None:
+        # Correlated mode: the second half's decode waits for the first half's
+        # final estimate, so each batch runs decode, (OSD,) decode, (OSD,)
+        # count in stream order. Without OSD the mask is the first decode's
+        # bit-packed estimate tensor itself: no kernel, copy or sync between.
+        acc = torch.zeros(len(keys), dtype=torch.int64, device=dev)
+        count_dev = ch.count_logical_device if logical else ch.count_device
+        osd_flags = []
+        while done < my_shots:
+            B = min(batch_size, my_shots - done)
+            packed = osd < 0
+            sy_z, sy_x, errX, errZ = ch.sample(p, B, bits=packed)
+            halves = [(Hz, sy_z, lpX, lrX), (Hx, sy_x, lpZ, lrZ)]
+            if correlated == "ZX":
+                halves.reverse()
+            res, mask = [], None
+            for H_, sy_, lp_, lr_ in halves:
+                kw = {} if mask is None else {"prior_mask": mask, "p_masked": q1}
+                r_ = decoders.decode_batch(H_, sy_, p / 3 if mask is None else p0c, decIterations, algo=decType,
+                                           want_post=osd >= 0, layer_ptr=lp_, layer_rows=lr_, ehat_bits=packed, **kw)
+                if osd >= 0:                           # (decoders.py:179-180) before the estimate is used
+                    items = [(H_, sy_, r_)]
+                    decoders.osd_device_finish(items, decoders.osd_device_stage(items, order=osd), osd)
+                    decoders.osd_status_check(items, defer=osd_flags)
+                res.append(r_)
+                mask = r_.ehat
+            rX, rZ = res if correlated == "XZ" else res[::-1]
+            count_dev(sy_z, sy_x, errX, errZ, rX.ehat, rZ.ehat, rX.iters, rZ.iters, acc)
+            done += B
+            if verbose and rank == 0:
+                print(f"\r(p={p:5.2e}) Decoding block n. {done:3}/{my_shots:4}... "
+                      f"({done / (time.time() - t0):.3g} shots/s)", end="", flush=True)
+        decoders.osd_status_raise(osd_flags)
+        tot = dict(zip(keys, (int(x) for x in acc.cpu().tolist())))
+    elif use_dev:
         # Two-stage pipeline over batches: the host computes batch b-1's OSD
         # reliability orders (NumPy, the shots the device order leaves) while
         # the GPU runs batch b's decode and device OSD;
@@ -500,10 +557,21 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
             sy_z, sy_x, errX, errZ = (np.asarray(a)[sl].astype(np.uint8) for a in samples)
         else:
             sy_z, sy_x, errX, errZ = sample_channel(Hx, Hz, p, B, rng)
-        rX = decoders.decode_batch(Hz, sy_z, p / 3, decIterations, algo=decType, osd_order=osd,
-                                   layer_ptr=lpX, layer_rows=lrX)
-        rZ = decoders.decode_batch(Hx, sy_x, p / 3, decIterations, algo=decType, osd_order=osd,
-                                   layer_ptr=lpZ, layer_rows=lrZ)
+        if correlated is None:
+            rX = decoders.decode_batch(Hz, sy_z, p / 3, decIterations, algo=decType, osd_order=osd,
+                                       layer_ptr=lpX, layer_rows=lrX)
+            rZ = decoders.decode_batch(Hx, sy_x, p / 3, decIterations, algo=decType, osd_order=osd,
+                                       layer_ptr=lpZ, layer_rows=lrZ)
+        else:
+            halves = [(Hz, sy_z, lpX, lrX), (Hx, sy_x, lpZ, lrZ)]
+            if correlated == "ZX":
+                halves.reverse()
+            (H1, s1, lp1, lr1), (H2, s2, lp2, lr2) = halves
+            r1 = decoders.decode_batch(H1, s1, p / 3, decIterations, algo=decType, osd_order=osd,
+                                       layer_ptr=lp1, layer_rows=lr1)
+            r2 = decoders.decode_batch(H2, s2, p0c, decIterations, algo=decType, osd_order=osd,
+                                       layer_ptr=lp2, layer_rows=lr2, prior_mask=r1.ehat, p_masked=q1)
+            rX, rZ = (r1, r2) if correlated == "XZ" else (r2, r1)
         if logical:
             c = count_logical_outcomes(Hx, Hz, sy_z, sy_x, errX, errZ, rX.ehat, rZ.ehat, rX.iters, rZ.iters,
                                        logicals=pair_logicals)
@@ -594,7 +662,8 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
              decIterations: int = 99, decSchedule: str = "F", OSDorder: int = -1,
              rngSeed: Optional[int] = None, *, batch_size: Optional[int] = None, verbose: bool = True,
              return_results: bool = False, sampler: Optional[str] = None,
-             resultsFile: Optional[str] = None, on_point=None, logical: bool = False):
+             resultsFile: Optional[str] = None, on_point=None, logical: bool = False,
+             correlated: Optional[str] = None, correlated_q1: float = 0.49):
     """p-sweep + results table (simulator.py:319-347). Returns None like the
     reference unless return_results=True.
 
@@ -602,6 +671,10 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
     table with the logical block error rate, its 95 % interval and the logical
     errors per half follows the reference's. The results file's meta then
     holds "logical": true (a file written without the option is refused).
+
+    correlated, correlated_q1 (extension): simulate_p's correlated X/Z
+    decoding for every point; both enter the results file's meta, so a sweep
+    is never resumed across modes.
 
     resultsFile (extension): a JSON file the sweep writes after every
     p-point; a rerun with the same arguments skips the points already there
@@ -621,6 +694,11 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
     if logical:
         meta["logical"] = True
         extra["logical"] = True
+    if correlated is not None:
+        meta["correlated"] = correlated
+        meta["correlated_q1"] = correlated_q1
+        extra["correlated"] = correlated
+        extra["correlated_q1"] = correlated_q1
     done = _load_results(resultsFile, meta)
     results = []
     for pT in p:
@@ -701,6 +779,12 @@ def main(argv=None):
     parser.add_argument("--logical", action="store_true",
                         help="Also count logical errors (residuals tested against the CSS pair's logical "
                              "operators) and print the logical block error rate with its 95 %% interval.")
+    parser.add_argument("--correlated", choices=["XZ", "ZX"], default=None,
+                        help="Correlated X/Z decoding (MS, BP): decode the halves in this order and give the "
+                             "second one a two-level prior from the first one's estimate.")
+    parser.add_argument("--correlated-q1", type=float, default=0.49, dest="correlated_q1",
+                        help="Prior of the second component on a qubit flagged by the first half (exactly 1/2 "
+                             "in theory; its LLR 0 is degenerate for the decoders: default 0.49).")
     args = parser.parse_args(argv)
     own_group = _init_dist_from_env()              # torchrun: shots shard over the ranks
     _, rank, _ = _dist()
@@ -712,7 +796,8 @@ def main(argv=None):
         simulate(HxFile=args.Hx, HzFile=args.Hz, p=args.p, shots=args.shots, decType=args.decType,
                  decIterations=args.decIterations, decSchedule=args.decSchedule,
                  OSDorder=args.OSDorder, rngSeed=args.rngSeed, batch_size=args.batch,
-                 sampler=args.sampler, resultsFile=args.results, **({"logical": True} if args.logical else {}))
+                 sampler=args.sampler, resultsFile=args.results, **({"logical": True} if args.logical else {}),
+                 **({"correlated": args.correlated, "correlated_q1": args.correlated_q1} if args.correlated else {}))
     finally:
         if own_group:
             import torch.distributed as dist
