@@ -6,13 +6,16 @@
 // maps onto the DPP rows of a wave: lane = 16 q + k, row q decodes one
 // half-shot, lane k owns position k of every check block and of every
 // variable block. Per lane: MB x DC float32 messages (check block b, edge e)
-// and NB float32 column sums S; posterior = L + (double)S as the LDS body
-// forms it. A message exchange between check block b and variable block c is
-// a rotation inside the DPP row by the block's shift s:
+// and, per variable block, the float64 posterior P = L + (double)S as the LDS
+// body forms it (S the float32 column sum), formed once in the VN pass; the
+// blocks past the first qc_np<T>() in qc_post64's order keep S and form the
+// posterior per edge. A message exchange between check block b and variable
+// block c is a rotation inside the DPP row by the block's shift s:
 //   check position r  <->  variable position (r + s) % 16.
 // row_ror:n gives lane i the value of lane (i - n) % 16 of its row, so a check
-// reads its variable's S with n = (16 - s) % 16 and a variable reads its
-// check's message with n = s. No LDS, no addresses, no wave barriers.
+// reads its variable's P (both words) or S with n = (16 - s) % 16 and a
+// variable reads its check's message with n = s. No LDS, no addresses, no
+// wave barriers.
 //
 // The four rows of a wave advance independently: each has its own iteration
 // count and stop test (ballot bits 16 q .. 16 q + 15); a row that finishes
@@ -40,6 +43,56 @@ __device__ __forceinline__ float row_ror_f32(float x) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x120 + (N & 15),
                                                                  0xf, 0xf, true));
   }
+}
+
+// the same rotation of a float64: low and high word by the same row_ror
+template <int N>
+__device__ __forceinline__ double row_ror_f64(double x) {
+  if constexpr ((N & 15) == 0) {
+    return x;
+  } else {
+    const uint64_t u = __builtin_bit_cast(uint64_t, x);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, 0x120 + (N & 15), 0xf, 0xf, true);
+    const uint32_t hi =
+        (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), 0x120 + (N & 15), 0xf, 0xf, true);
+    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+  }
+}
+
+// Number of variable blocks whose posterior is held in float64 (the rest keep
+// the float32 column sum and form the posterior per edge); -DQLDPC_QC_NP=n
+// overrides it for A/B. DESIGN.md §3.1.1 for the measured choice.
+#ifndef QLDPC_QC_NP
+#define QLDPC_QC_NP 34
+#endif
+template <typename T>
+constexpr int qc_np() { return QLDPC_QC_NP < T::NB ? QLDPC_QC_NP : T::NB; }
+
+// Modelled cycles per trip saved by holding block c's posterior in float64
+// (float64 instruction 4 cycles, 32-bit one 2): deg conversions and additions
+// become one of each, and every non-zero shift rotates two words instead of one.
+template <typename T>
+constexpr int qc_post64_saving(int c) {
+  int zero = 0;
+  for (int t = 0; t < T::vdeg[c]; ++t) zero += T::vshift[c][t] == 0;
+  return 8 * T::vdeg[c] - 2 * (T::vdeg[c] - zero) - 8;
+}
+// block c is among the qc_np<T>() blocks of largest saving (ties in table order)
+template <typename T>
+constexpr bool qc_post64(int c) {
+  int rank = 0;
+  for (int d = 0; d < T::NB; ++d) {
+    const int sd = qc_post64_saving<T>(d), sc = qc_post64_saving<T>(c);
+    rank += sd > sc || (sd == sc && d < c);
+  }
+  return rank < qc_np<T>();
+}
+
+// posterior of this lane's variable of block C
+template <typename T, int C>
+__device__ __forceinline__ double qc_post(double L, const float (&S)[T::NB], const double (&P)[T::NB]) {
+  if constexpr (qc_post64<T>(C)) return P[C];
+  else return L + (double)S[C];
 }
 
 // 16-bit slice of a ballot that belongs to this lane's row (rowsh = lane & 48)
@@ -84,24 +137,33 @@ struct RowQueue {
 };
 
 // Min-sum update of check block B (decoders.py:155-169 for the lane's check):
-// cn_ms_compute with the posteriors rotated in from S and the messages in
-// registers. Returns the check's "unsatisfied" bit for the posteriors it read.
+// cn_ms_compute with the posteriors rotated in from P (or formed from the
+// rotated S) and the messages in registers. Returns the check's "unsatisfied"
+// bit for the posteriors it read.
 template <typename T, int B>
-__device__ __forceinline__ uint32_t qc_check(const DecodeArgs& a, double L, float (&S)[T::NB],
+__device__ __forceinline__ uint32_t qc_check(const DecodeArgs& a, double L, float (&S)[T::NB], double (&P)[T::NB],
                                              float (&c2v)[T::MB][T::DC], uint32_t synb, int& fl) {
   constexpr int DC = T::DC;
   // one check block's working set at a time: the inputs are pinned behind the
   // previous block's outputs (volatile asm statements keep their order), so no
   // widened copy of a later block's operands is formed ahead of its turn
   static_for<DC>([&](auto E) __attribute__((always_inline)) {
-    float &sx = S[T::cvar[B][E]], &cx = c2v[B][E];      // (named: asm operands alone do not capture)
-    asm volatile("" : "+v"(sx), "+v"(cx));
+    float& cx = c2v[B][E];                              // (named: asm operands alone do not capture)
+    if constexpr (qc_post64<T>(T::cvar[B][E])) {
+      double& px = P[T::cvar[B][E]];
+      asm volatile("" : "+v"(px), "+v"(cx));
+    } else {
+      float& sx = S[T::cvar[B][E]];
+      asm volatile("" : "+v"(sx), "+v"(cx));
+    }
   });
   double v[DC];
   uint32_t hv[DC], hp[DC];
   static_for<DC>([&](auto E) __attribute__((always_inline)) {
     constexpr int e = E, c = T::cvar[B][e], s = T::cshift[B][e];
-    const double post = L + (double)row_ror_f32<(16 - s) & 15>(S[c]);
+    double post;
+    if constexpr (qc_post64<T>(c)) post = row_ror_f64<(16 - s) & 15>(P[c]);
+    else post = L + (double)row_ror_f32<(16 - s) & 15>(S[c]);
     v[e] = post - (double)c2v[B][e];                      // v2c = post - c2v (:177)
     hv[e] = hi_word(v[e]);
     hp[e] = hi_word(post);
@@ -175,7 +237,7 @@ __device__ __forceinline__ void flood_qc_body(const DecodeArgs& a) {
   constexpr int MB = T::MB, NB = T::NB, DC = T::DC;
   static_assert(qc::kLift == 16, "one DPP row per half-shot");
   const int lane = threadIdx.x & 63;
-  const int k = lane & 15, q = lane >> 4, rowsh = lane & 48;
+  const int q = lane >> 4, rowsh = lane & 48;
   const int waves = blockDim.x >> 6;
   const long long rows = 4ll * gridDim.x * waves;
   const long long batch = a.batch;
@@ -183,6 +245,7 @@ __device__ __forceinline__ void flood_qc_body(const DecodeArgs& a) {
   constexpr int wn = (n + 63) / 64;
 
   float c2v[MB][DC], S[NB];
+  double P[NB];                          // S[c] or P[c] per block (qc_post64): constant indices only
   int it = 0, fl = 0;
   uint32_t synreg = 0;
   long long hs = 4ll * ((long long)blockIdx.x * waves + (threadIdx.x >> 6)) + q;
@@ -202,13 +265,14 @@ __device__ __forceinline__ void flood_qc_body(const DecodeArgs& a) {
     if (finb != 0) {
       if (started) {
         if (fin) {
-          // outputs in original variable order: column 16 c + k is this lane's S[c].
+          // outputs in original variable order: column 16 c + k is this lane's block c.
           // Arguments and lane offsets used only here are formed here: read afresh
           // (kargs_fresh) and behind an opaque lane, they hold no registers in the loop
           const DecodeArgs& f = kargs_fresh();
-          int kl = k, rsh = rowsh;
-          asm volatile("" : "+v"(kl), "+v"(rsh));
-          // (each posterior formed where it is used: NB doubles at once do not fit the registers)
+          int ln = threadIdx.x;
+          asm volatile("" : "+v"(ln));
+          const int kl = ln & 15, rsh = ln & 48;
+          // (a float32 block's posterior formed where it is used)
           if (f.eh_bits) {
             // word w of this row: blocks 4 w .. 4 w + 3, 16 ballot bits each; lane k = w stores it
             uint32_t lo = 0, hi = 0;
@@ -216,7 +280,7 @@ __device__ __forceinline__ void flood_qc_body(const DecodeArgs& a) {
               uint32_t r[4] = {0, 0, 0, 0};
               static_for<4>([&](auto I) __attribute__((always_inline)) {
                 constexpr int c = 4 * W + I;
-                if constexpr (c < NB) r[I] = row_bits(ballot_b(a.L + (double)S[c] < 0.0), rsh);
+                if constexpr (c < NB) r[I] = row_bits(ballot_b(qc_post<T, c>(a.L, S, P) < 0.0), rsh);
               });
               if (kl == W) lo = r[0] | (r[1] << 16), hi = r[2] | (r[3] << 16);
             });
@@ -224,12 +288,12 @@ __device__ __forceinline__ void flood_qc_body(const DecodeArgs& a) {
           } else {
             uint8_t* eo = f.ehat + hs * (long long)n + kl;
             static_for<NB>([&](auto C) __attribute__((always_inline)) {
-              eo[16 * C] = (uint8_t)(a.L + (double)S[C] < 0.0);
+              eo[16 * C] = (uint8_t)(qc_post<T, C>(a.L, S, P) < 0.0);
             });
           }
           if (f.post) {
             double* po = f.post + hs * (long long)n + kl;
-            static_for<NB>([&](auto C) __attribute__((always_inline)) { po[16 * C] = a.L + (double)S[C]; });
+            static_for<NB>([&](auto C) __attribute__((always_inline)) { po[16 * C] = qc_post<T, C>(a.L, S, P); });
           }
           const bool mz = row_bits(ballot_b((fl & FLAG_MIN_ZERO) != 0), rsh) != 0;
           if (kl == 0) {
@@ -258,8 +322,9 @@ __device__ __forceinline__ void flood_qc_body(const DecodeArgs& a) {
         it = 0, synreg = 0;
         if (live) {
           const DecodeArgs& f = kargs_fresh();
-          int kl = k;
-          asm volatile("" : "+v"(kl));
+          int ln = threadIdx.x;
+          asm volatile("" : "+v"(ln));
+          const int kl = ln & 15;
           if (f.syn_bits) {              // 64-bit words: check 16 b + k is bit 16 (b & 1) + k of half-word b >> 1
             const uint32_t* row = (const uint32_t*)((const uint64_t*)f.syn + hs * f.wm);
             uint32_t w[(MB + 1) / 2];
@@ -276,9 +341,11 @@ __device__ __forceinline__ void flood_qc_body(const DecodeArgs& a) {
             for (int b = 0; b < MB; ++b) synreg |= (w[b] & 1u) << b;
           }
         }
-        const double vf = (double)a.L32;
+        // (L32 and beta read afresh: their products hold no registers in the loop)
+        const DecodeArgs& g = kargs_fresh();
+        const double vf = (double)g.L32;
         const double av = __builtin_fabs(vf);
-        const uint32_t cb = __builtin_bit_cast(uint32_t, (float)(a.beta * av));
+        const uint32_t cb = __builtin_bit_cast(uint32_t, (float)(g.beta * av));
         const uint32_t neg = (uint32_t)(vf < 0.0);
         fl = av == 0.0 ? FLAG_MIN_ZERO : 0;
         static_for<MB>([&](auto B) __attribute__((always_inline)) {
@@ -293,15 +360,21 @@ __device__ __forceinline__ void flood_qc_body(const DecodeArgs& a) {
 
     if (live) {
       static_for<NB>([&](auto C) __attribute__((always_inline)) {
-        float& sc = S[C];
-        sc = qc_colsum<T, C>(c2v);
-        asm volatile("" : "+v"(sc));                      // one variable block at a time
+        if constexpr (qc_post64<T>(C)) {
+          double& pc = P[C];
+          pc = a.L + (double)qc_colsum<T, C>(c2v);
+          asm volatile("" : "+v"(pc));                    // one variable block at a time
+        } else {
+          float& sc = S[C];
+          sc = qc_colsum<T, C>(c2v);
+          asm volatile("" : "+v"(sc));
+        }
       });
       it += 1;
       if (it == a.max_iter) {
         uint32_t hw[(NB + 31) / 32] = {};
         static_for<NB>([&](auto C) __attribute__((always_inline)) {
-          hw[C / 32] |= (hi_word(a.L + (double)S[C]) >> 31) << (C % 32);
+          hw[C / 32] |= (hi_word(qc_post<T, C>(a.L, S, P)) >> 31) << (C % 32);
         });
         uint32_t un = 0;
         static_for<MB>([&](auto B) __attribute__((always_inline)) {
@@ -314,7 +387,7 @@ __device__ __forceinline__ void flood_qc_body(const DecodeArgs& a) {
     if (live && !fin) {
       uint32_t unsat = 0;
       static_for<MB>([&](auto B) __attribute__((always_inline)) {
-        unsat |= qc_check<T, B>(a, a.L, S, c2v, (synreg >> B) & 1u, fl);
+        unsat |= qc_check<T, B>(a, a.L, S, P, c2v, (synreg >> B) & 1u, fl);
       });
       // stop test of iteration it - 1 (decoders.py:175-176)
       if (row_bits(ballot_b(unsat != 0), rowsh) == 0) fin = true, conv = true, iters = it;
