@@ -83,6 +83,7 @@ extern "C" {
 typedef struct qldpc_code qldpc_code;         /* Tanner graph of one H, resident in HBM */
 typedef struct qldpc_schedule qldpc_schedule; /* layer partition bound to one code     */
 typedef struct qldpc_logicals qldpc_logicals; /* logical operators of a CSS pair, in HBM */
+typedef struct qldpc_relay qldpc_relay;       /* relay min-sum: legs and memory strengths of one code */
 
 const char *qldpc_last_error(void);
 const char *qldpc_version(void);
@@ -201,6 +202,59 @@ int qldpc_decode_host_prior(const qldpc_code *code, const qldpc_schedule *sched,
  * it (e.g. "decode_prior_kernel<0, false, 8>"); needs no device. */
 int qldpc_decode_prior_kernel_name(const qldpc_code *code, const qldpc_schedule *sched, int algo, char *buf,
                                    int len);
+
+/* Relay min-sum (Relay-BP, Mueller et al. 2025): flooding
+ * min-sum whose prior is blended with each variable's own previous posterior,
+ *   Lam_j = fl((1 - gamma[r][j]) L) + fl(gamma[r][j] M_j),   M_j = Lam_j + S_j,
+ * run as `legs` chained legs of leg_iters[r] iterations: leg 0 starts from
+ * M = L, every later leg from the previous leg's M with c2v = 0; a leg ends at
+ * its first pass whose hard decisions (M < 0) satisfy the syndrome, and the
+ * decoder stops after `sols` such solutions, keeping the lightest (ties: the
+ * earlier). No reference counterpart; with one leg, gamma = 0 and sols = 1 it
+ * is min-sum flooding bit for bit (e_hat, iterations, posteriors, CONVERGED).
+ *   h_leg_iters  int32 [legs], each >= 1, their sum <= 2^20
+ *   h_gamma      float64 [legs][n_gamma], original column order, finite;
+ *                n_gamma must be the code's n
+ *   sols         >= 1
+ * Anything else is QLDPC_EINVAL. Limits are the generic LDS kernel's: m, n and
+ * edges <= 65535, row degree <= 32, tables and one wave's state within the
+ * LDS; past them, and with option "force_hbm" set, QLDPC_EUNSUP (there is no
+ * HBM-resident variant). Creation needs no device (decoding does). */
+int qldpc_relay_create(const qldpc_code *code, int legs, const int32_t *h_leg_iters, const double *h_gamma,
+                       int n_gamma, int sols, qldpc_relay **out);
+int qldpc_relay_destroy(qldpc_relay *relay);
+
+/* The per-wave LDS layout of the relay kernel (no device needed), bytes:
+ * out7 = {graph image, wave slice, offsets inside the slice of c2v, the
+ * syndrome words, the posterior row M, the hard-decision words, the
+ * best-solution words}; the row the check nodes read is at offset 0. */
+int qldpc_relay_layout(const qldpc_relay *relay, int32_t *out7);
+
+/* Decode `batch` syndromes with the handle's legs; device pointers,
+ * asynchronous on `stream`. Buffers and formats as qldpc_decode_device_ex;
+ * the prior is L = log((1-p)/max(p, eps)), beta the min-sum normalisation.
+ *   d_iters  int32 [batch]  passes run over all legs
+ *   d_post   float64 [batch][n] (nullable) the last pass's M
+ *   d_flags  int32 [batch] (nullable) QLDPC_FLAG_CONVERGED iff a solution was
+ *            found; QLDPC_FLAG_MIN_ZERO if a check-node pass met a zero minimum
+ *   d_info   int32 [batch][2] (nullable) solutions found, and the leg of the
+ *            one returned (-1: none; e_hat is then the last pass's M < 0)
+ * Arguments are checked before any HIP call. Options "static_sched",
+ * "waves_per_wg" and "wg_per_cu" apply as for qldpc_decode_device. */
+int qldpc_decode_device_relay(const qldpc_code *code, const qldpc_relay *relay, const void *d_syn, int syn_format,
+                              int64_t batch, double p, double beta, double eps, void *d_ehat, int ehat_format,
+                              int32_t *d_iters, double *d_post, int32_t *d_flags, int32_t *d_info, void *stream);
+
+/* Same with host buffers (one byte per bit), staged like qldpc_decode_host. */
+int qldpc_decode_host_relay(const qldpc_code *code, const qldpc_relay *relay, const uint8_t *h_syn, int64_t batch,
+                            double p, double beta, double eps, uint8_t *h_ehat, int32_t *h_iters, double *h_post,
+                            int32_t *h_flags, int32_t *h_info);
+
+/* Name of the kernel qldpc_decode_device_relay launches ("relay_ms_kernel<8>";
+ * needs no device) and its launch geometry (as qldpc_decode_launch_info). */
+int qldpc_decode_relay_kernel_name(const qldpc_code *code, const qldpc_relay *relay, char *buf, int len);
+int qldpc_decode_relay_launch_info(const qldpc_code *code, const qldpc_relay *relay, int *waves_per_wg,
+                                   int *wg_per_cu, int *lds_bytes);
 
 /* The hard-decision decoders, batched, device pointers, asynchronous on
  * `stream`. Replaces `batch` calls of NG_decoder(H, syndrome)

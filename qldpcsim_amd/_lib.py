@@ -28,6 +28,8 @@ EXPORTS = (
     "qldpc_decode_device", "qldpc_decode_device_ex", "qldpc_decode_host", "qldpc_decode_kernel_name",
     "qldpc_decode_launch_info",
     "qldpc_decode_device_prior", "qldpc_decode_host_prior", "qldpc_decode_prior_kernel_name",
+    "qldpc_relay_create", "qldpc_relay_destroy", "qldpc_relay_layout", "qldpc_decode_device_relay",
+    "qldpc_decode_host_relay", "qldpc_decode_relay_kernel_name", "qldpc_decode_relay_launch_info",
     "qldpc_hard_decode_device", "qldpc_hard_decode_host", "qldpc_hard_kernel_name", "qldpc_hard_launch_info",
     "qldpc_osd_decode", "qldpc_osd_decode_batch", "qldpc_osd_device", "qldpc_osd_order_device",
     "qldpc_osd_device_ordered", "qldpc_osd_device_ordered_ex", "qldpc_cpython_setdiff_first",
@@ -79,6 +81,13 @@ def _load():
         "qldpc_decode_device_prior": ([P, P, I, P, I, I64, D, D, P, I, I, D, D, P, I, P, P, P, P], I),
         "qldpc_decode_host_prior": ([P, P, I, P, I64, D, D, P, I, D, D, P, P, P, P], I),
         "qldpc_decode_prior_kernel_name": ([P, P, I, ctypes.c_char_p, I], I),
+        "qldpc_relay_create": ([P, I, P, P, I, I, PP], I),
+        "qldpc_relay_destroy": ([P], I),
+        "qldpc_relay_layout": ([P, P], I),
+        "qldpc_decode_device_relay": ([P, P, P, I, I64, D, D, D, P, I, P, P, P, P, P], I),
+        "qldpc_decode_host_relay": ([P, P, P, I64, D, D, D, P, P, P, P, P], I),
+        "qldpc_decode_relay_kernel_name": ([P, P, ctypes.c_char_p, I], I),
+        "qldpc_decode_relay_launch_info": ([P, P, ctypes.POINTER(I), ctypes.POINTER(I), ctypes.POINTER(I)], I),
         "qldpc_hard_decode_device": ([P, I, P, I, I64, I, P, I, P, P, P], I),
         "qldpc_hard_decode_host": ([P, I, P, I64, I, P, P, P], I),
         "qldpc_hard_kernel_name": ([P, I, ctypes.c_char_p, I], I),
@@ -166,6 +175,51 @@ class Schedule:
             self.handle = None
 
 
+class Relay:
+    """Legs, memory strengths and solution count of a relay min-sum decoder
+    bound to a Code (qldpc_relay). `gammas` is float64 [legs, n] in original
+    column order."""
+
+    def __init__(self, code, leg_iters, gammas, sols):
+        self.code = code
+        self.leg_iters = np.ascontiguousarray(leg_iters, dtype=np.int32).reshape(-1)
+        g = np.ascontiguousarray(gammas, dtype=np.float64)
+        if g.ndim != 2 or g.shape[0] != len(self.leg_iters):
+            raise ValueError(f"gammas must be float64 [{len(self.leg_iters)}, {code.n}] (one row per leg)")
+        self.gammas = g
+        self.sols = int(sols)
+        h = ctypes.c_void_p()
+        check(lib.qldpc_relay_create(code.handle, len(self.leg_iters), ptr(self.leg_iters), ptr(g), g.shape[1],
+                                     self.sols, ctypes.byref(h)))
+        self.handle = h
+
+    def layout(self):
+        """Per-wave LDS layout of the relay kernel (no device needed): bytes of
+        the graph image and of a wave's slice, and the offsets inside it."""
+        out = np.zeros(7, np.int32)
+        check(lib.qldpc_relay_layout(self.handle, ptr(out)))
+        return dict(zip(("image", "wave_bytes", "off_c2v", "off_synw", "off_m", "off_ew", "off_best"),
+                        (int(x) for x in out)))
+
+    def kernel_name(self):
+        buf = ctypes.create_string_buffer(128)
+        check(lib.qldpc_decode_relay_kernel_name(self.code.handle, self.handle, buf, 128))
+        return buf.value.decode()
+
+    def launch_info(self):
+        """(waves per workgroup, workgroups per CU, LDS bytes per workgroup)"""
+        w, b, l = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        check(lib.qldpc_decode_relay_launch_info(self.code.handle, self.handle, ctypes.byref(w), ctypes.byref(b),
+                                                 ctypes.byref(l)))
+        return w.value, b.value, l.value
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h and lib is not None:
+            lib.qldpc_relay_destroy(h)
+            self.handle = None
+
+
 class Code:
     """Tanner graph of one parity-check matrix, resident on the current device."""
 
@@ -180,7 +234,19 @@ class Code:
         check(lib.qldpc_code_create(ptr(Hc), self.m, self.n, ctypes.byref(h)))
         self.handle = h
         self._sched = {}
+        self._relay = {}
         self._lock = threading.Lock()
+
+    def relay(self, leg_iters, gammas, sols):
+        """Cached Relay handle per (leg counts, table bytes, sols), as schedules are."""
+        key = (np.asarray(leg_iters, np.int32).tobytes(), np.ascontiguousarray(gammas, np.float64).tobytes(),
+               int(sols))
+        with self._lock:
+            r = self._relay.get(key)
+            if r is None:
+                r = Relay(self, leg_iters, gammas, sols)
+                self._relay[key] = r
+            return r
 
     def schedule(self, layer_ptr, layer_rows):
         key = (np.asarray(layer_ptr, np.int32).tobytes(), np.asarray(layer_rows, np.int32).tobytes())
@@ -195,6 +261,7 @@ class Code:
         h = getattr(self, "handle", None)
         if h and lib is not None:
             self._sched = {}
+            self._relay = {}
             lib.qldpc_code_destroy(h)
             self.handle = None
 

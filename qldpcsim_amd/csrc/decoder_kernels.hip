@@ -2240,8 +2240,10 @@ __global__ void __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))
 // translation units of their own (bp_team_kernels.hip, built without SLP
 // vectorization; ms_flood_kernels.hip, built with the max-ILP machine
 // scheduler), and so are the two-level-prior kernels
-// (decode_prior_kernels.hip); every other kernel here.
-#if defined(QLDPC_TU_PRIOR)
+// (decode_prior_kernels.hip); every other kernel here. relay_kernels.hip
+// takes the device functions alone and brings its own helpers.
+#if defined(QLDPC_TU_RELAY)
+#elif defined(QLDPC_TU_PRIOR)
 
 const void* select_prior_kernel(int algo, bool layered, int dc, const char** name) {
   static const char* names[2][2][3] = {

@@ -50,6 +50,7 @@ from . import _lib, hostcores
 from .schedule import pack_layers
 
 __all__ = ["MS_decoder", "BP_decoder", "NG_decoder", "BF_decoder", "OSDdec", "decode_batch", "DecodeResult",
+           "Relay_decoder", "RelayConfig", "relay_gammas",
            "osd_perm", "pack_bits", "unpack_bits",
            "osd_perms", "apply_osd", "apply_osd_device", "apply_osd_device_many", "osd_device_stage",
            "osd_device_finish", "osd_host_orders", "osd_status_check", "numpy_order_pinned",
@@ -62,10 +63,39 @@ class DecodeResult:
     iters: object         # int32 [B]
     post: object          # float64 [B, n] or None
     flags: object         # int32 [B]
+    info: object = None   # algo "RELAY": int32 [B, 2] (solutions found, leg of the one returned or -1)
 
     @property
     def converged(self):
         return (self.flags & _lib.FLAG_CONVERGED) != 0
+
+    @property
+    def found(self):
+        return None if self.info is None else self.info[:, 0]
+
+    @property
+    def best_leg(self):
+        return None if self.info is None else self.info[:, 1]
+
+
+@dataclass
+class RelayConfig:
+    """Settings of decode_batch(algo="RELAY"): iterations per leg, the memory
+    strengths float64 [legs, n] in original column order (relay_gammas), and
+    the number of solutions to stop at."""
+    leg_iters: object
+    gammas: object
+    sols: int = 1
+
+
+def relay_gammas(n, legs, gamma0=0.125, lo=-0.24, hi=0.66, seed=0):
+    """Memory strengths float64 [legs, n] of a relay decoder: row 0 is gamma0
+    for every variable, rows 1.. are np.random.default_rng(seed).uniform(lo, hi,
+    (legs - 1, n)) (Relay-BP's disordered legs, some strengths negative)."""
+    g = np.empty((int(legs), int(n)), np.float64)
+    g[0] = gamma0
+    g[1:] = np.random.default_rng(seed).uniform(lo, hi, (int(legs) - 1, int(n)))
+    return g
 
 
 def _is_torch(x):
@@ -93,7 +123,7 @@ def unpack_bits(words, k):
 
 def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, eps=1e-9,
                  want_post=False, osd_order=-1, layer_ptr=None, layer_rows=None, stream=None,
-                 out=None, ehat_bits=False, prior_mask=None, p_masked=None):
+                 out=None, ehat_bits=False, prior_mask=None, p_masked=None, relay=None):
     """Decode a batch of syndromes of one matrix on the GPU.
 
     syndromes: uint8 [B, m] NumPy array (host; staged, synchronous) or a
@@ -117,7 +147,18 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
     host path: a uint8 [B, n] array. Runs decode_prior_kernel, the generic LDS
     kernel's twin: NotImplementedError for a code it cannot hold or with
     option force_hbm. With p_masked == p the result is the scalar decode's.
+    `algo="RELAY"` with `relay=RelayConfig(...)`: relay min-sum (DESIGN.md
+    §3.11), flooding only. `max_iter` is ignored: the legs carry their own
+    counts (relay.leg_iters). layers other than flooding, prior_mask and
+    osd_order >= 0 raise ValueError (post is returned with want_post, so a
+    caller can run OSDdec on the failures). The result's `info` (`found`,
+    `best_leg`) says how many solutions each shot met and which leg's was kept.
     """
+    if algo == "RELAY":
+        return _decode_batch_relay(H, syndromes, p, relay, layers, beta, eps, want_post, osd_order, layer_ptr,
+                                   layer_rows, stream, out, ehat_bits, prior_mask, p_masked)
+    if relay is not None:
+        raise ValueError('relay= goes with algo="RELAY"')
     if algo not in _lib.ALGO:
         raise ValueError("Unrecognized decoder type.")
     if (prior_mask is None) != (p_masked is None):
@@ -226,6 +267,89 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
     if osd_order >= 0:
         apply_osd(H, syn, ehat, post, flags, osd_order)
     return res
+
+
+def _decode_batch_relay(H, syndromes, p, relay, layers, beta, eps, want_post, osd_order, layer_ptr, layer_rows,
+                        stream, out, ehat_bits, prior_mask, p_masked):
+    """decode_batch for algo "RELAY" (relay_ms_kernel)."""
+    if not isinstance(relay, RelayConfig):
+        raise ValueError('algo="RELAY" needs relay=RelayConfig(leg_iters, gammas, sols)')
+    if prior_mask is not None or p_masked is not None:
+        raise ValueError("relay min-sum takes no two-level prior (prior_mask)")
+    if osd_order >= 0:
+        raise ValueError("relay min-sum has no OSD step (decode with want_post and run OSDdec on the failures)")
+    H = np.asarray(H)
+    if H.ndim != 2:
+        raise ValueError("H must be a 2-D matrix")
+    m, n = H.shape
+    if layer_ptr is None:
+        layer_ptr, layer_rows = pack_layers(layers, m)
+    if not (len(layer_ptr) == 2 and np.array_equal(np.sort(np.asarray(layer_rows)), np.arange(m))):
+        raise ValueError("relay min-sum runs the flooding schedule only (layers=None)")
+    T = np.asarray(relay.leg_iters, np.int64).reshape(-1)
+    G = np.asarray(relay.gammas, np.float64)
+    if G.shape != (len(T), n):
+        raise ValueError(f"relay.gammas must be float64 [{len(T)}, {n}] (one row per leg, one entry per variable)")
+    if _is_torch(syndromes):
+        import torch
+        dev = syndromes.device
+        code = _lib.code_for(H, dev.index)
+        rl = code.relay(T, G, relay.sols)
+        syn = syndromes.contiguous()
+        wm, wn = (m + 63) // 64, (n + 63) // 64
+        if syn.dim() == 2 and syn.dtype == torch.uint8 and syn.shape[1] == m:
+            syn_fmt = _lib.FMT_BYTES
+        elif syn.dim() == 2 and syn.dtype == torch.int64 and syn.shape[1] == wm:
+            syn_fmt = _lib.FMT_BITS
+        else:
+            raise ValueError(f"syndromes must be uint8 [B, {m}] or int64 words [B, {wm}]")
+        B = syn.shape[0]
+        e_shape, e_dtype = ((B, wn), torch.int64) if ehat_bits else ((B, n), torch.uint8)
+        if out is not None:
+            ehat, iters, flags, info = out.ehat, out.iters, out.flags, out.info
+            post = out.post if want_post else None
+            ok = (ehat.shape == e_shape and ehat.dtype == e_dtype and iters.shape == (B,) and
+                  iters.dtype == torch.int32 and flags.shape == (B,) and flags.dtype == torch.int32 and
+                  info is not None and info.shape == (B, 2) and info.dtype == torch.int32 and
+                  all(t.device == dev and t.is_contiguous() for t in (ehat, iters, flags, info)) and
+                  (not want_post or (post is not None and post.shape == (B, n) and
+                                     post.dtype == torch.float64 and post.device == dev and
+                                     post.is_contiguous())))
+            if not ok:
+                raise ValueError("out buffers do not match the batch (uint8 [B, n] or int64 [B, ceil(n/64)], "
+                                 "int32 [B], int32 [B], int32 info [B, 2], float64 [B, n] if want_post) on the "
+                                 "syndromes' device")
+        else:
+            ehat = torch.empty(e_shape, dtype=e_dtype, device=dev)
+            iters = torch.empty(B, dtype=torch.int32, device=dev)
+            flags = torch.empty(B, dtype=torch.int32, device=dev)
+            info = torch.empty((B, 2), dtype=torch.int32, device=dev)
+            post = torch.empty((B, n), dtype=torch.float64, device=dev) if want_post else None
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.lib.qldpc_decode_device_relay(
+            code.handle, rl.handle, syn.data_ptr(), syn_fmt, B, float(p), float(beta), float(eps), ehat.data_ptr(),
+            _lib.FMT_BITS if ehat_bits else _lib.FMT_BYTES, iters.data_ptr(),
+            post.data_ptr() if post is not None else None, flags.data_ptr(), info.data_ptr(), st))
+        return DecodeResult(ehat, iters, post, flags, info)
+
+    syn = np.ascontiguousarray(syndromes)
+    if syn.ndim != 2 or syn.shape[1] != m:
+        raise ValueError(f"syndromes must be [B, {m}]")
+    if syn.size and (syn.min() < 0 or syn.max() > 1):
+        raise ValueError("syndrome entries must be 0 or 1")
+    syn = syn.astype(np.uint8, copy=False)
+    B = syn.shape[0]
+    code = _lib.code_for(H)
+    rl = code.relay(T, G, relay.sols)
+    ehat = np.zeros((B, n), np.uint8)
+    iters = np.zeros(B, np.int32)
+    flags = np.zeros(B, np.int32)
+    info = np.zeros((B, 2), np.int32)
+    post = np.zeros((B, n), np.float64) if want_post else None
+    _lib.check(_lib.lib.qldpc_decode_host_relay(
+        code.handle, rl.handle, _lib.ptr(syn), B, float(p), float(beta), float(eps), _lib.ptr(ehat),
+        _lib.ptr(iters), _lib.ptr(post), _lib.ptr(flags), _lib.ptr(info)))
+    return DecodeResult(ehat, iters, post, flags, info)
 
 
 def _decode_batch_hard(H, syndromes, max_iter, algo, want_post, osd_order, stream, out, ehat_bits):
@@ -863,6 +987,23 @@ def BP_decoder(H: np.ndarray, syndrome: np.ndarray, p: float, max_iter: int = 99
     if not conv and OSDorder >= 0:                 # (:287-288)
         e_hat = OSDdec(H, e_hat, syndrome, post, OSDorder)
     return e_hat, it
+
+
+def Relay_decoder(H: np.ndarray, syndrome: np.ndarray, p: float, leg_iters, gammas, sols: int = 1,
+                  beta: float = 0.75, eps: float = 1e-9):
+    """Relay min-sum of one syndrome on the GPU, in the style
+    of MS_decoder: (e_hat int8 [n], passes run over all legs). `gammas` is
+    float64 [len(leg_iters), n] (relay_gammas)."""
+    H = np.asarray(H)
+    syndrome = np.asarray(syndrome)
+    if H.size == 0 or syndrome.size == 0:          # the bare array of MS_decoder
+        return np.zeros(H.shape[1] if H.size else 0, dtype=np.int8)
+    m, n = H.shape
+    if syndrome.shape != (m,):
+        raise ValueError(f"syndrome must have shape ({m},), got {syndrome.shape}")
+    r = decode_batch(H, syndrome.reshape(1, m), p, 0, algo="RELAY", beta=beta, eps=eps,
+                     relay=RelayConfig(leg_iters, gammas, sols))
+    return r.ehat[0].astype(np.int8), int(r.iters[0])
 
 
 def _single_hard(H, syndrome, algo, max_iter=1):

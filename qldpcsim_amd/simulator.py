@@ -356,7 +356,9 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
                decIterations: int = 99, decSchedule: str = "F", OSDorder: int = -1,
                rngSeed: Optional[int] = None, *, batch_size: Optional[int] = None,
                verbose: bool = True, samples=None, sampler: Optional[str] = None,
-               logical: bool = False, correlated: Optional[str] = None, correlated_q1: float = 0.49) -> dict:
+               logical: bool = False, correlated: Optional[str] = None, correlated_q1: float = 0.49,
+               relay_legs: int = 11, relay_leg_iters: int = 60, relay_sols: int = 1, relay_gamma0: float = 0.125,
+               relay_gamma_range=(-0.24, 0.66), relay_seed: int = 0) -> dict:
     """One depolarizing probability: sample, decode both halves, count.
 
     Returns the reference's dict (simulator.py:308-315). `samples`, if given,
@@ -386,7 +388,29 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
     every shot, so the default is 0.49 (LLR 0.04), which decodes as well.
     The second half runs the generic LDS kernel's twin, and with OSD the two
     halves' OSD steps are not pipelined.
+
+    `decType="RELAY"` (extension): relay min-sum, flooding
+    only. `decIterations` is the first leg's iteration count and the other
+    `relay_legs` - 1 legs run `relay_leg_iters` each; the first leg's memory
+    strength is `relay_gamma0`, the later legs draw theirs uniformly from
+    `relay_gamma_range` with np.random.default_rng(relay_seed), one table per
+    half, the Hz-decoded half first; the decoder stops at `relay_sols`
+    solutions. The defaults come from a CPU trial on LP04_0 / LP118_0 and are
+    not tuned per code. OSDorder >= 0, correlated= and a decSchedule other than
+    "F" raise ValueError.
     """
+    if decType == "RELAY":
+        if OSDorder >= 0:
+            raise ValueError("decType RELAY has no OSD step (OSDorder must be < 0)")
+        if correlated is not None:
+            raise ValueError("decType RELAY cannot be combined with correlated=")
+        if decSchedule != "F":
+            raise ValueError("decType RELAY runs the flooding schedule only (decSchedule 'F')")
+        if int(relay_legs) < 1 or int(relay_leg_iters) < 1 or int(relay_sols) < 1 or int(decIterations) < 1:
+            raise ValueError("relay_legs, relay_leg_iters, relay_sols and decIterations must be >= 1")
+        lo_, hi_ = (float(x) for x in relay_gamma_range)
+        if not (np.isfinite([lo_, hi_, float(relay_gamma0)]).all() and lo_ <= hi_):
+            raise ValueError("relay_gamma0 and relay_gamma_range (lo <= hi) must be finite")
     if rngSeed is not None:
         np.random.seed(rngSeed)                    # reference side effect (:187-188)
     dist, rank, world = _dist()
@@ -396,8 +420,17 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
     if Hz.size and Hz.shape[1] != n:
         raise ValueError("Hx and Hz must have the same number of columns (physical qubits).")
     layersX, layersZ = select_layers(Hx, Hz, decSchedule)   # raises ValueError (:236)
-    if decType not in _lib.ALGO:
+    if decType not in _lib.ALGO and decType != "RELAY":
         raise ValueError("Unrecognized decoder type.")
+    rkwX, rkwZ = {}, {}                            # decode_batch's relay= of each half
+    if decType == "RELAY":
+        T_ = [int(decIterations)] + [int(relay_leg_iters)] * (int(relay_legs) - 1)
+        grng = np.random.default_rng(relay_seed)   # one generator: the Hz-decoded half draws first
+        for kw_ in (rkwX, rkwZ):
+            G_ = np.empty((len(T_), n), np.float64)
+            G_[0] = relay_gamma0
+            G_[1:] = grng.uniform(lo_, hi_, (len(T_) - 1, n))
+            kw_["relay"] = decoders.RelayConfig(T_, G_, int(relay_sols))
     if correlated not in (None, "XZ", "ZX"):
         raise ValueError("correlated must be 'XZ', 'ZX' or None")
     if correlated is not None:
@@ -513,9 +546,9 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
                 sy_z, sy_x, errX, errZ = ch.sample(p, B, bits=packed)
                 want_post = osd >= 0
                 rX = decoders.decode_batch(Hz, sy_z, p / 3, decIterations, algo=decType, want_post=want_post,
-                                           layer_ptr=lpX, layer_rows=lrX, ehat_bits=packed)
+                                           layer_ptr=lpX, layer_rows=lrX, ehat_bits=packed, **rkwX)
                 rZ = decoders.decode_batch(Hx, sy_x, p / 3, decIterations, algo=decType, want_post=want_post,
-                                           layer_ptr=lpZ, layer_rows=lrZ, ehat_bits=packed)
+                                           layer_ptr=lpZ, layer_rows=lrZ, ehat_bits=packed, **rkwZ)
                 cur = [sy_z, sy_x, errX, errZ, rX, rZ, None]
                 done += B
             if cur is not None and osd >= 0 and stage_first:
@@ -559,9 +592,9 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
             sy_z, sy_x, errX, errZ = sample_channel(Hx, Hz, p, B, rng)
         if correlated is None:
             rX = decoders.decode_batch(Hz, sy_z, p / 3, decIterations, algo=decType, osd_order=osd,
-                                       layer_ptr=lpX, layer_rows=lrX)
+                                       layer_ptr=lpX, layer_rows=lrX, **rkwX)
             rZ = decoders.decode_batch(Hx, sy_x, p / 3, decIterations, algo=decType, osd_order=osd,
-                                       layer_ptr=lpZ, layer_rows=lrZ)
+                                       layer_ptr=lpZ, layer_rows=lrZ, **rkwZ)
         else:
             halves = [(Hz, sy_z, lpX, lrX), (Hx, sy_x, lpZ, lrZ)]
             if correlated == "ZX":
@@ -663,7 +696,9 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
              rngSeed: Optional[int] = None, *, batch_size: Optional[int] = None, verbose: bool = True,
              return_results: bool = False, sampler: Optional[str] = None,
              resultsFile: Optional[str] = None, on_point=None, logical: bool = False,
-             correlated: Optional[str] = None, correlated_q1: float = 0.49):
+             correlated: Optional[str] = None, correlated_q1: float = 0.49,
+             relay_legs: int = 11, relay_leg_iters: int = 60, relay_sols: int = 1, relay_gamma0: float = 0.125,
+             relay_gamma_range=(-0.24, 0.66), relay_seed: int = 0):
     """p-sweep + results table (simulator.py:319-347). Returns None like the
     reference unless return_results=True.
 
@@ -675,6 +710,9 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
     correlated, correlated_q1 (extension): simulate_p's correlated X/Z
     decoding for every point; both enter the results file's meta, so a sweep
     is never resumed across modes.
+
+    relay_* (extension; decType "RELAY"): simulate_p's relay min-sum settings;
+    all of them enter the results file's meta.
 
     resultsFile (extension): a JSON file the sweep writes after every
     p-point; a rerun with the same arguments skips the points already there
@@ -699,6 +737,11 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
         meta["correlated_q1"] = correlated_q1
         extra["correlated"] = correlated
         extra["correlated_q1"] = correlated_q1
+    if decType == "RELAY":
+        extra.update(relay_legs=int(relay_legs), relay_leg_iters=int(relay_leg_iters), relay_sols=int(relay_sols),
+                     relay_gamma0=float(relay_gamma0), relay_gamma_range=[float(x) for x in relay_gamma_range],
+                     relay_seed=int(relay_seed))
+        meta.update({k: v for k, v in extra.items() if k.startswith("relay_")})
     done = _load_results(resultsFile, meta)
     results = []
     for pT in p:
@@ -762,9 +805,22 @@ def main(argv=None):
     parser.add_argument("--p", type=float, nargs="+", required=True, help="Depolarizing probability.")
     parser.add_argument("--shots", type=int, default=1000, help="Number of Monte Carlo shots.")
     parser.add_argument("--rngSeed", type=int, default=None, help="RNG seed.")
-    parser.add_argument("--decType", choices=["NG", "BF", "MS", "BP"], default="MS",
+    parser.add_argument("--decType", choices=["NG", "BF", "MS", "BP", "RELAY"], default="MS",
                         help="Decoder type: [NG] Naive Greedy; [BF] Bit Flipping; [MS] Min-Sum; "
-                             "[BP] Belief Propagation.")
+                             "[BP] Belief Propagation; [RELAY] relay min-sum (extension: flooding min-sum with "
+                             "memory in chained disordered legs; no OSD, --decIterations is the first leg's "
+                             "count; the relay defaults come from a CPU trial and are not tuned per code).")
+    parser.add_argument("--relay-legs", type=int, default=11, dest="relay_legs", help="RELAY: number of legs.")
+    parser.add_argument("--relay-leg-iters", type=int, default=60, dest="relay_leg_iters",
+                        help="RELAY: iterations of every leg after the first.")
+    parser.add_argument("--relay-sols", type=int, default=1, dest="relay_sols",
+                        help="RELAY: solutions to stop at (the lightest is kept).")
+    parser.add_argument("--relay-gamma0", type=float, default=0.125, dest="relay_gamma0",
+                        help="RELAY: memory strength of the first leg.")
+    parser.add_argument("--relay-gamma-range", type=float, nargs=2, default=[-0.24, 0.66], metavar=("LO", "HI"),
+                        dest="relay_gamma_range", help="RELAY: later legs draw their memory strengths from U(LO, HI).")
+    parser.add_argument("--relay-seed", type=int, default=0, dest="relay_seed",
+                        help="RELAY: seed of the memory-strength tables.")
     parser.add_argument("--decIterations", type=int, default=99, help="Number of decoding iterations.")
     parser.add_argument("--decSchedule", choices=["F", "L", "S"], default="F",
                         help="Decoder scheduling method: [F] flooding; [L] layered; [S] serial.")
@@ -797,7 +853,10 @@ def main(argv=None):
                  decIterations=args.decIterations, decSchedule=args.decSchedule,
                  OSDorder=args.OSDorder, rngSeed=args.rngSeed, batch_size=args.batch,
                  sampler=args.sampler, resultsFile=args.results, **({"logical": True} if args.logical else {}),
-                 **({"correlated": args.correlated, "correlated_q1": args.correlated_q1} if args.correlated else {}))
+                 **({"correlated": args.correlated, "correlated_q1": args.correlated_q1} if args.correlated else {}),
+                 **({k: getattr(args, k) for k in ("relay_legs", "relay_leg_iters", "relay_sols", "relay_gamma0",
+                                                   "relay_gamma_range", "relay_seed")}
+                    if args.decType == "RELAY" else {}))
     finally:
         if own_group:
             import torch.distributed as dist
