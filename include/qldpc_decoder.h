@@ -84,6 +84,8 @@ typedef struct qldpc_code qldpc_code;         /* Tanner graph of one H, resident
 typedef struct qldpc_schedule qldpc_schedule; /* layer partition bound to one code     */
 typedef struct qldpc_logicals qldpc_logicals; /* logical operators of a CSS pair, in HBM */
 typedef struct qldpc_relay qldpc_relay;       /* relay min-sum: legs and memory strengths of one code */
+typedef struct qldpc_prior qldpc_prior;       /* one prior probability per variable of one code */
+typedef struct qldpc_channel qldpc_channel;   /* per-qubit Pauli probabilities of a CSS pair */
 
 const char *qldpc_last_error(void);
 const char *qldpc_version(void);
@@ -202,6 +204,50 @@ int qldpc_decode_host_prior(const qldpc_code *code, const qldpc_schedule *sched,
  * it (e.g. "decode_prior_kernel<0, false, 8>"); needs no device. */
 int qldpc_decode_prior_kernel_name(const qldpc_code *code, const qldpc_schedule *sched, int algo, char *buf,
                                    int len);
+
+/* Per-variable priors: one error probability per column of
+ * H, the `channel_probs` vector of other BP / BP-OSD packages. No reference
+ * counterpart (the reference's decoders take a scalar p).
+ *   h_p   float64 [n], original column order, every 0 <= p_j < 1 (anything
+ *         else, NaN included: QLDPC_EINVAL)
+ *   eps   decoders.py's eps (1e-9); it belongs to the handle
+ * Creation forms L_j = log((1 - p_j) / max(p_j, eps)) with NumPy's log, as the
+ * scalar entry forms L (an L_j that is not finite: QLDPC_EINVAL), permutes the
+ * row to the kernels' variable order and uploads it once (one hipMalloc, one
+ * synchronous copy). The code must outlive the handle. Without a visible
+ * device the handle is still made (as qldpc_code_create); decoding then fails
+ * with QLDPC_EHIP. A handle serves every schedule of its code. */
+int qldpc_prior_create(const qldpc_code *code, const double *h_p, double eps, qldpc_prior **out);
+int qldpc_prior_destroy(qldpc_prior *prior);
+
+/* qldpc_decode_device_ex with the handle's prior row in place of p and eps:
+ * the scalar decode's arithmetic with L replaced by the variable's own L_j
+ * everywhere (min-sum's first check-node pass reads float32(L_j) per edge;
+ * the layered schedules' initial check parities follow L_j < 0 per variable).
+ * With every p_j equal the outputs equal the scalar decode's bit for bit, and
+ * with two distinct values qldpc_decode_device_prior's whose mask rows are
+ * the indicator of the second. p_j = 0.5 behaves as p1 = 0.5 there
+ * (QLDPC_FLAG_MIN_ZERO / QLDPC_FLAG_NONFINITE). Runs decode_vprior_kernel, the
+ * generic LDS kernel's second twin, which keeps the row in LDS (8 n bytes per
+ * workgroup): QLDPC_EUNSUP, before any launch, under the conditions of
+ * qldpc_decode_device_prior (m, n or edges > 65535, MS row degree > 32, BP
+ * column degree > 128, state past the LDS, option "force_hbm"). A handle made
+ * for another code: QLDPC_EINVAL. Arguments are checked before any HIP call;
+ * asynchronous on `stream`, a launch plan of its own per (schedule, algo). */
+int qldpc_decode_device_vprior(const qldpc_code *code, const qldpc_schedule *sched, int algo, const void *d_syn,
+                               int syn_format, int64_t batch, const qldpc_prior *prior, int max_iter, double beta,
+                               void *d_ehat, int ehat_format, int32_t *d_iters, double *d_post, int32_t *d_flags,
+                               void *stream);
+
+/* Same with host buffers (one byte per bit), staged like qldpc_decode_host. */
+int qldpc_decode_host_vprior(const qldpc_code *code, const qldpc_schedule *sched, int algo, const uint8_t *h_syn,
+                             int64_t batch, const qldpc_prior *prior, int max_iter, double beta, uint8_t *h_ehat,
+                             int32_t *h_iters, double *h_post, int32_t *h_flags);
+
+/* Name of the kernel qldpc_decode_device_vprior launches, as rocprofv3 reports
+ * it (e.g. "decode_vprior_kernel<0, false, 8>"); needs no device. */
+int qldpc_decode_vprior_kernel_name(const qldpc_code *code, const qldpc_schedule *sched, int algo, char *buf,
+                                    int len);
 
 /* Relay min-sum (Relay-BP, Mueller et al. 2025): flooding
  * min-sum whose prior is blended with each variable's own previous posterior,
@@ -444,6 +490,38 @@ int qldpc_count_outcomes(const qldpc_code *hx, const qldpc_code *hz, int64_t bat
                          const uint8_t *d_syn_x, const uint8_t *d_ehat_x, const uint8_t *d_ehat_z,
                          const int32_t *d_iters_x, const int32_t *d_iters_z, int64_t *d_counters,
                          void *stream);
+
+/* ---- Inhomogeneous / biased Pauli channel --------------------------------
+ * qldpc_channel_sample_ex with probabilities per qubit. No reference
+ * counterpart (the reference's circuit is depolarizing, simulator.py:107).
+ *
+ * qldpc_channel_table (host only): the draw thresholds of n qubits into
+ * t = uint64 [3][n], in float64:
+ *   t[0][j] = min(2^32, floor(px_j 2^32)),
+ *   t[1][j] = min(2^32, floor((px_j + py_j) 2^32)),
+ *   t[2][j] = min(2^32, floor(((px_j + py_j) + pz_j) 2^32));
+ * every px_j, py_j, pz_j >= 0 and (px_j + py_j) + pz_j <= 1, else QLDPC_EINVAL
+ * (NaN included). With px = py = pz = p/3 the three are exactly
+ * qldpc_channel_thresholds(p).
+ *
+ * qldpc_channel_create: validates as above, forms the table and uploads it
+ * once to the codes' device; h_px, h_py, h_pz are float64 [n]. hx / hz must
+ * outlive the handle; n <= 4096 (QLDPC_EUNSUP past it). Without a visible
+ * device the handle is still made.
+ *
+ * qldpc_channel_sample_vec: the stream of qldpc_channel_sample — u(shot, j) is
+ * the same Philox draw — with qubit j's own thresholds: X if u < t[0][j], Y if
+ * t[0][j] <= u < t[1][j], Z if t[1][j] <= u < t[2][j]. Outputs and formats as
+ * qldpc_channel_sample_ex; with a uniform depolarizing table they are that
+ * call's bit for bit. Asynchronous on `stream`; arguments are checked before
+ * any HIP call. */
+int qldpc_channel_table(const double *px, const double *py, const double *pz, int n, uint64_t *t);
+int qldpc_channel_create(const qldpc_code *hx, const qldpc_code *hz, const double *h_px, const double *h_py,
+                         const double *h_pz, qldpc_channel **out);
+int qldpc_channel_destroy(qldpc_channel *ch);
+int qldpc_channel_sample_vec(const qldpc_channel *ch, uint64_t seed, uint64_t shot0, int64_t batch,
+                             uint64_t *d_errx, uint64_t *d_errz, void *d_syn_z, void *d_syn_x, int syn_format,
+                             void *stream);
 
 /* ---- Logical error counting of a CSS pair -------------------------------
  * The reference's "degen" counter is an integer product that real codes never

@@ -28,6 +28,8 @@ EXPORTS = (
     "qldpc_decode_device", "qldpc_decode_device_ex", "qldpc_decode_host", "qldpc_decode_kernel_name",
     "qldpc_decode_launch_info",
     "qldpc_decode_device_prior", "qldpc_decode_host_prior", "qldpc_decode_prior_kernel_name",
+    "qldpc_prior_create", "qldpc_prior_destroy", "qldpc_decode_device_vprior", "qldpc_decode_host_vprior",
+    "qldpc_decode_vprior_kernel_name",
     "qldpc_relay_create", "qldpc_relay_destroy", "qldpc_relay_layout", "qldpc_decode_device_relay",
     "qldpc_decode_host_relay", "qldpc_decode_relay_kernel_name", "qldpc_decode_relay_launch_info",
     "qldpc_hard_decode_device", "qldpc_hard_decode_host", "qldpc_hard_kernel_name", "qldpc_hard_launch_info",
@@ -36,6 +38,7 @@ EXPORTS = (
     "qldpc_osd_order_host", "qldpc_np_argsort_host", "qldpc_osd_keys_host", "qldpc_libm_eval_host",
     "qldpc_channel_thresholds", "qldpc_channel_sample", "qldpc_channel_sample_ex", "qldpc_count_outcomes",
     "qldpc_count_outcomes_ex",
+    "qldpc_channel_table", "qldpc_channel_create", "qldpc_channel_destroy", "qldpc_channel_sample_vec",
     "qldpc_logicals_create", "qldpc_logicals_destroy", "qldpc_count_logical_ex",
     "qldpc_timing_enable", "qldpc_timing_reset", "qldpc_timing_read",
     "qldpc_set_option", "qldpc_get_option",
@@ -81,6 +84,11 @@ def _load():
         "qldpc_decode_device_prior": ([P, P, I, P, I, I64, D, D, P, I, I, D, D, P, I, P, P, P, P], I),
         "qldpc_decode_host_prior": ([P, P, I, P, I64, D, D, P, I, D, D, P, P, P, P], I),
         "qldpc_decode_prior_kernel_name": ([P, P, I, ctypes.c_char_p, I], I),
+        "qldpc_prior_create": ([P, P, D, PP], I),
+        "qldpc_prior_destroy": ([P], I),
+        "qldpc_decode_device_vprior": ([P, P, I, P, I, I64, P, I, D, P, I, P, P, P, P], I),
+        "qldpc_decode_host_vprior": ([P, P, I, P, I64, P, I, D, P, P, P, P], I),
+        "qldpc_decode_vprior_kernel_name": ([P, P, I, ctypes.c_char_p, I], I),
         "qldpc_relay_create": ([P, I, P, P, I, I, PP], I),
         "qldpc_relay_destroy": ([P], I),
         "qldpc_relay_layout": ([P, P], I),
@@ -108,6 +116,10 @@ def _load():
         "qldpc_channel_sample_ex": ([P, P, D, ctypes.c_uint64, ctypes.c_uint64, I64, P, P, P, P, I, P], I),
         "qldpc_count_outcomes": ([P, P, I64, P, P, P, P, P, P, P, P, P, P], I),
         "qldpc_count_outcomes_ex": ([P, P, I64, P, P, P, P, I, P, P, I, P, P, P, P], I),
+        "qldpc_channel_table": ([P, P, P, I, P], I),
+        "qldpc_channel_create": ([P, P, P, P, P, PP], I),
+        "qldpc_channel_destroy": ([P], I),
+        "qldpc_channel_sample_vec": ([P, ctypes.c_uint64, ctypes.c_uint64, I64, P, P, P, P, I, P], I),
         "qldpc_logicals_create": ([P, P, P, P, I, PP], I),
         "qldpc_logicals_destroy": ([P], I),
         "qldpc_count_logical_ex": ([P, P, P, I64, P, P, P, P, I, P, P, I, P, P, P, P, P, P, P, P], I),
@@ -220,6 +232,28 @@ class Relay:
             self.handle = None
 
 
+class Prior:
+    """One prior error probability per variable of a Code (qldpc_prior):
+    `probs` is float64 [n] in original column order, every 0 <= p_j < 1."""
+
+    def __init__(self, code, probs, eps):
+        self.code = code
+        self.probs = np.ascontiguousarray(probs, dtype=np.float64)
+        if self.probs.shape != (code.n,):
+            raise ValueError(f"prior must hold {code.n} probabilities (one per column of H), got shape "
+                             f"{self.probs.shape}")
+        self.eps = float(eps)
+        h = ctypes.c_void_p()
+        check(lib.qldpc_prior_create(code.handle, ptr(self.probs), self.eps, ctypes.byref(h)))
+        self.handle = h
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h and lib is not None:
+            lib.qldpc_prior_destroy(h)
+            self.handle = None
+
+
 class Code:
     """Tanner graph of one parity-check matrix, resident on the current device."""
 
@@ -235,7 +269,19 @@ class Code:
         self.handle = h
         self._sched = {}
         self._relay = {}
+        self._prior = {}
         self._lock = threading.Lock()
+
+    def prior(self, probs, eps):
+        """Cached Prior handle per (probability bytes, eps), as schedules are."""
+        a = np.ascontiguousarray(probs, dtype=np.float64)
+        key = (a.tobytes(), float(eps))
+        with self._lock:
+            r = self._prior.get(key)
+            if r is None:
+                r = Prior(self, a, eps)
+                self._prior[key] = r
+            return r
 
     def relay(self, leg_iters, gammas, sols):
         """Cached Relay handle per (leg counts, table bytes, sols), as schedules are."""
@@ -262,6 +308,7 @@ class Code:
         if h and lib is not None:
             self._sched = {}
             self._relay = {}
+            self._prior = {}
             lib.qldpc_code_destroy(h)
             self.handle = None
 
@@ -328,6 +375,37 @@ class Logicals:
 _logicals_cache = {}
 
 
+def channel_table(px, py, pz):
+    """qldpc_channel_table: the draw thresholds uint64 [3, n] of per-qubit
+    Pauli probabilities (ValueError unless each is >= 0 and their sum <= 1)."""
+    px, py, pz = (np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (px, py, pz))
+    if not (px.shape == py.shape == pz.shape):
+        raise ValueError("px, py and pz must have the same length")
+    t = np.zeros((3, px.size), np.uint64)
+    check(lib.qldpc_channel_table(ptr(px), ptr(py), ptr(pz), px.size, ptr(t)))
+    return t
+
+
+class Channel:
+    """Per-qubit Pauli probabilities of the pair (cx, cz) on the codes' device
+    (qldpc_channel). Keeps both Codes alive."""
+
+    def __init__(self, cx, cz, px, py, pz):
+        self.cx, self.cz = cx, cz
+        px, py, pz = (np.ascontiguousarray(a, dtype=np.float64) for a in (px, py, pz))
+        if not (px.shape == py.shape == pz.shape == (cx.n,)):
+            raise ValueError(f"px, py and pz must each hold {cx.n} probabilities (one per qubit)")
+        h = ctypes.c_void_p()
+        check(lib.qldpc_channel_create(cx.handle, cz.handle, ptr(px), ptr(py), ptr(pz), ctypes.byref(h)))
+        self.handle = h
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h and lib is not None:
+            lib.qldpc_channel_destroy(h)
+            self.handle = None
+
+
 def logicals_for(Hx, Hz, device_index=None):
     """Cached Logicals of a CSS pair on a device: the operators come from
     logicals.css_logicals, computed and uploaded once per pair."""
@@ -376,6 +454,16 @@ def prior_kernel_name(H, layer_ptr, layer_rows, algo, device_index=None):
     sched = code.schedule(layer_ptr, layer_rows)
     buf = ctypes.create_string_buffer(128)
     check(lib.qldpc_decode_prior_kernel_name(code.handle, sched.handle, ALGO[algo], buf, 128))
+    return buf.value.decode()
+
+
+def vprior_kernel_name(H, layer_ptr, layer_rows, algo, device_index=None):
+    """Name of the kernel a decode with prior= launches for (H, schedule,
+    algo): decode_vprior_kernel<...> (NotImplementedError where it cannot run)."""
+    code = code_for(H, device_index)
+    sched = code.schedule(layer_ptr, layer_rows)
+    buf = ctypes.create_string_buffer(128)
+    check(lib.qldpc_decode_vprior_kernel_name(code.handle, sched.handle, ALGO[algo], buf, 128))
     return buf.value.decode()
 
 

@@ -97,6 +97,98 @@ extern "C" int qldpc_channel_sample_ex(const qldpc_code* hx, const qldpc_code* h
   return QLDPC_OK;
 }
 
+// ---------------------------------------------------------------------------
+// inhomogeneous Pauli channel: per-qubit thresholds, uploaded once per handle
+// ---------------------------------------------------------------------------
+struct qldpc_channel {
+  const qldpc_code* hx = nullptr;
+  const qldpc_code* hz = nullptr;
+  int mx = 0, mz = 0, ex = 0, ez = 0, n = 0;   // the pair's shapes when the table was built
+  int device = -1;
+  std::vector<uint64_t> thr;                   // [3][n]
+  DevBuf<uint64_t> d_thr;
+};
+
+extern "C" int qldpc_channel_table(const double* px, const double* py, const double* pz, int n, uint64_t* t) {
+  if (n < 0) return fail(QLDPC_EINVAL, "negative n");
+  if (n > 0 && (!px || !py || !pz || !t)) return fail(QLDPC_EINVAL, "null argument");
+  const double two32 = 4294967296.0;
+  for (int j = 0; j < n; ++j) {
+    const double xy = px[j] + py[j], xyz = xy + pz[j];
+    if (!(px[j] >= 0.0 && py[j] >= 0.0 && pz[j] >= 0.0 && xyz <= 1.0))   // (NaN fails)
+      return fail(QLDPC_EINVAL, "qubit %d: (px, py, pz) = (%g, %g, %g) must be >= 0 with a sum <= 1", j, px[j], py[j],
+                  pz[j]);
+    t[j] = (uint64_t)std::min(two32, std::floor(px[j] * two32));
+    t[(size_t)n + j] = (uint64_t)std::min(two32, std::floor(xy * two32));
+    t[2 * (size_t)n + j] = (uint64_t)std::min(two32, std::floor(xyz * two32));
+  }
+  return QLDPC_OK;
+}
+
+extern "C" int qldpc_channel_create(const qldpc_code* hx, const qldpc_code* hz, const double* h_px, const double* h_py,
+                                    const double* h_pz, qldpc_channel** out) {
+  if (!out) return fail(QLDPC_EINVAL, "out is null");
+  *out = nullptr;
+  if (!hx || !hz) return fail(QLDPC_EINVAL, "code is null");
+  if (hx->n != hz->n)
+    return fail(QLDPC_EINVAL, "Hx and Hz must have the same number of columns (physical qubits).");
+  if (hx->device != hz->device) return fail(QLDPC_EINVAL, "Hx and Hz live on different devices");
+  if ((hx->n + 63) / 64 > 64) return fail(QLDPC_EUNSUP, "the channel kernels support n <= 4096 qubits (got %d)", hx->n);
+  std::unique_ptr<qldpc_channel> ch(new qldpc_channel());
+  ch->hx = hx, ch->hz = hz;
+  ch->mx = hx->m, ch->mz = hz->m, ch->ex = hx->E, ch->ez = hz->E, ch->n = hx->n, ch->device = hx->device;
+  ch->thr.resize(3 * (size_t)ch->n);
+  if (int rc = qldpc_channel_table(h_px, h_py, h_pz, ch->n, ch->thr.data())) return rc;
+  if (ch->device >= 0) {                               // (no visible device: the handle is still made)
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev != ch->device)
+      return fail(QLDPC_EINVAL, "codes live on device %d, current device is %d", ch->device, dev);
+    HIP_TRY(ch->d_thr.upload(ch->thr));
+  }
+  *out = ch.release();
+  return QLDPC_OK;
+}
+
+extern "C" int qldpc_channel_destroy(qldpc_channel* ch) {
+  delete ch;
+  return QLDPC_OK;
+}
+
+extern "C" int qldpc_channel_sample_vec(const qldpc_channel* ch, uint64_t seed, uint64_t shot0, int64_t batch,
+                                        uint64_t* d_errx, uint64_t* d_errz, void* d_syn_z, void* d_syn_x,
+                                        int syn_format, void* stream) {
+  if (!ch) return fail(QLDPC_EINVAL, "channel handle is null");
+  if (syn_format != QLDPC_FMT_BYTES && syn_format != QLDPC_FMT_BITS)
+    return fail(QLDPC_EINVAL, "unknown syndrome format");
+  const qldpc_code *hx = ch->hx, *hz = ch->hz;
+  if (ch->n != hx->n || ch->n != hz->n || ch->mx != hx->m || ch->mz != hz->m || ch->ex != hx->E || ch->ez != hz->E)
+    return fail(QLDPC_EINVAL, "the channel handle was built for another code pair");
+  if (batch < 0) return fail(QLDPC_EINVAL, "negative batch");
+  if (batch == 0) return QLDPC_OK;
+  if (!d_errx || !d_errz || (hz->m && !d_syn_z) || (hx->m && !d_syn_x))
+    return fail(QLDPC_EINVAL, "null device buffer");
+  qldpc::SampleVecArgs va{};
+  qldpc::SampleArgs& a = va.s;
+  int rc = pair_tabs(hx, hz, &a.t);                    // no device: QLDPC_EHIP
+  if (rc != QLDPC_OK) return rc;
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev != ch->device) return fail(QLDPC_EINVAL, "codes live on device %d, current device is %d", ch->device, dev);
+  va.thr = ch->d_thr;
+  a.errx = d_errx;
+  a.errz = d_errz;
+  a.syz = (uint8_t*)d_syn_z;
+  a.syx = (uint8_t*)d_syn_x;
+  a.syn_bits = syn_format == QLDPC_FMT_BITS;
+  a.batch = batch;
+  a.shot0 = shot0;
+  a.key0 = (uint32_t)seed;
+  a.key1 = (uint32_t)(seed >> 32);
+  HIP_TRY(qldpc::launch_channel_sample_vec(va, channel_grid(batch), (hipStream_t)stream));
+  return QLDPC_OK;
+}
+
 extern "C" int qldpc_count_outcomes(const qldpc_code* hx, const qldpc_code* hz, int64_t batch,
                                     const uint64_t* d_errx, const uint64_t* d_errz, const uint8_t* d_syn_z,
                                     const uint8_t* d_syn_x, const uint8_t* d_ehat_x, const uint8_t* d_ehat_z,

@@ -3,6 +3,7 @@
 
 #include <cmath>
 #include <cstdio>
+#include <memory>
 
 #include "capi_internal.h"
 #include "../../include/qldpc_libm.h"   // after hip_runtime.h
@@ -146,21 +147,41 @@ KernelChoice capi::choose_kernel(const qldpc_schedule* s, int algo) {
   return k;
 }
 
-int capi::choose_prior_kernel(const qldpc_schedule* s, int algo, KernelChoice* k) {
+// what both prior twins of the generic LDS kernel refuse (`what` names the caller's feature)
+static int twin_limits(const qldpc_schedule* s, int algo, const char* what) {
   const qldpc_code* c = s->code;
   if (!s->lds_ok)
-    return fail(QLDPC_EUNSUP, "two-level priors: %d x %d with %d edges is past the LDS kernels' 16-bit tables "
-                "(m, n, edges, layer rows <= 65535); there is no HBM-resident variant", c->m, c->n, c->E);
+    return fail(QLDPC_EUNSUP, "%s: %d x %d with %d edges is past the LDS kernels' 16-bit tables "
+                "(m, n, edges, layer rows <= 65535); there is no HBM-resident variant", what, c->m, c->n, c->E);
   if (algo == QLDPC_ALGO_MS && c->max_row_deg > 32)
-    return fail(QLDPC_EUNSUP, "two-level priors: MS row degree %d > 32 has no LDS kernel", c->max_row_deg);
+    return fail(QLDPC_EUNSUP, "%s: MS row degree %d > 32 has no LDS kernel", what, c->max_row_deg);
   if (algo == QLDPC_ALGO_BP && c->max_col_deg > 128)
-    return fail(QLDPC_EUNSUP, "two-level priors: BP column degree %d > 128 has no LDS kernel", c->max_col_deg);
+    return fail(QLDPC_EUNSUP, "%s: BP column degree %d > 128 has no LDS kernel", what, c->max_col_deg);
   if (opt(&Options::force_hbm) != 0)
-    return fail(QLDPC_EUNSUP, "two-level priors: option force_hbm is set and there is no HBM-resident variant");
+    return fail(QLDPC_EUNSUP, "%s: option force_hbm is set and there is no HBM-resident variant", what);
+  return QLDPC_OK;
+}
+
+static const char* const kTwoLevel = "two-level priors";
+static const char* const kPerQubit = "per-variable priors";
+
+int capi::choose_prior_kernel(const qldpc_schedule* s, int algo, KernelChoice* k) {
+  const qldpc_code* c = s->code;
+  if (int rc = twin_limits(s, algo, kTwoLevel)) return rc;
   *k = KernelChoice{};
   k->max_waves = QLDPC_MAX_THREADS / 64;
   k->prior = true;
   k->kernel = qldpc::select_prior_kernel(algo, s->layered, fast_table_ok(c) ? c->uniform_deg : 0, &k->name);
+  return QLDPC_OK;
+}
+
+int capi::choose_vprior_kernel(const qldpc_schedule* s, int algo, KernelChoice* k) {
+  const qldpc_code* c = s->code;
+  if (int rc = twin_limits(s, algo, kPerQubit)) return rc;
+  *k = KernelChoice{};
+  k->max_waves = QLDPC_MAX_THREADS / 64;
+  k->vprior = true;
+  k->kernel = qldpc::select_vprior_kernel(algo, s->layered, fast_table_ok(c) ? c->uniform_deg : 0, &k->name);
   return QLDPC_OK;
 }
 
@@ -194,6 +215,11 @@ int capi::plan_static(const qldpc_schedule* s, int algo, const KernelChoice& k, 
   a->off_adj_ptr = t.off.adj_ptr, a->off_adj_vars = t.off.adj_vars, a->off_chunk_dmax = t.off.chunk_dmax;
   const bool msl = k.family == FAM_MS_LAYERED;
   wave_layout(c, s->layered, algo, msl, msl && k.lanes == 0 ? (int)s->h_lay_rows.size() : 0, k.prior, a);
+  if (k.vprior) {
+    // decode_vprior_kernel: the prior row f64[n] between the image and the slices
+    a->vprior_bytes = align16(8 * c->n);
+    image_lds += a->vprior_bytes;
+  }
   if (k.team) team_layout(c, k.team, a);
   a->m = c->m, a->n = c->n, a->E = c->E, a->n_layers = s->n_layers;
   a->wm = (c->m + 63) / 64, a->wn = (c->n + 63) / 64;
@@ -224,7 +250,10 @@ void capi::plan_static_hbm(const qldpc_schedule* s, qldpc::HbmArgs* a) {
 // ---------------------------------------------------------------------------
 // launch plan, device half: occupancy, and the cache under the schedule's lock
 // ---------------------------------------------------------------------------
-static int build_plan(qldpc_schedule* s, int algo, bool prior, LaunchPlan* p) {
+enum PlanKind { PLAN_SCALAR = 0, PLAN_PRIOR = 1, PLAN_VPRIOR = 2 };   // which of a schedule's plan arrays
+
+static int build_plan(qldpc_schedule* s, int algo, PlanKind kind, LaunchPlan* p) {
+  const bool prior = kind != PLAN_SCALAR;             // a twin of the generic LDS kernel, or nothing
   const qldpc_code* c = s->code;
   int dev = 0, max_lds = 0;
   HIP_TRY(hipGetDevice(&dev));
@@ -236,8 +265,8 @@ static int build_plan(qldpc_schedule* s, int algo, bool prior, LaunchPlan* p) {
   p->hbm = !s->lds_ok || opt(&Options::force_hbm) != 0 || (algo == QLDPC_ALGO_MS && c->max_row_deg > 32) ||
            (algo == QLDPC_ALGO_BP && c->max_col_deg > 128);
   KernelChoice pk;
-  if (prior) {                                        // decode_prior_kernel or nothing
-    if (int rc = choose_prior_kernel(s, algo, &pk)) return rc;
+  if (prior) {
+    if (int rc = kind == PLAN_PRIOR ? choose_prior_kernel(s, algo, &pk) : choose_vprior_kernel(s, algo, &pk)) return rc;
     p->hbm = false;
   }
   if (!p->hbm) {
@@ -282,8 +311,9 @@ static int build_plan(qldpc_schedule* s, int algo, bool prior, LaunchPlan* p) {
     // HBM-resident kernel decodes it; decided once per plan, not per launch
     p->hbm = best_waves == 0;
     if (prior && p->hbm)
-      return fail(QLDPC_EUNSUP, "two-level priors: the tables and one wave's state (%d + %d B) do not fit the %d B "
-                  "of LDS; there is no HBM-resident variant", image_lds, p->args.wave_bytes, max_lds);
+      return fail(QLDPC_EUNSUP, "%s: the tables and one wave's state (%d + %d B) do not fit the %d B "
+                  "of LDS; there is no HBM-resident variant", kind == PLAN_PRIOR ? kTwoLevel : kPerQubit, image_lds,
+                  p->args.wave_bytes, max_lds);
   }
   if (p->hbm) {
     p->kernel = qldpc::select_hbm_kernel(algo, c->max_row_deg, &p->name);
@@ -299,16 +329,19 @@ static int build_plan(qldpc_schedule* s, int algo, bool prior, LaunchPlan* p) {
 // The one validating way to a plan: copied into *out under the schedule's
 // lock, so a launch keeps its own consistent snapshot even if an option change
 // (qldpc_set_option) rebuilds the cached one meanwhile.
-static int resolve_plan(const qldpc_code* code, qldpc_schedule* s, int algo, LaunchPlan* out, bool prior = false) {
+static int resolve_plan(const qldpc_code* code, qldpc_schedule* s, int algo, LaunchPlan* out,
+                        PlanKind kind = PLAN_SCALAR) {
   if (algo != QLDPC_ALGO_MS && algo != QLDPC_ALGO_BP) return fail(QLDPC_EINVAL, "Unrecognized decoder type.");
   if (code->device < 0 || !s->generic.dev)
     return fail(QLDPC_EHIP, "no HIP device was visible when the code/schedule was created");
   std::lock_guard<std::mutex> lk(s->mu);
   const uint32_t gen = g_opt.gen.load();
-  LaunchPlan& slot = prior ? s->prior_plan[algo] : s->plan[algo];
+  LaunchPlan& slot = kind == PLAN_VPRIOR  ? s->vprior_plan[algo]
+                     : kind == PLAN_PRIOR ? s->prior_plan[algo]
+                                          : s->plan[algo];
   if (!slot.ok || slot.gen != gen) {
     LaunchPlan p{};                                   // built aside, published whole
-    const int rc = build_plan(s, algo, prior, &p);
+    const int rc = build_plan(s, algo, kind, &p);
     if (rc) return rc;
     p.ok = true;
     p.gen = gen;
@@ -507,10 +540,26 @@ static int validate_prior(const qldpc_code* code, const qldpc_schedule* sched, i
   return QLDPC_OK;
 }
 
+// everything qldpc_decode_device_vprior checks on top of the scalar entry,
+// before any HIP call
+static int validate_vprior(const qldpc_code* code, const qldpc_schedule* sched, int algo, const qldpc_prior* vp) {
+  if (!vp) return fail(QLDPC_EINVAL, "prior handle is null");
+  if (code && (vp->code != code || vp->n != code->n || vp->m != code->m || vp->E != code->E))
+    return fail(QLDPC_EINVAL, "prior handle was built for a different code");
+  if (code && sched && sched->code == code && (algo == QLDPC_ALGO_MS || algo == QLDPC_ALGO_BP)) {
+    KernelChoice k;
+    if (int rc = choose_vprior_kernel(sched, algo, &k)) return rc;
+  }
+  return QLDPC_OK;
+}
+
+// pr: the two-level prior of qldpc_decode_device_prior; vp: the per-variable
+// priors of qldpc_decode_device_vprior (p is then unread); at most one of them
 static int decode_device(const qldpc_code* code, const qldpc_schedule* sched_c, int algo,
                          const void* d_syn, int syn_format, int64_t batch, double p, int max_iter,
                          double beta, double eps, void* d_ehat, int ehat_format, int32_t* d_iters,
-                         double* d_post, int32_t* d_flags, void* stream, const PriorCall* pr) {
+                         double* d_post, int32_t* d_flags, void* stream, const PriorCall* pr,
+                         const qldpc_prior* vp = nullptr) {
   auto* sched = const_cast<qldpc_schedule*>(sched_c);
   if ((syn_format != QLDPC_FMT_BYTES && syn_format != QLDPC_FMT_BITS) ||
       (ehat_format != QLDPC_FMT_BYTES && ehat_format != QLDPC_FMT_BITS))
@@ -522,6 +571,8 @@ static int decode_device(const qldpc_code* code, const qldpc_schedule* sched_c, 
   if (max_iter < 1) return fail(QLDPC_EINVAL, "max_iter must be >= 1 (the reference leaves e_hat unbound)");
   if (pr)
     if (int rc = validate_prior(code, sched, algo, batch, p, *pr)) return rc;
+  if (vp)
+    if (int rc = validate_vprior(code, sched, algo, vp)) return rc;
   if (batch == 0) return QLDPC_OK;
   if (!d_syn || !d_ehat || !d_iters) return fail(QLDPC_EINVAL, "null device buffer");
   if (code->device < 0 || !sched->generic.dev)
@@ -530,7 +581,7 @@ static int decode_device(const qldpc_code* code, const qldpc_schedule* sched_c, 
   HIP_TRY(hipGetDevice(&dev));
   if (dev != code->device) return fail(QLDPC_EINVAL, "code lives on device %d, current device is %d", code->device, dev);
   LaunchPlan plan;
-  if (int rc = resolve_plan(code, sched, algo, &plan, pr != nullptr)) return rc;
+  if (int rc = resolve_plan(code, sched, algo, &plan, vp ? PLAN_VPRIOR : pr ? PLAN_PRIOR : PLAN_SCALAR)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (plan.hbm)
     return decode_hbm(code, sched, algo, plan,
@@ -551,6 +602,11 @@ static int decode_device(const qldpc_code* code, const qldpc_schedule* sched_c, 
     a.L1 = qldpc_prior_llr(pr->p1, eps);
     a.pmask = pr->mask;
     a.pmask_bits = pr->mask_format == QLDPC_FMT_BITS;
+  }
+  if (vp) {
+    if (!vp->d_L.p) return fail(QLDPC_EHIP, "no HIP device was visible when the prior handle was created");
+    a.vprior = vp->d_L;
+    a.L = 0.0, a.L32 = 0.0f;                          // (unread: every prior comes from the row)
   }
   a.beta = beta, a.eps = eps;
   bp_saturation(eps, &a.bp_csat, &a.bp_sat_hi);
@@ -658,17 +714,26 @@ int capi::ws_reserve(qldpc_code* code, int64_t batch, bool want_post) {
   return QLDPC_OK;
 }
 
-// qldpc_decode_host, and with `pr` (a host byte mask) qldpc_decode_host_prior
+// qldpc_decode_host, with `pr` (a host byte mask) qldpc_decode_host_prior, and
+// with `vp` qldpc_decode_host_vprior
 static int decode_host(const qldpc_code* code_c, const qldpc_schedule* sched, int algo,
                        const uint8_t* h_syn, int64_t batch, double p, int max_iter,
                        double beta, double eps, uint8_t* h_ehat, int32_t* h_iters,
-                       double* h_post, int32_t* h_flags, const PriorCall* pr) {
+                       double* h_post, int32_t* h_flags, const PriorCall* pr, const qldpc_prior* vp = nullptr) {
   auto* code = const_cast<qldpc_code*>(code_c);
   if (!code) return fail(QLDPC_EINVAL, "code is null");
   if (batch < 0) return fail(QLDPC_EINVAL, "negative batch");
   if (pr) {
     if (!sched) return fail(QLDPC_EINVAL, "code/schedule is null");
     if (int rc = validate_prior(code, sched, algo, batch, p, *pr)) return rc;
+  }
+  if (vp) {
+    // (the checks decode_device makes before any HIP call, made before the staging copies)
+    if (!sched) return fail(QLDPC_EINVAL, "code/schedule is null");
+    if (sched->code != code) return fail(QLDPC_EINVAL, "schedule was built for a different code");
+    if (algo != QLDPC_ALGO_MS && algo != QLDPC_ALGO_BP) return fail(QLDPC_EINVAL, "Unrecognized decoder type.");
+    if (max_iter < 1) return fail(QLDPC_EINVAL, "max_iter must be >= 1 (the reference leaves e_hat unbound)");
+    if (int rc = validate_vprior(code, sched, algo, vp)) return rc;
   }
   if (batch == 0) return QLDPC_OK;
   if (!h_syn || !h_ehat || !h_iters) return fail(QLDPC_EINVAL, "null host buffer");
@@ -698,7 +763,7 @@ static int decode_host(const qldpc_code* code_c, const qldpc_schedule* sched, in
   }
   int rc = decode_device(code, sched, algo, code->ws_syn, QLDPC_FMT_BYTES, batch, p, max_iter, beta, eps,
                          code->ws_ehat, QLDPC_FMT_BYTES, code->ws_iters, h_post ? code->ws_post.p : nullptr,
-                         code->ws_flags, st, pr ? &dpr : nullptr);
+                         code->ws_flags, st, pr ? &dpr : nullptr, vp);
   if (rc) return rc;
   if (batch * n) HIP_TRY(hipMemcpyAsync(code->hp_ehat, code->ws_ehat, batch * n, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(code->hp_iters, code->ws_iters, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, st));
@@ -728,4 +793,72 @@ extern "C" int qldpc_decode_host_prior(const qldpc_code* code, const qldpc_sched
   const PriorCall pr{p1, h_mask, QLDPC_FMT_BYTES};
   return decode_host(code, sched, algo, h_syn, batch, p0, max_iter, beta, eps, h_ehat, h_iters, h_post, h_flags,
                      &pr);
+}
+
+// ---------------------------------------------------------------------------
+// per-variable priors: the qldpc_prior handle and its decode entry points
+// ---------------------------------------------------------------------------
+extern "C" int qldpc_prior_create(const qldpc_code* code, const double* h_p, double eps, qldpc_prior** out) {
+  if (!out) return fail(QLDPC_EINVAL, "out is null");
+  *out = nullptr;
+  if (!code) return fail(QLDPC_EINVAL, "code is null");
+  if (code->n > 0 && !h_p) return fail(QLDPC_EINVAL, "per-variable priors: null probability vector");
+  const int n = code->n;
+  for (int j = 0; j < n; ++j)
+    if (!(h_p[j] >= 0.0 && h_p[j] < 1.0))             // (NaN fails both)
+      return fail(QLDPC_EINVAL, "per-variable priors: p[%d] = %g is not a probability in [0, 1)", j, h_p[j]);
+  std::unique_ptr<qldpc_prior> pr(new qldpc_prior());
+  pr->code = code;
+  pr->m = code->m, pr->n = n, pr->E = code->E;
+  pr->eps = eps;
+  pr->L.resize(n);
+  for (int j = 0; j < n; ++j) {                       // relabeled variable j is original column vperm[j]
+    pr->L[j] = qldpc_prior_llr(h_p[code->vperm[j]], eps);
+    if (!std::isfinite(pr->L[j]))
+      return fail(QLDPC_EINVAL, "per-variable priors: p[%d] = %g with eps = %g has no finite prior", code->vperm[j],
+                  h_p[code->vperm[j]], eps);
+  }
+  if (code->device >= 0) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev != code->device)
+      return fail(QLDPC_EINVAL, "code lives on device %d, current device is %d", code->device, dev);
+    HIP_TRY(pr->d_L.upload(pr->L));
+  }
+  *out = pr.release();
+  return QLDPC_OK;
+}
+
+extern "C" int qldpc_prior_destroy(qldpc_prior* prior) {
+  delete prior;
+  return QLDPC_OK;
+}
+
+extern "C" int qldpc_decode_device_vprior(const qldpc_code* code, const qldpc_schedule* sched, int algo,
+                                          const void* d_syn, int syn_format, int64_t batch, const qldpc_prior* prior,
+                                          int max_iter, double beta, void* d_ehat, int ehat_format, int32_t* d_iters,
+                                          double* d_post, int32_t* d_flags, void* stream) {
+  if (!prior) return fail(QLDPC_EINVAL, "prior handle is null");
+  return decode_device(code, sched, algo, d_syn, syn_format, batch, 0.0, max_iter, beta, prior->eps, d_ehat,
+                       ehat_format, d_iters, d_post, d_flags, stream, nullptr, prior);
+}
+
+extern "C" int qldpc_decode_host_vprior(const qldpc_code* code, const qldpc_schedule* sched, int algo,
+                                        const uint8_t* h_syn, int64_t batch, const qldpc_prior* prior, int max_iter,
+                                        double beta, uint8_t* h_ehat, int32_t* h_iters, double* h_post,
+                                        int32_t* h_flags) {
+  if (!prior) return fail(QLDPC_EINVAL, "prior handle is null");
+  return decode_host(code, sched, algo, h_syn, batch, 0.0, max_iter, beta, prior->eps, h_ehat, h_iters, h_post,
+                     h_flags, nullptr, prior);
+}
+
+extern "C" int qldpc_decode_vprior_kernel_name(const qldpc_code* code, const qldpc_schedule* sched, int algo,
+                                               char* buf, int len) {
+  if (!code || !sched || !buf || len <= 0) return fail(QLDPC_EINVAL, "null argument");
+  if (sched->code != code) return fail(QLDPC_EINVAL, "schedule was built for a different code");
+  if (algo != QLDPC_ALGO_MS && algo != QLDPC_ALGO_BP) return fail(QLDPC_EINVAL, "Unrecognized decoder type.");
+  KernelChoice k;                                     // (no device needed: the name depends on the code alone)
+  if (int rc = choose_vprior_kernel(sched, algo, &k)) return rc;
+  snprintf(buf, (size_t)len, "%s", k.name);
+  return QLDPC_OK;
 }

@@ -131,6 +131,7 @@ struct KernelChoice {
   int max_waves = 0;        // most waves per workgroup the kernel was compiled for
   int qc_table = -1;        // FAM_MS_FLOOD_QC: the generated table H expands from (qc_tables.h)
   bool prior = false;       // decode_prior_kernel: the wave slice also holds the selector bits
+  bool vprior = false;      // decode_vprior_kernel: the prior row lies behind the graph image
 };
 
 struct LaunchPlan {
@@ -222,6 +223,17 @@ struct qldpc_code {
 };
 
 // ---------------------------------------------------------------------------
+// per-variable priors of one code (capi_decode.cpp)
+// ---------------------------------------------------------------------------
+struct qldpc_prior {
+  const qldpc_code* code = nullptr;
+  int m = 0, n = 0, E = 0;       // the code's shape when the row was formed
+  double eps = 0.0;
+  std::vector<double> L;         // [n] L_j = log((1 - p_j) / max(p_j, eps)), relabeled variable order
+  capi::DevBuf<double> d_L;
+};
+
+// ---------------------------------------------------------------------------
 // schedule (layers) and its table images (capi_schedule.cpp)
 // ---------------------------------------------------------------------------
 struct qldpc_schedule {
@@ -235,6 +247,7 @@ struct qldpc_schedule {
   capi::TableImage flood_ms;     // ms_flood_kernel, uniform degree: global tables, no LDS image
   capi::LaunchPlan plan[2];   // per algo, under mu
   capi::LaunchPlan prior_plan[2];   // the same for decode_prior_kernel (qldpc_decode_device_prior)
+  capi::LaunchPlan vprior_plan[2];  // and for decode_vprior_kernel (qldpc_decode_device_vprior)
   std::mutex mu;
   // HBM-resident kernel (hbm_kernels.hip): 32-bit layer tables and a grow-only
   // slot-major workspace; hbm_ev orders launches that share the workspace
@@ -280,6 +293,8 @@ KernelChoice choose_kernel(const qldpc_schedule* s, int algo);
 // kernel cannot run the code (16-bit tables, MS row degree > 32, BP column
 // degree > 128) or option force_hbm is set; calls no HIP function
 int choose_prior_kernel(const qldpc_schedule* s, int algo, KernelChoice* k);
+// decode_vprior_kernel for (schedule, algo), with the same limits
+int choose_vprior_kernel(const qldpc_schedule* s, int algo, KernelChoice* k);
 // The generated protograph table (qc_tables.h) whose expansion is exactly the
 // code's H, or -1: compared entry by entry, not by shape or hash
 int qc_table_of(const qldpc_code* c);

@@ -30,6 +30,12 @@ struct SampleArgs {
   uint64_t t1, t2, t3;  // X: u < t1, Y: t1 <= u < t2, Z: t2 <= u < t3 (u a 32-bit draw)
 };
 
+// channel_sample_vec_kernel: the same stream with thresholds per qubit
+struct SampleVecArgs {
+  SampleArgs s;         // s.t1 .. s.t3 unread
+  const uint64_t* thr;  // [3][n]: T1_j, T2_j, T3_j (each <= 2^32), original qubit order
+};
+
 struct CountArgs {
   PairTabs t;
   const uint64_t* errx;  // [batch][W]
@@ -67,6 +73,7 @@ int channel_lds_bytes(const PairTabs& t, bool counters);
 // LDS bytes of count_logical_kernel, with both logical tables staged or not
 int logical_lds_bytes(const PairTabs& t, int kp, bool tabs_lds);
 hipError_t launch_channel_sample(const SampleArgs& a, int grid, hipStream_t stream);
+hipError_t launch_channel_sample_vec(const SampleVecArgs& a, int grid, hipStream_t stream);
 hipError_t launch_count_outcomes(const CountArgs& a, int grid, hipStream_t stream);
 hipError_t launch_count_logical(const LogicalArgs& a, int grid, hipStream_t stream);
 

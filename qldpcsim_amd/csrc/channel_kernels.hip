@@ -174,6 +174,82 @@ __global__ void __launch_bounds__(64 * kChannelWaves) channel_sample_kernel(Samp
   }
 }
 
+// channel_sample_kernel's twin for an inhomogeneous Pauli channel: the same
+// draws u(shot, j), compared with qubit j's own thresholds (X if u < T1_j, Y
+// if T1_j <= u < T2_j, Z if T2_j <= u < T3_j) from the table a.thr, uint64
+// [3][n] (a threshold may be 2^32). Lane l reads qubit 64 w + l: one coalesced
+// 512-byte row segment per threshold and word; the table is per channel, so
+// it stays in L2 across shots. With every triple equal to the scalar
+// kernel's (t1, t2, t3) the outputs are the scalar kernel's bit for bit.
+template <int DC>
+__global__ void __launch_bounds__(64 * kChannelWaves) channel_sample_vec_kernel(SampleVecArgs va) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const SampleArgs& a = va.s;
+  const PairTabs& t = a.t;
+  const Tabs tb = stage_tables(t, smem);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int W = t.W, n = t.n;
+  uint64_t* wx = reinterpret_cast<uint64_t*>(tb.tail) + wave * 2 * W;  // errX words
+  uint64_t* wz = wx + W;                                                // errZ words
+  const uint32_t* wx32 = reinterpret_cast<const uint32_t*>(wx);
+  const uint32_t* wz32 = reinterpret_cast<const uint32_t*>(wz);
+  const uint64_t* thr1 = va.thr;
+  const uint64_t* thr2 = va.thr + n;
+  const uint64_t* thr3 = va.thr + 2 * (size_t)n;
+  __syncthreads();
+  for (long long b = (long long)blockIdx.x * kChannelWaves + wave; b < a.batch;
+       b += (long long)gridDim.x * kChannelWaves) {
+    const uint64_t shot = a.shot0 + (uint64_t)b;
+    uint64_t myx = 0, myz = 0;
+    for (int wq = 0; 4 * wq < W; ++wq) {
+      const uint4 r = philox4x32_10((uint32_t)lane, (uint32_t)wq, (uint32_t)shot,
+                                    (uint32_t)(shot >> 32), a.key0, a.key1);
+      const uint32_t rr[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int w = 4 * wq + i;
+        if (w >= W) break;  // wave-uniform
+        const int j = 64 * w + lane;
+        const bool v = j < n;
+        const uint64_t t1 = v ? thr1[j] : 0, t2 = v ? thr2[j] : 0, t3 = v ? thr3[j] : 0;
+        const uint64_t u = rr[i];
+        const uint64_t bx = __ballot(v && u < t2);
+        const uint64_t bz = __ballot(v && u >= t1 && u < t3);
+        if (lane == w) {
+          myx = bx;
+          myz = bz;
+        }
+      }
+    }
+    if (lane < W) {
+      wx[lane] = myx;
+      wz[lane] = myz;
+      a.errx[b * W + lane] = myx;
+      a.errz[b * W + lane] = myz;
+    }
+    wave_sync();
+    if (a.syn_bits) {                           // one 64-bit word per 64 checks (ballot)
+      const int wmz = (t.mz + 63) >> 6, wmx = (t.mx + 63) >> 6;
+      for (int c0 = 0; c0 < t.mz; c0 += 64) {
+        const int c = c0 + lane;
+        const uint64_t bits = __ballot(c < t.mz && row_parity<DC>(tb.rpz, tb.ciz, c < t.mz ? c : 0, wx32));
+        if (lane == 0) reinterpret_cast<uint64_t*>(a.syz)[b * wmz + (c0 >> 6)] = bits;
+      }
+      for (int c0 = 0; c0 < t.mx; c0 += 64) {
+        const int c = c0 + lane;
+        const uint64_t bits = __ballot(c < t.mx && row_parity<DC>(tb.rpx, tb.cix, c < t.mx ? c : 0, wz32));
+        if (lane == 0) reinterpret_cast<uint64_t*>(a.syx)[b * wmx + (c0 >> 6)] = bits;
+      }
+    } else {
+      for (int c = lane; c < t.mz; c += 64)
+        a.syz[b * t.mz + c] = (uint8_t)row_parity<DC>(tb.rpz, tb.ciz, c, wx32);
+      for (int c = lane; c < t.mx; c += 64)
+        a.syx[b * t.mx + c] = (uint8_t)row_parity<DC>(tb.rpx, tb.cix, c, wz32);
+    }
+    wave_sync();  // the next shot overwrites wx / wz
+  }
+}
+
 // Pack one estimate row (uint8 [n], 0/1) into the per-wave LDS bit vector
 // `dst` (bytes; bit j % 8 of byte j / 8), all loads issued up front.
 // VEC: n % 4 == 0, so each lane reads 4 estimates with one aligned 32-bit
@@ -465,6 +541,16 @@ hipError_t launch_channel_sample(const SampleArgs& a, int grid, hipStream_t stre
     case 7: return launch(channel_sample_kernel<7>, &a, sizeof a, grid, lds, stream);
     case 8: return launch(channel_sample_kernel<8>, &a, sizeof a, grid, lds, stream);
     default: return launch(channel_sample_kernel<0>, &a, sizeof a, grid, lds, stream);
+  }
+}
+
+hipError_t launch_channel_sample_vec(const SampleVecArgs& a, int grid, hipStream_t stream) {
+  const int lds = channel_lds_bytes(a.s.t, false);
+  switch (uniform_degree(a.s.t)) {
+    case 6: return launch(channel_sample_vec_kernel<6>, &a, sizeof a, grid, lds, stream);
+    case 7: return launch(channel_sample_vec_kernel<7>, &a, sizeof a, grid, lds, stream);
+    case 8: return launch(channel_sample_vec_kernel<8>, &a, sizeof a, grid, lds, stream);
+    default: return launch(channel_sample_vec_kernel<0>, &a, sizeof a, grid, lds, stream);
   }
 }
 

@@ -1,6 +1,7 @@
-// decode_kernel_body.inc — the body of decode_kernel / decode_prior_kernel
-// (decoder_kernels.hip), included inside each kernel with `a` (DecodeArgs),
-// the template parameters ALGO, LAYERED, DC and a constexpr bool PRI in scope.
+// decode_kernel_body.inc — the body of decode_kernel / decode_prior_kernel /
+// decode_vprior_kernel (decoder_kernels.hip), included inside each kernel with
+// `a` (DecodeArgs), the template parameters ALGO, LAYERED, DC and a constexpr
+// int PRI (PRI_SCALAR / PRI_MASK / PRI_ROW) in scope.
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
   // Stage the read-only graph blob into LDS (16-byte vector copies).
@@ -9,6 +10,12 @@
     uint4* dst = (uint4*)lds;
     const int nvec = a.blob_bytes >> 4;
     for (int i = threadIdx.x; i < nvec; i += blockDim.x) dst[i] = src[i];
+  }
+  if constexpr (PRI == PRI_ROW) {
+    // the code's prior row (relabeled order) behind the graph image: staged
+    // once, shared by every wave of the workgroup
+    double* dst = (double*)(lds + a.blob_bytes);
+    for (int j = threadIdx.x; j < a.n; j += blockDim.x) dst[j] = a.vprior[j];
   }
   __syncthreads();
 
@@ -31,12 +38,14 @@
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
   const int waves = blockDim.x >> 6;
-  unsigned char* ws = lds + a.blob_bytes + wid * a.wave_bytes;
+  unsigned char* ws = lds + a.blob_bytes + (PRI == PRI_ROW ? a.vprior_bytes : 0) + wid * a.wave_bytes;
   double* post = (double*)ws;
   void* c2v = (void*)(ws + a.off_c2v);
   uint32_t* synw = (uint32_t*)(ws + a.off_synw);
   uint32_t* parw = (uint32_t*)(ws + a.off_parw);
-  const uint32_t* selw = PRI ? (const uint32_t*)(ws + a.off_selw) : nullptr;
+  const uint32_t* selw = PRI == PRI_ROW    ? (const uint32_t*)(lds + a.blob_bytes)       // the prior row
+                         : PRI == PRI_MASK ? (const uint32_t*)(ws + a.off_selw)
+                                           : nullptr;
 
   const int m = a.m, n = a.n;
   const int nwords = (m + 31) >> 5;
@@ -48,7 +57,7 @@
     int iters = a.max_iter;
     bool conv = false;
 
-    if constexpr (PRI) {
+    if constexpr (PRI == PRI_MASK) {
       // the half-shot's mask row (original column order) as selector bits in
       // relabeled order: lane reads the bit of variable j0 + lane's column,
       // one ballot per 64 variables (2 ceil(n / 64) words in the slice)

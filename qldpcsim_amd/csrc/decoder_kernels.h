@@ -62,12 +62,18 @@ struct DecodeArgs {
   double L1;                  // log((1-p1)/max(p1,eps))
   int pmask_bits;             // the mask's format, as syn_bits
   int off_selw;               // inside a wave slice: selector bits, relabeled order (2 ceil(n/64) words)
+  // decode_vprior_kernel: variable j's prior is vprior[j]; each workgroup keeps
+  // a copy in LDS between the graph image and the wave slices
+  const double* vprior;       // [n] relabeled variable order (global)
+  int vprior_bytes;           // LDS bytes of that copy (8 n rounded up to 16)
 };
 
 // `name` (nullable) receives the kernel's name as rocprofv3 reports it
 const void* select_kernel(int algo, bool layered, int dc, const char** name);
 // its two-level-prior twin decode_prior_kernel (same template arguments)
 const void* select_prior_kernel(int algo, bool layered, int dc, const char** name);
+// its per-variable-prior twin decode_vprior_kernel (same template arguments)
+const void* select_vprior_kernel(int algo, bool layered, int dc, const char** name);
 // flooding MS, uniform row degree: global tables (fblob), LDS = wave state only
 const void* select_ms_flood_kernel(int dc, int kc, const char** name);  // nullptr if no instantiation fits
 int ms_flood_max_waves(int kc);                      // waves per workgroup it was compiled for

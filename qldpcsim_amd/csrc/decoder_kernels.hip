@@ -646,12 +646,17 @@ __device__ __forceinline__ uint32_t cn_ms_uniform(const DecodeArgs& a, const uin
   }
 }
 
-// Two-level priors (decode_prior_kernel): bit j of `selw` (this wave's LDS
-// slice, relabeled variable order) picks variable j's prior, L (bit 0) or L1
-// (bit 1). Without PRI every variable's prior is the scalar a.L.
-template <bool PRI>
+// Where a variable's prior comes from (PRI). PRI_MASK, two-level priors
+// (decode_prior_kernel): bit j of `selw` (this wave's LDS slice, relabeled
+// variable order) picks variable j's prior, L (bit 0) or L1 (bit 1). PRI_ROW,
+// per-variable priors (decode_vprior_kernel): `selw` is the workgroup's LDS
+// copy of the code's prior row, float64 [n] in relabeled order, and variable
+// j's prior is one read of it. PRI_SCALAR: every variable's prior is a.L.
+enum { PRI_SCALAR = 0, PRI_MASK = 1, PRI_ROW = 2 };
+template <int PRI>
 __device__ __forceinline__ double prior_of(const DecodeArgs& a, const uint32_t* selw, int j) {
-  if constexpr (PRI) return ((selw[j >> 5] >> (j & 31)) & 1u) ? a.L1 : a.L;
+  if constexpr (PRI == PRI_ROW) return ((const double*)selw)[j];
+  if constexpr (PRI == PRI_MASK) return ((selw[j >> 5] >> (j & 31)) & 1u) ? a.L1 : a.L;
   return a.L;
 }
 // Mask bit of original column jo of half-shot hs (DecodeArgs::pmask)
@@ -666,7 +671,7 @@ __device__ __forceinline__ uint32_t pmask_bit(const DecodeArgs& a, long long hs,
 // computed from the hard decisions of the posteriors it reads (only
 // meaningful when !first).
 // ---------------------------------------------------------------------------
-template <int ALGO, int DC, bool PRI = false>
+template <int ALGO, int DC, int PRI = PRI_SCALAR>
 __device__ __forceinline__ uint32_t cn_update(const DecodeArgs& a, const LdsView& g, int c,
                                               uint32_t synb, bool first, const double* post,
                                               void* c2v_raw, int& fl, const uint32_t* selw = nullptr) {
@@ -682,7 +687,7 @@ __device__ __forceinline__ uint32_t cn_update(const DecodeArgs& a, const LdsView
         const uint32_t cb = lds_addr(c2v_raw);
 #pragma unroll
         for (int k = 0; k < DC; ++k) {
-          L.pj[k] = (double)(float)prior_of<true>(a, selw, tab_var<DC>(t[0][k]));
+          L.pj[k] = (double)(float)prior_of<PRI>(a, selw, tab_var<DC>(t[0][k]));
           L.cv[k] = 0.0f;
           ca[k] = cb + (t[0][k] >> 16);
         }
@@ -820,7 +825,7 @@ __device__ __forceinline__ float ms_colsum_sw(const float* c, int d, int dmax) {
 
 // dmax: wave-uniform upper bound of the degrees of the variables this pass
 // covers (per 64-variable chunk, from the host), so the loads are unrolled.
-template <int ALGO, bool PRI = false>
+template <int ALGO, int PRI = PRI_SCALAR>
 __device__ __forceinline__ double vn_post(const DecodeArgs& a, const LdsView& g, int j,
                                           const void* c2v_raw, int dmax, const uint32_t* selw = nullptr) {
   const double Lj = prior_of<PRI>(a, selw, j);
@@ -851,21 +856,29 @@ __device__ __forceinline__ double vn_post(const DecodeArgs& a, const LdsView& g,
   }
 }
 
-// decode_kernel and its two-level-prior twin decode_prior_kernel (PRI:
+// decode_kernel, its two-level-prior twin decode_prior_kernel (PRI_MASK:
 // DecodeArgs::pmask / L1; instantiated in
-// decode_prior_kernels.hip) share one body, decode_kernel_body.inc, included
+// decode_prior_kernels.hip) and its per-variable-prior twin
+// decode_vprior_kernel (PRI_ROW: DecodeArgs::vprior, DESIGN.md §3.12;
+// decode_vprior_kernels.hip) share one body, decode_kernel_body.inc, included
 // into each kernel: as a __device__ function taking the arguments, the same
 // text compiled to different code for decode_kernel (register allocation of
 // the by-value kernel arguments), and its code must stay what it was.
 template <int ALGO, bool LAYERED, int DC>
 __global__ void __launch_bounds__(QLDPC_MAX_THREADS) decode_kernel(DecodeArgs a) {
-  constexpr bool PRI = false;
+  constexpr int PRI = PRI_SCALAR;
 #include "decode_kernel_body.inc"
 }
 
 template <int ALGO, bool LAYERED, int DC>
 __global__ void __launch_bounds__(QLDPC_MAX_THREADS) decode_prior_kernel(DecodeArgs a) {
-  constexpr bool PRI = true;
+  constexpr int PRI = PRI_MASK;
+#include "decode_kernel_body.inc"
+}
+
+template <int ALGO, bool LAYERED, int DC>
+__global__ void __launch_bounds__(QLDPC_MAX_THREADS) decode_vprior_kernel(DecodeArgs a) {
+  constexpr int PRI = PRI_ROW;
 #include "decode_kernel_body.inc"
 }
 
@@ -2240,7 +2253,8 @@ __global__ void __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))
 // translation units of their own (bp_team_kernels.hip, built without SLP
 // vectorization; ms_flood_kernels.hip, built with the max-ILP machine
 // scheduler), and so are the two-level-prior kernels
-// (decode_prior_kernels.hip); every other kernel here. relay_kernels.hip
+// (decode_prior_kernels.hip) and the per-variable-prior kernels
+// (decode_vprior_kernels.hip); every other kernel here. relay_kernels.hip
 // takes the device functions alone and brings its own helpers.
 #if defined(QLDPC_TU_RELAY)
 #elif defined(QLDPC_TU_PRIOR)
@@ -2260,6 +2274,32 @@ const void* select_prior_kernel(int algo, bool layered, int dc, const char** nam
                            : (const void*)&decode_prior_kernel<ALG, false, 8>;                                \
     default: return layered ? (const void*)&decode_prior_kernel<ALG, true, 0>                                 \
                             : (const void*)&decode_prior_kernel<ALG, false, 0>;                               \
+  }
+  if (algo == ALGO_MS) {
+    QLDPC_PICK(ALGO_MS)
+  } else {
+    QLDPC_PICK(ALGO_BP)
+  }
+#undef QLDPC_PICK
+}
+
+#elif defined(QLDPC_TU_VPRIOR)
+
+const void* select_vprior_kernel(int algo, bool layered, int dc, const char** name) {
+  static const char* names[2][2][3] = {
+      {{"decode_vprior_kernel<0, false, 0>", "decode_vprior_kernel<0, false, 7>", "decode_vprior_kernel<0, false, 8>"},
+       {"decode_vprior_kernel<0, true, 0>", "decode_vprior_kernel<0, true, 7>", "decode_vprior_kernel<0, true, 8>"}},
+      {{"decode_vprior_kernel<1, false, 0>", "decode_vprior_kernel<1, false, 7>", "decode_vprior_kernel<1, false, 8>"},
+       {"decode_vprior_kernel<1, true, 0>", "decode_vprior_kernel<1, true, 7>", "decode_vprior_kernel<1, true, 8>"}}};
+  if (name) *name = names[algo == ALGO_MS ? 0 : 1][layered ? 1 : 0][dc == 7 ? 1 : (dc == 8 ? 2 : 0)];
+#define QLDPC_PICK(ALG)                                                                                          \
+  switch (dc) {                                                                                                  \
+    case 7: return layered ? (const void*)&decode_vprior_kernel<ALG, true, 7>                                    \
+                           : (const void*)&decode_vprior_kernel<ALG, false, 7>;                                  \
+    case 8: return layered ? (const void*)&decode_vprior_kernel<ALG, true, 8>                                    \
+                           : (const void*)&decode_vprior_kernel<ALG, false, 8>;                                  \
+    default: return layered ? (const void*)&decode_vprior_kernel<ALG, true, 0>                                   \
+                            : (const void*)&decode_vprior_kernel<ALG, false, 0>;                                 \
   }
   if (algo == ALGO_MS) {
     QLDPC_PICK(ALGO_MS)

@@ -123,7 +123,7 @@ def unpack_bits(words, k):
 
 def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, eps=1e-9,
                  want_post=False, osd_order=-1, layer_ptr=None, layer_rows=None, stream=None,
-                 out=None, ehat_bits=False, prior_mask=None, p_masked=None, relay=None):
+                 out=None, ehat_bits=False, prior_mask=None, p_masked=None, relay=None, prior=None):
     """Decode a batch of syndromes of one matrix on the GPU.
 
     syndromes: uint8 [B, m] NumPy array (host; staged, synchronous) or a
@@ -147,6 +147,12 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
     host path: a uint8 [B, n] array. Runs decode_prior_kernel, the generic LDS
     kernel's twin: NotImplementedError for a code it cannot hold or with
     option force_hbm. With p_masked == p the result is the scalar decode's.
+    `prior` (MS / BP): one prior probability per column of H, a float64
+    array-like of n values in [0, 1) (the `channel_probs` of other BP
+    packages), shared by every shot of the batch; `p` must then be None. Runs
+    decode_vprior_kernel on both paths, with the limits of
+    the prior_mask kernel; not combinable with prior_mask, relay= or NG / BF.
+    A uniform vector gives the scalar decode's result bit for bit.
     `algo="RELAY"` with `relay=RelayConfig(...)`: relay min-sum (DESIGN.md
     §3.11), flooding only. `max_iter` is ignored: the legs carry their own
     counts (relay.leg_iters). layers other than flooding, prior_mask and
@@ -154,6 +160,19 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
     caller can run OSDdec on the failures). The result's `info` (`found`,
     `best_leg`) says how many solutions each shot met and which leg's was kept.
     """
+    if prior is not None:
+        if p is not None:
+            raise ValueError("give either p (one scalar prior) or prior (one per column), not both")
+        if prior_mask is not None or p_masked is not None:
+            raise ValueError("prior (per-column) and prior_mask (two-level, per shot) cannot be combined")
+        if relay is not None or algo == "RELAY":
+            raise ValueError("relay min-sum takes no per-column prior")
+        if algo in _lib.HARD_ALGOS:
+            raise ValueError(f"{algo} is a hard-decision decoder: it takes no prior")
+        prior = np.ascontiguousarray(prior, dtype=np.float64)
+        if prior.shape != (np.asarray(H).shape[1],):
+            raise ValueError(f"prior must hold {np.asarray(H).shape[1]} probabilities (one per column of H), got "
+                             f"shape {prior.shape}")
     if algo == "RELAY":
         return _decode_batch_relay(H, syndromes, p, relay, layers, beta, eps, want_post, osd_order, layer_ptr,
                                    layer_rows, stream, out, ehat_bits, prior_mask, p_masked)
@@ -220,7 +239,11 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         e_fmt = _lib.FMT_BITS if ehat_bits else _lib.FMT_BYTES
         post_p = post.data_ptr() if post is not None else None
-        if prior_mask is not None:
+        if prior is not None:
+            _lib.check(_lib.lib.qldpc_decode_device_vprior(
+                code.handle, sched.handle, _lib.ALGO[algo], syn.data_ptr(), syn_fmt, B, code.prior(prior, eps).handle,
+                int(max_iter), float(beta), ehat.data_ptr(), e_fmt, iters.data_ptr(), post_p, flags.data_ptr(), st))
+        elif prior_mask is not None:
             _lib.check(_lib.lib.qldpc_decode_device_prior(
                 code.handle, sched.handle, _lib.ALGO[algo], syn.data_ptr(), syn_fmt, B, float(p), float(p_masked),
                 prior_mask.data_ptr(), mask_fmt, int(max_iter), float(beta), float(eps), ehat.data_ptr(), e_fmt,
@@ -254,7 +277,11 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
     flags = np.zeros(B, np.int32)
     need_post = want_post or osd_order >= 0
     post = np.zeros((B, n), np.float64) if need_post else None
-    if prior_mask is not None:
+    if prior is not None:
+        _lib.check(_lib.lib.qldpc_decode_host_vprior(
+            code.handle, sched.handle, _lib.ALGO[algo], _lib.ptr(syn), B, code.prior(prior, eps).handle,
+            int(max_iter), float(beta), _lib.ptr(ehat), _lib.ptr(iters), _lib.ptr(post), _lib.ptr(flags)))
+    elif prior_mask is not None:
         _lib.check(_lib.lib.qldpc_decode_host_prior(
             code.handle, sched.handle, _lib.ALGO[algo], _lib.ptr(syn), B, float(p), float(p_masked),
             _lib.ptr(prior_mask), int(max_iter), float(beta), float(eps), _lib.ptr(ehat), _lib.ptr(iters),
@@ -955,8 +982,11 @@ def _single(H, syndrome, p, max_iter, layers, algo, beta, eps):
         # the reference's iteration loop never binds e_hat (decoders.py:153/:182)
         raise UnboundLocalError("local variable 'e_hat' referenced before assignment")
     lp, lr = pack_layers(layers, m)
-    r = decode_batch(H, syndrome.reshape(1, m), p, max_iter, algo=algo, beta=beta, eps=eps,
-                     want_post=True, layer_ptr=lp, layer_rows=lr)
+    # p may be an array of n probabilities, one per column (the reference
+    # raises on max(array, eps) there: DESIGN.md §7)
+    vec = np.ndim(p) > 0
+    r = decode_batch(H, syndrome.reshape(1, m), None if vec else p, max_iter, algo=algo, beta=beta, eps=eps,
+                     want_post=True, layer_ptr=lp, layer_rows=lr, prior=p if vec else None)
     return r.ehat[0], int(r.iters[0]), r.post[0], bool(r.converged[0])
 
 

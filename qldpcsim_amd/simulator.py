@@ -88,6 +88,65 @@ def sample_channel(Hx, Hz, p, shots, rng):
     return sy_z.astype(np.uint8), sy_x.astype(np.uint8), errX, errZ
 
 
+def bias_weights(eta):
+    """Channel weights (X, Y, Z) of a Z-biased Pauli channel with bias eta =
+    pZ / (pX + pY), pX = pY: (1/(2(eta+1)), 1/(2(eta+1)), eta/(eta+1)); they sum
+    to 1 and eta = 0.5 is the depolarizing channel."""
+    eta = float(eta)
+    if not (np.isfinite(eta) and eta >= 0.0):
+        raise ValueError("bias must be a finite number >= 0")
+    return np.array([1 / (2 * (eta + 1)), 1 / (2 * (eta + 1)), eta / (eta + 1)], np.float64)
+
+
+def _weights_3n(channel_weights, n):
+    """simulate_p's `channel_weights` ([3] or [3, n], rows X, Y, Z) as a
+    validated float64 [3, n] array."""
+    w = np.asarray(channel_weights, dtype=np.float64)
+    if w.shape == (3,):
+        w = np.repeat(w[:, None], n, axis=1)
+    if w.shape != (3, n):
+        raise ValueError(f"channel_weights must have shape [3] or [3, {n}] (rows X, Y, Z), got {list(w.shape)}")
+    if not (np.isfinite(w).all() and (w >= 0).all()):
+        raise ValueError("channel_weights must be finite and non-negative")
+    return w
+
+
+def channel_probs(p, channel_weights, n):
+    """Per-qubit Pauli probabilities float64 [3, n] (rows X, Y, Z) of
+    simulate_p's `channel_weights` at strength p: p * w[:, j]. ValueError
+    unless every qubit's three sum to at most 1."""
+    pr = float(p) * _weights_3n(channel_weights, n)
+    if not ((pr[0] + pr[1]) + pr[2] <= 1.0).all():
+        raise ValueError(f"p * sum(channel_weights) must be <= 1 on every qubit (p = {p})")
+    return pr
+
+
+def sample_channel_vec(Hx, Hz, probs, shots, rng):
+    """sample_channel for per-qubit Pauli probabilities `probs` (float64 [3, n],
+    rows X, Y, Z): one 32-bit draw per qubit against the device sampler's
+    thresholds (qldpc_channel_table): X if u < T1_j, Y if T1_j <= u < T2_j, Z
+    if T2_j <= u < T3_j. Same outputs as sample_channel."""
+    n = Hx.shape[1]
+    T = _lib.channel_table(probs[0], probs[1], probs[2])
+    u = rng.integers(0, 1 << 32, (shots, n), dtype=np.uint64)
+    errX = (u < T[1]).astype(np.uint8)                           # X | Y
+    errZ = ((u >= T[0]) & (u < T[2])).astype(np.uint8)           # Y | Z
+    sy_z = (errX.astype(np.float32) @ Hz.T.astype(np.float32)).astype(np.int64) % 2
+    sy_x = (errZ.astype(np.float32) @ Hx.T.astype(np.float32)).astype(np.int64) % 2
+    return sy_z.astype(np.uint8), sy_x.astype(np.uint8), errX, errZ
+
+
+def _half_prior(q, hard):
+    """decode_batch's (p, extra keywords) for a half whose qubits have the
+    marginal error probabilities q [n]: the scalar entry point where they are
+    all equal (the specialised kernels), else prior=q; NG / BF take no prior."""
+    if hard:
+        return 0.0, {}
+    if q.size == 0 or (q == q[0]).all():
+        return (float(q[0]) if q.size else 0.0), {}
+    return None, {"prior": q}
+
+
 def count_outcomes(Hx, Hz, sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ):
     """The reference's per-shot outcome counting (simulator.py:291-303), vectorised.
 
@@ -204,6 +263,13 @@ class DeviceChannel:
         self._Hx, self._Hz, self._lg = Hx, Hz, None
         self.seed = int(seed) & ((1 << 64) - 1)
         self.shot = int(shot0)
+        self._vec = None
+
+    def set_probs(self, probs):
+        """Per-qubit Pauli probabilities float64 [3, n] (rows X, Y, Z): sample()
+        then draws from them (qldpc_channel_sample_vec) and ignores its p."""
+        with self.torch.cuda.device(self.dev):
+            self._vec = _lib.Channel(self.cx, self.cz, probs[0], probs[1], probs[2])
 
     def _stream(self):
         return self.torch.cuda.current_stream(self.dev).cuda_stream
@@ -220,10 +286,15 @@ class DeviceChannel:
         else:
             sy_z = torch.empty((B, self.mz), dtype=torch.uint8, device=self.dev)
             sy_x = torch.empty((B, self.mx), dtype=torch.uint8, device=self.dev)
-        _lib.check(_lib.lib.qldpc_channel_sample_ex(
-            self.cx.handle, self.cz.handle, float(p), self.seed, self.shot, int(B), errX.data_ptr(),
-            errZ.data_ptr(), sy_z.data_ptr(), sy_x.data_ptr(), _lib.FMT_BITS if bits else _lib.FMT_BYTES,
-            self._stream()))
+        if self._vec is not None:
+            _lib.check(_lib.lib.qldpc_channel_sample_vec(
+                self._vec.handle, self.seed, self.shot, int(B), errX.data_ptr(), errZ.data_ptr(), sy_z.data_ptr(),
+                sy_x.data_ptr(), _lib.FMT_BITS if bits else _lib.FMT_BYTES, self._stream()))
+        else:
+            _lib.check(_lib.lib.qldpc_channel_sample_ex(
+                self.cx.handle, self.cz.handle, float(p), self.seed, self.shot, int(B), errX.data_ptr(),
+                errZ.data_ptr(), sy_z.data_ptr(), sy_x.data_ptr(), _lib.FMT_BITS if bits else _lib.FMT_BYTES,
+                self._stream()))
         self.shot += int(B)
         return sy_z, sy_x, errX, errZ
 
@@ -358,7 +429,7 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
                verbose: bool = True, samples=None, sampler: Optional[str] = None,
                logical: bool = False, correlated: Optional[str] = None, correlated_q1: float = 0.49,
                relay_legs: int = 11, relay_leg_iters: int = 60, relay_sols: int = 1, relay_gamma0: float = 0.125,
-               relay_gamma_range=(-0.24, 0.66), relay_seed: int = 0) -> dict:
+               relay_gamma_range=(-0.24, 0.66), relay_seed: int = 0, channel_weights=None) -> dict:
     """One depolarizing probability: sample, decode both halves, count.
 
     Returns the reference's dict (simulator.py:308-315). `samples`, if given,
@@ -398,7 +469,34 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
     solutions. The defaults come from a CPU trial on LP04_0 / LP118_0 and are
     not tuned per code. OSDorder >= 0, correlated= and a decSchedule other than
     "F" raise ValueError.
+
+    `channel_weights` (extension): a non-negative array of shape [3] or [3, n]
+    (rows X, Y, Z): qubit j suffers X, Y, Z with probabilities p * w[:, j]
+    (biased and inhomogeneous noise; p * sum(w) <= 1 on every qubit, else
+    ValueError). The decoders get the true marginals as priors: the X half
+    (decodes Hz) p (w_X + w_Y)_j, the Z half p (w_Z + w_Y)_j; a half whose
+    marginals are equal on every qubit (uniform bias) calls the scalar entry
+    point with that value and keeps the specialised kernels, any other runs
+    decode_batch(prior=...) (decode_vprior_kernel). NG / BF
+    take no prior: only the sampling changes. Not combinable with correlated=;
+    decType "RELAY" needs uniform marginals in both halves (ValueError).
     """
+    n_ = Hx.shape[1]
+    probs = None
+    hard_ = decType in _lib.HARD_ALGOS
+    pX_, pkwX = p / 3, {}                          # decode_batch's p and prior= of each half
+    pZ_, pkwZ = p / 3, {}
+    if channel_weights is not None:
+        if correlated is not None:
+            raise ValueError("channel_weights cannot be combined with correlated= (its second-half prior "
+                             "assumes depolarizing noise)")
+        probs = channel_probs(p, channel_weights, n_)
+        w_ = _weights_3n(channel_weights, n_)
+        pX_, pkwX = _half_prior(float(p) * (w_[0] + w_[1]), hard_)
+        pZ_, pkwZ = _half_prior(float(p) * (w_[2] + w_[1]), hard_)
+        if decType == "RELAY" and (pkwX or pkwZ):
+            raise ValueError("decType RELAY takes one scalar prior per half: channel_weights must give every "
+                             "qubit the same marginals")
     if decType == "RELAY":
         if OSDorder >= 0:
             raise ValueError("decType RELAY has no OSD step (OSDorder must be < 0)")
@@ -478,6 +576,8 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
         import torch
         dev = torch.device("cuda", torch.cuda.current_device())
         ch = DeviceChannel(Hx, Hz, dev, np.random.SeedSequence(seed).generate_state(1, np.uint64)[0])
+        if probs is not None:
+            ch.set_probs(probs)
     if use_dev and correlated is not None:
         # Correlated mode: the second half's decode waits for the first half's
         # final estimate, so each batch runs decode, (OSD,) decode, (OSD,)
@@ -545,10 +645,10 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
                 packed = osd < 0
                 sy_z, sy_x, errX, errZ = ch.sample(p, B, bits=packed)
                 want_post = osd >= 0
-                rX = decoders.decode_batch(Hz, sy_z, p / 3, decIterations, algo=decType, want_post=want_post,
-                                           layer_ptr=lpX, layer_rows=lrX, ehat_bits=packed, **rkwX)
-                rZ = decoders.decode_batch(Hx, sy_x, p / 3, decIterations, algo=decType, want_post=want_post,
-                                           layer_ptr=lpZ, layer_rows=lrZ, ehat_bits=packed, **rkwZ)
+                rX = decoders.decode_batch(Hz, sy_z, pX_, decIterations, algo=decType, want_post=want_post,
+                                           layer_ptr=lpX, layer_rows=lrX, ehat_bits=packed, **rkwX, **pkwX)
+                rZ = decoders.decode_batch(Hx, sy_x, pZ_, decIterations, algo=decType, want_post=want_post,
+                                           layer_ptr=lpZ, layer_rows=lrZ, ehat_bits=packed, **rkwZ, **pkwZ)
                 cur = [sy_z, sy_x, errX, errZ, rX, rZ, None]
                 done += B
             if cur is not None and osd >= 0 and stage_first:
@@ -588,13 +688,15 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
         if samples is not None:
             sl = slice(my_start + done, my_start + done + B)
             sy_z, sy_x, errX, errZ = (np.asarray(a)[sl].astype(np.uint8) for a in samples)
+        elif probs is not None:
+            sy_z, sy_x, errX, errZ = sample_channel_vec(Hx, Hz, probs, B, rng)
         else:
             sy_z, sy_x, errX, errZ = sample_channel(Hx, Hz, p, B, rng)
         if correlated is None:
-            rX = decoders.decode_batch(Hz, sy_z, p / 3, decIterations, algo=decType, osd_order=osd,
-                                       layer_ptr=lpX, layer_rows=lrX, **rkwX)
-            rZ = decoders.decode_batch(Hx, sy_x, p / 3, decIterations, algo=decType, osd_order=osd,
-                                       layer_ptr=lpZ, layer_rows=lrZ, **rkwZ)
+            rX = decoders.decode_batch(Hz, sy_z, pX_, decIterations, algo=decType, osd_order=osd,
+                                       layer_ptr=lpX, layer_rows=lrX, **rkwX, **pkwX)
+            rZ = decoders.decode_batch(Hx, sy_x, pZ_, decIterations, algo=decType, osd_order=osd,
+                                       layer_ptr=lpZ, layer_rows=lrZ, **rkwZ, **pkwZ)
         else:
             halves = [(Hz, sy_z, lpX, lrX), (Hx, sy_x, lpZ, lrZ)]
             if correlated == "ZX":
@@ -698,7 +800,8 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
              resultsFile: Optional[str] = None, on_point=None, logical: bool = False,
              correlated: Optional[str] = None, correlated_q1: float = 0.49,
              relay_legs: int = 11, relay_leg_iters: int = 60, relay_sols: int = 1, relay_gamma0: float = 0.125,
-             relay_gamma_range=(-0.24, 0.66), relay_seed: int = 0):
+             relay_gamma_range=(-0.24, 0.66), relay_seed: int = 0, bias: Optional[float] = None,
+             channel_weights=None):
     """p-sweep + results table (simulator.py:319-347). Returns None like the
     reference unless return_results=True.
 
@@ -713,6 +816,11 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
 
     relay_* (extension; decType "RELAY"): simulate_p's relay min-sum settings;
     all of them enter the results file's meta.
+
+    bias, channel_weights (extension; one of them at most): simulate_p's
+    channel_weights for every point, given as a bias eta (bias_weights) or as
+    the weights themselves ([3] or [3, n]). Both enter the results file's meta,
+    the weights by a SHA-256 digest of their float64 bytes.
 
     resultsFile (extension): a JSON file the sweep writes after every
     p-point; a rerun with the same arguments skips the points already there
@@ -742,6 +850,19 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
                      relay_gamma0=float(relay_gamma0), relay_gamma_range=[float(x) for x in relay_gamma_range],
                      relay_seed=int(relay_seed))
         meta.update({k: v for k, v in extra.items() if k.startswith("relay_")})
+    if bias is not None and channel_weights is not None:
+        raise ValueError("give either bias or channel_weights, not both")
+    if bias is not None:
+        extra["channel_weights"] = bias_weights(bias)
+        meta["bias"] = float(bias)
+    elif channel_weights is not None:
+        import hashlib
+        w = np.ascontiguousarray(channel_weights, dtype=np.float64)
+        extra["channel_weights"] = w
+        meta["channel_weights"] = {"shape": list(w.shape), "sha256": hashlib.sha256(w.tobytes()).hexdigest()}
+    if "channel_weights" in extra:
+        for pT in p:                          # every point is checked before the first one runs
+            channel_probs(pT, extra["channel_weights"], Hx.shape[1])
     done = _load_results(resultsFile, meta)
     results = []
     for pT in p:
@@ -841,7 +962,15 @@ def main(argv=None):
     parser.add_argument("--correlated-q1", type=float, default=0.49, dest="correlated_q1",
                         help="Prior of the second component on a qubit flagged by the first half (exactly 1/2 "
                              "in theory; its LLR 0 is degenerate for the decoders: default 0.49).")
+    parser.add_argument("--bias", type=float, default=None, metavar="ETA",
+                        help="Z-biased Pauli channel with pZ / (pX + pY) = ETA and pX = pY, at total error "
+                             "probability p (0.5: depolarizing); the decoders get the true marginals as priors.")
+    parser.add_argument("--channel-weights", default=None, dest="channel_weights", metavar="FILE.npy",
+                        help="Pauli weights, shape [3] or [3, n] (rows X, Y, Z): qubit j suffers X, Y, Z with "
+                             "probabilities p * w[:, j]; the decoders get each qubit's true marginal as its prior.")
     args = parser.parse_args(argv)
+    if args.bias is not None and args.channel_weights is not None:
+        parser.error("--bias and --channel-weights exclude each other")
     own_group = _init_dist_from_env()              # torchrun: shots shard over the ranks
     _, rank, _ = _dist()
     if rank == 0:
@@ -854,6 +983,8 @@ def main(argv=None):
                  OSDorder=args.OSDorder, rngSeed=args.rngSeed, batch_size=args.batch,
                  sampler=args.sampler, resultsFile=args.results, **({"logical": True} if args.logical else {}),
                  **({"correlated": args.correlated, "correlated_q1": args.correlated_q1} if args.correlated else {}),
+                 **({"bias": args.bias} if args.bias is not None else {}),
+                 **({"channel_weights": np.load(args.channel_weights)} if args.channel_weights else {}),
                  **({k: getattr(args, k) for k in ("relay_legs", "relay_leg_iters", "relay_sols", "relay_gamma0",
                                                    "relay_gamma_range", "relay_seed")}
                     if args.decType == "RELAY" else {}))
