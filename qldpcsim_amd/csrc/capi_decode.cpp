@@ -162,26 +162,17 @@ static int twin_limits(const qldpc_schedule* s, int algo, const char* what) {
   return QLDPC_OK;
 }
 
-static const char* const kTwoLevel = "two-level priors";
-static const char* const kPerQubit = "per-variable priors";
+// the feature's name in messages (kind: PLAN_PRIOR or PLAN_VPRIOR)
+static const char* twin_name(PlanKind kind) { return kind == PLAN_PRIOR ? "two-level priors" : "per-variable priors"; }
 
-int capi::choose_prior_kernel(const qldpc_schedule* s, int algo, KernelChoice* k) {
+int capi::choose_twin_kernel(const qldpc_schedule* s, int algo, PlanKind kind, KernelChoice* k) {
   const qldpc_code* c = s->code;
-  if (int rc = twin_limits(s, algo, kTwoLevel)) return rc;
+  if (int rc = twin_limits(s, algo, twin_name(kind))) return rc;
   *k = KernelChoice{};
   k->max_waves = QLDPC_MAX_THREADS / 64;
-  k->prior = true;
-  k->kernel = qldpc::select_prior_kernel(algo, s->layered, fast_table_ok(c) ? c->uniform_deg : 0, &k->name);
-  return QLDPC_OK;
-}
-
-int capi::choose_vprior_kernel(const qldpc_schedule* s, int algo, KernelChoice* k) {
-  const qldpc_code* c = s->code;
-  if (int rc = twin_limits(s, algo, kPerQubit)) return rc;
-  *k = KernelChoice{};
-  k->max_waves = QLDPC_MAX_THREADS / 64;
-  k->vprior = true;
-  k->kernel = qldpc::select_vprior_kernel(algo, s->layered, fast_table_ok(c) ? c->uniform_deg : 0, &k->name);
+  k->kind = kind;
+  const auto select = kind == PLAN_PRIOR ? qldpc::select_prior_kernel : qldpc::select_vprior_kernel;
+  k->kernel = select(algo, s->layered, fast_table_ok(c) ? c->uniform_deg : 0, &k->name);
   return QLDPC_OK;
 }
 
@@ -214,8 +205,9 @@ int capi::plan_static(const qldpc_schedule* s, int algo, const KernelChoice& k, 
   a->off_vn_chk = t.off.vn_chk, a->off_lay_ptr = t.off.lay_ptr, a->off_lay_rows = t.off.lay_rows;
   a->off_adj_ptr = t.off.adj_ptr, a->off_adj_vars = t.off.adj_vars, a->off_chunk_dmax = t.off.chunk_dmax;
   const bool msl = k.family == FAM_MS_LAYERED;
-  wave_layout(c, s->layered, algo, msl, msl && k.lanes == 0 ? (int)s->h_lay_rows.size() : 0, k.prior, a);
-  if (k.vprior) {
+  wave_layout(c, s->layered, algo, msl, msl && k.lanes == 0 ? (int)s->h_lay_rows.size() : 0, k.kind == PLAN_PRIOR,
+              a);
+  if (k.kind == PLAN_VPRIOR) {
     // decode_vprior_kernel: the prior row f64[n] between the image and the slices
     a->vprior_bytes = align16(8 * c->n);
     image_lds += a->vprior_bytes;
@@ -250,8 +242,6 @@ void capi::plan_static_hbm(const qldpc_schedule* s, qldpc::HbmArgs* a) {
 // ---------------------------------------------------------------------------
 // launch plan, device half: occupancy, and the cache under the schedule's lock
 // ---------------------------------------------------------------------------
-enum PlanKind { PLAN_SCALAR = 0, PLAN_PRIOR = 1, PLAN_VPRIOR = 2 };   // which of a schedule's plan arrays
-
 static int build_plan(qldpc_schedule* s, int algo, PlanKind kind, LaunchPlan* p) {
   const bool prior = kind != PLAN_SCALAR;             // a twin of the generic LDS kernel, or nothing
   const qldpc_code* c = s->code;
@@ -266,7 +256,7 @@ static int build_plan(qldpc_schedule* s, int algo, PlanKind kind, LaunchPlan* p)
            (algo == QLDPC_ALGO_BP && c->max_col_deg > 128);
   KernelChoice pk;
   if (prior) {
-    if (int rc = kind == PLAN_PRIOR ? choose_prior_kernel(s, algo, &pk) : choose_vprior_kernel(s, algo, &pk)) return rc;
+    if (int rc = choose_twin_kernel(s, algo, kind, &pk)) return rc;
     p->hbm = false;
   }
   if (!p->hbm) {
@@ -312,8 +302,7 @@ static int build_plan(qldpc_schedule* s, int algo, PlanKind kind, LaunchPlan* p)
     p->hbm = best_waves == 0;
     if (prior && p->hbm)
       return fail(QLDPC_EUNSUP, "%s: the tables and one wave's state (%d + %d B) do not fit the %d B "
-                  "of LDS; there is no HBM-resident variant", kind == PLAN_PRIOR ? kTwoLevel : kPerQubit, image_lds,
-                  p->args.wave_bytes, max_lds);
+                  "of LDS; there is no HBM-resident variant", twin_name(kind), image_lds, p->args.wave_bytes, max_lds);
   }
   if (p->hbm) {
     p->kernel = qldpc::select_hbm_kernel(algo, c->max_row_deg, &p->name);
@@ -336,9 +325,7 @@ static int resolve_plan(const qldpc_code* code, qldpc_schedule* s, int algo, Lau
     return fail(QLDPC_EHIP, "no HIP device was visible when the code/schedule was created");
   std::lock_guard<std::mutex> lk(s->mu);
   const uint32_t gen = g_opt.gen.load();
-  LaunchPlan& slot = kind == PLAN_VPRIOR  ? s->vprior_plan[algo]
-                     : kind == PLAN_PRIOR ? s->prior_plan[algo]
-                                          : s->plan[algo];
+  LaunchPlan& slot = s->plan[kind][algo];
   if (!slot.ok || slot.gen != gen) {
     LaunchPlan p{};                                   // built aside, published whole
     const int rc = build_plan(s, algo, kind, &p);
@@ -502,7 +489,7 @@ extern "C" int qldpc_decode_device(const qldpc_code* code, const qldpc_schedule*
                                 QLDPC_FMT_BYTES, d_iters, d_post, d_flags, stream);
 }
 
-// The BP check node's saturated value (decoder_kernels.hip, cn_bp_word): at
+// The BP check node's saturated value (bp_team.h, cn_bp_word): at
 // |th2| = 1 the reference clips th2 to +-(1 - eps) (decoders.py:256-258), so
 // c2v = +-2 atanh(1 - eps) — computed here by the restated SVML atanh the
 // kernels and the oracle share (include/qldpc_libm.h), the same expression
@@ -524,43 +511,38 @@ struct PriorCall {
   int mask_format;
 };
 
-// everything qldpc_decode_device_prior checks on top of the scalar entry,
-// before any HIP call
-static int validate_prior(const qldpc_code* code, const qldpc_schedule* sched, int algo, int64_t batch, double p0,
-                          const PriorCall& pr) {
-  if (pr.mask_format != QLDPC_FMT_BYTES && pr.mask_format != QLDPC_FMT_BITS)
-    return fail(QLDPC_EINVAL, "unknown mask format");
-  if (!(p0 >= 0.0 && p0 <= 1.0) || !(pr.p1 >= 0.0 && pr.p1 <= 1.0))
-    return fail(QLDPC_EINVAL, "two-level priors: p0 and p1 must be probabilities (0 <= p <= 1)");
-  if (batch > 0 && !pr.mask) return fail(QLDPC_EINVAL, "null mask");
-  if (code && sched && sched->code == code && (algo == QLDPC_ALGO_MS || algo == QLDPC_ALGO_BP)) {
-    KernelChoice k;
-    if (int rc = choose_prior_kernel(sched, algo, &k)) return rc;
-  }
-  return QLDPC_OK;
+// A decode call carries at most one of pr, the two-level prior of
+// qldpc_decode_device_prior, and vp, the per-variable priors of
+// qldpc_decode_device_vprior (p is then unread)
+static PlanKind kind_of(const PriorCall* pr, const qldpc_prior* vp) {
+  return vp ? PLAN_VPRIOR : pr ? PLAN_PRIOR : PLAN_SCALAR;
 }
 
-// everything qldpc_decode_device_vprior checks on top of the scalar entry,
-// before any HIP call
-static int validate_vprior(const qldpc_code* code, const qldpc_schedule* sched, int algo, const qldpc_prior* vp) {
-  if (!vp) return fail(QLDPC_EINVAL, "prior handle is null");
-  if (code && (vp->code != code || vp->n != code->n || vp->m != code->m || vp->E != code->E))
+// what a call with `pr` or `vp` checks on top of the scalar entry, before any
+// HIP call: its own arguments, then what the twin kernel refuses
+static int validate_twin(const qldpc_code* code, const qldpc_schedule* sched, int algo, int64_t batch, double p0,
+                         const PriorCall* pr, const qldpc_prior* vp) {
+  if (pr) {
+    if (pr->mask_format != QLDPC_FMT_BYTES && pr->mask_format != QLDPC_FMT_BITS)
+      return fail(QLDPC_EINVAL, "unknown mask format");
+    if (!(p0 >= 0.0 && p0 <= 1.0) || !(pr->p1 >= 0.0 && pr->p1 <= 1.0))
+      return fail(QLDPC_EINVAL, "two-level priors: p0 and p1 must be probabilities (0 <= p <= 1)");
+    if (batch > 0 && !pr->mask) return fail(QLDPC_EINVAL, "null mask");
+  }
+  if (vp && code && (vp->code != code || vp->n != code->n || vp->m != code->m || vp->E != code->E))
     return fail(QLDPC_EINVAL, "prior handle was built for a different code");
-  if (code && sched && sched->code == code && (algo == QLDPC_ALGO_MS || algo == QLDPC_ALGO_BP)) {
+  if ((pr || vp) && code && sched && sched->code == code && (algo == QLDPC_ALGO_MS || algo == QLDPC_ALGO_BP)) {
     KernelChoice k;
-    if (int rc = choose_vprior_kernel(sched, algo, &k)) return rc;
+    if (int rc = choose_twin_kernel(sched, algo, kind_of(pr, vp), &k)) return rc;
   }
   return QLDPC_OK;
 }
 
-// pr: the two-level prior of qldpc_decode_device_prior; vp: the per-variable
-// priors of qldpc_decode_device_vprior (p is then unread); at most one of them
-static int decode_device(const qldpc_code* code, const qldpc_schedule* sched_c, int algo,
-                         const void* d_syn, int syn_format, int64_t batch, double p, int max_iter,
-                         double beta, double eps, void* d_ehat, int ehat_format, int32_t* d_iters,
-                         double* d_post, int32_t* d_flags, void* stream, const PriorCall* pr,
-                         const qldpc_prior* vp = nullptr) {
-  auto* sched = const_cast<qldpc_schedule*>(sched_c);
+// The device-free checks of a decode call, in the order decode_device reports
+// them (decode_host makes them before its staging copies where it can)
+static int validate_call(const qldpc_code* code, const qldpc_schedule* sched, int algo, int syn_format,
+                         int ehat_format, int64_t batch, double p, int max_iter, const PriorCall* pr,
+                         const qldpc_prior* vp) {
   if ((syn_format != QLDPC_FMT_BYTES && syn_format != QLDPC_FMT_BITS) ||
       (ehat_format != QLDPC_FMT_BYTES && ehat_format != QLDPC_FMT_BITS))
     return fail(QLDPC_EINVAL, "unknown syndrome / estimate format");
@@ -569,10 +551,16 @@ static int decode_device(const qldpc_code* code, const qldpc_schedule* sched_c, 
   if (algo != QLDPC_ALGO_MS && algo != QLDPC_ALGO_BP) return fail(QLDPC_EINVAL, "Unrecognized decoder type.");
   if (batch < 0) return fail(QLDPC_EINVAL, "negative batch");
   if (max_iter < 1) return fail(QLDPC_EINVAL, "max_iter must be >= 1 (the reference leaves e_hat unbound)");
-  if (pr)
-    if (int rc = validate_prior(code, sched, algo, batch, p, *pr)) return rc;
-  if (vp)
-    if (int rc = validate_vprior(code, sched, algo, vp)) return rc;
+  return validate_twin(code, sched, algo, batch, p, pr, vp);
+}
+
+static int decode_device(const qldpc_code* code, const qldpc_schedule* sched_c, int algo,
+                         const void* d_syn, int syn_format, int64_t batch, double p, int max_iter,
+                         double beta, double eps, void* d_ehat, int ehat_format, int32_t* d_iters,
+                         double* d_post, int32_t* d_flags, void* stream, const PriorCall* pr,
+                         const qldpc_prior* vp = nullptr) {
+  auto* sched = const_cast<qldpc_schedule*>(sched_c);
+  if (int rc = validate_call(code, sched, algo, syn_format, ehat_format, batch, p, max_iter, pr, vp)) return rc;
   if (batch == 0) return QLDPC_OK;
   if (!d_syn || !d_ehat || !d_iters) return fail(QLDPC_EINVAL, "null device buffer");
   if (code->device < 0 || !sched->generic.dev)
@@ -581,7 +569,7 @@ static int decode_device(const qldpc_code* code, const qldpc_schedule* sched_c, 
   HIP_TRY(hipGetDevice(&dev));
   if (dev != code->device) return fail(QLDPC_EINVAL, "code lives on device %d, current device is %d", code->device, dev);
   LaunchPlan plan;
-  if (int rc = resolve_plan(code, sched, algo, &plan, vp ? PLAN_VPRIOR : pr ? PLAN_PRIOR : PLAN_SCALAR)) return rc;
+  if (int rc = resolve_plan(code, sched, algo, &plan, kind_of(pr, vp))) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (plan.hbm)
     return decode_hbm(code, sched, algo, plan,
@@ -652,15 +640,20 @@ extern "C" int qldpc_decode_device_prior(const qldpc_code* code, const qldpc_sch
                        d_iters, d_post, d_flags, stream, &pr);
 }
 
-extern "C" int qldpc_decode_prior_kernel_name(const qldpc_code* code, const qldpc_schedule* sched, int algo,
-                                              char* buf, int len) {
+static int twin_kernel_name(const qldpc_code* code, const qldpc_schedule* sched, int algo, PlanKind kind, char* buf,
+                            int len) {
   if (!code || !sched || !buf || len <= 0) return fail(QLDPC_EINVAL, "null argument");
   if (sched->code != code) return fail(QLDPC_EINVAL, "schedule was built for a different code");
   if (algo != QLDPC_ALGO_MS && algo != QLDPC_ALGO_BP) return fail(QLDPC_EINVAL, "Unrecognized decoder type.");
   KernelChoice k;                                     // (no device needed: the name depends on the code alone)
-  if (int rc = choose_prior_kernel(sched, algo, &k)) return rc;
+  if (int rc = choose_twin_kernel(sched, algo, kind, &k)) return rc;
   snprintf(buf, (size_t)len, "%s", k.name);
   return QLDPC_OK;
+}
+
+extern "C" int qldpc_decode_prior_kernel_name(const qldpc_code* code, const qldpc_schedule* sched, int algo,
+                                              char* buf, int len) {
+  return twin_kernel_name(code, sched, algo, PLAN_PRIOR, buf, len);
 }
 
 extern "C" int qldpc_decode_kernel_name(const qldpc_code* code, const qldpc_schedule* sched_c, int algo,
@@ -723,17 +716,16 @@ static int decode_host(const qldpc_code* code_c, const qldpc_schedule* sched, in
   auto* code = const_cast<qldpc_code*>(code_c);
   if (!code) return fail(QLDPC_EINVAL, "code is null");
   if (batch < 0) return fail(QLDPC_EINVAL, "negative batch");
-  if (pr) {
-    if (!sched) return fail(QLDPC_EINVAL, "code/schedule is null");
-    if (int rc = validate_prior(code, sched, algo, batch, p, *pr)) return rc;
-  }
+  // Before the staging copies: with `vp` every check decode_device makes
+  // before its first HIP call; with `pr` the prior's own part alone, so its
+  // errors come ahead of the schedule / algo / max_iter ones, which this entry
+  // and the scalar one report from decode_device, behind the copies.
   if (vp) {
-    // (the checks decode_device makes before any HIP call, made before the staging copies)
+    if (int rc = validate_call(code, sched, algo, QLDPC_FMT_BYTES, QLDPC_FMT_BYTES, batch, p, max_iter, nullptr, vp))
+      return rc;
+  } else if (pr) {
     if (!sched) return fail(QLDPC_EINVAL, "code/schedule is null");
-    if (sched->code != code) return fail(QLDPC_EINVAL, "schedule was built for a different code");
-    if (algo != QLDPC_ALGO_MS && algo != QLDPC_ALGO_BP) return fail(QLDPC_EINVAL, "Unrecognized decoder type.");
-    if (max_iter < 1) return fail(QLDPC_EINVAL, "max_iter must be >= 1 (the reference leaves e_hat unbound)");
-    if (int rc = validate_vprior(code, sched, algo, vp)) return rc;
+    if (int rc = validate_twin(code, sched, algo, batch, p, pr, nullptr)) return rc;
   }
   if (batch == 0) return QLDPC_OK;
   if (!h_syn || !h_ehat || !h_iters) return fail(QLDPC_EINVAL, "null host buffer");
@@ -854,11 +846,5 @@ extern "C" int qldpc_decode_host_vprior(const qldpc_code* code, const qldpc_sche
 
 extern "C" int qldpc_decode_vprior_kernel_name(const qldpc_code* code, const qldpc_schedule* sched, int algo,
                                                char* buf, int len) {
-  if (!code || !sched || !buf || len <= 0) return fail(QLDPC_EINVAL, "null argument");
-  if (sched->code != code) return fail(QLDPC_EINVAL, "schedule was built for a different code");
-  if (algo != QLDPC_ALGO_MS && algo != QLDPC_ALGO_BP) return fail(QLDPC_EINVAL, "Unrecognized decoder type.");
-  KernelChoice k;                                     // (no device needed: the name depends on the code alone)
-  if (int rc = choose_vprior_kernel(sched, algo, &k)) return rc;
-  snprintf(buf, (size_t)len, "%s", k.name);
-  return QLDPC_OK;
+  return twin_kernel_name(code, sched, algo, PLAN_VPRIOR, buf, len);
 }

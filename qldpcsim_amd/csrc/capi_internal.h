@@ -121,6 +121,9 @@ struct TableImage {
 // decode launch needs that does not depend on the call (capi_decode.cpp)
 // ---------------------------------------------------------------------------
 enum KernelFamily { FAM_GENERIC, FAM_MS_FLOOD, FAM_MS_FLOOD_QC, FAM_MS_LAYERED, FAM_BP_TEAM, FAM_BP_TEAM_LG };
+// Which priors a launch takes: one scalar, or one of the generic LDS kernel's
+// twins (decode_prior_kernel, decode_vprior_kernel). Indexes qldpc_schedule::plan.
+enum PlanKind { PLAN_SCALAR = 0, PLAN_PRIOR = 1, PLAN_VPRIOR = 2 };
 
 struct KernelChoice {
   const void* kernel = nullptr;
@@ -130,8 +133,9 @@ struct KernelChoice {
   int lanes = 0;            // ms_layered_kernel: lanes per check, 0 = chosen per layer
   int max_waves = 0;        // most waves per workgroup the kernel was compiled for
   int qc_table = -1;        // FAM_MS_FLOOD_QC: the generated table H expands from (qc_tables.h)
-  bool prior = false;       // decode_prior_kernel: the wave slice also holds the selector bits
-  bool vprior = false;      // decode_vprior_kernel: the prior row lies behind the graph image
+  // PLAN_PRIOR (decode_prior_kernel): the wave slice also holds the selector
+  // bits; PLAN_VPRIOR (decode_vprior_kernel): the prior row lies behind the graph image
+  PlanKind kind = PLAN_SCALAR;
 };
 
 struct LaunchPlan {
@@ -245,9 +249,7 @@ struct qldpc_schedule {
   capi::TableImage layered_ms;   // ms_layered_kernel, uniform degree: layer-ordered tables
   capi::TableImage layered_bp;   // bp_team_lg_kernel: layer pointers in LDS, every table global
   capi::TableImage flood_ms;     // ms_flood_kernel, uniform degree: global tables, no LDS image
-  capi::LaunchPlan plan[2];   // per algo, under mu
-  capi::LaunchPlan prior_plan[2];   // the same for decode_prior_kernel (qldpc_decode_device_prior)
-  capi::LaunchPlan vprior_plan[2];  // and for decode_vprior_kernel (qldpc_decode_device_vprior)
+  capi::LaunchPlan plan[3][2];   // [PlanKind][algo], under mu
   std::mutex mu;
   // HBM-resident kernel (hbm_kernels.hip): 32-bit layer tables and a grow-only
   // slot-major workspace; hbm_ev orders launches that share the workspace
@@ -289,12 +291,11 @@ struct Gf2Basis {
 // capi_decode.cpp. choose_kernel and plan_static call no HIP function: the
 // static kernel arguments can be checked on a machine without a device.
 KernelChoice choose_kernel(const qldpc_schedule* s, int algo);
-// decode_prior_kernel for (schedule, algo): QLDPC_EUNSUP where the generic LDS
-// kernel cannot run the code (16-bit tables, MS row degree > 32, BP column
-// degree > 128) or option force_hbm is set; calls no HIP function
-int choose_prior_kernel(const qldpc_schedule* s, int algo, KernelChoice* k);
-// decode_vprior_kernel for (schedule, algo), with the same limits
-int choose_vprior_kernel(const qldpc_schedule* s, int algo, KernelChoice* k);
+// decode_prior_kernel (PLAN_PRIOR) or decode_vprior_kernel (PLAN_VPRIOR) for
+// (schedule, algo): QLDPC_EUNSUP where the generic LDS kernel cannot run the
+// code (16-bit tables, MS row degree > 32, BP column degree > 128) or option
+// force_hbm is set; calls no HIP function
+int choose_twin_kernel(const qldpc_schedule* s, int algo, PlanKind kind, KernelChoice* k);
 // The generated protograph table (qc_tables.h) whose expansion is exactly the
 // code's H, or -1: compared entry by entry, not by shape or hash
 int qc_table_of(const qldpc_code* c);

@@ -36,15 +36,10 @@
 // bytes, the counter reads them back with the 2n estimate bytes.
 
 #include "channel_kernels.h"
+#include "wave_common.h"
 
 namespace qldpc {
 namespace {
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Philox4x32-10 (Salmon et al., SC'11), counter (c0..c3), key (k0, k1).
 __device__ __forceinline__ uint4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,

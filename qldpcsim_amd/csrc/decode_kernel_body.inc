@@ -1,5 +1,5 @@
 // decode_kernel_body.inc — the body of decode_kernel / decode_prior_kernel /
-// decode_vprior_kernel (decoder_kernels.hip), included inside each kernel with
+// decode_vprior_kernel (decode_generic.h), included inside each kernel with
 // `a` (DecodeArgs), the template parameters ALGO, LAYERED, DC and a constexpr
 // int PRI (PRI_SCALAR / PRI_MASK / PRI_ROW) in scope.
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -50,7 +50,7 @@
   const int m = a.m, n = a.n;
   const int nwords = (m + 31) >> 5;
 
-  for (HalfShotQueue Q(a, waves, wid); Q.hs < a.batch; Q.advance()) {
+  for (HalfShotQueue Q(a.batch, a.queue, waves, wid); Q.hs < a.batch; Q.advance()) {
     const long long hs = Q.hs;
     Q.prefetch(threadIdx.x & 63);
     int fl = 0;

@@ -1,6 +1,11 @@
-// decode_prior_kernels.hip — decode_prior_kernel (decoder_kernels.hip: the
+// decode_prior_kernels.hip — decode_prior_kernel (decode_generic.h: the
 // generic LDS kernel's body with a per-half-shot mask over the variables and
 // two priors) instantiated in a translation unit of its own,
 // so the objects of every other kernel are built exactly as without it.
-#define QLDPC_TU_PRIOR 1
-#include "decoder_kernels.hip"
+#include "decode_generic.h"
+
+namespace qldpc {
+
+QLDPC_GENERIC_SELECTOR(select_prior_kernel, decode_prior_kernel)
+
+}  // namespace qldpc

@@ -8,70 +8,17 @@
 // every wave alike: cache hits); LDS holds only each wave's own state, so the
 // registers bound the occupancy, not LDS.
 #include "hard_kernels.h"
+#include "wave_common.h"
 
 namespace qldpc {
 namespace {
 
 typedef uint32_t __attribute__((may_alias)) u32a;   // ng_kernel reads its u16 scores in pairs
 
-// Lanes of one wave exchange data through LDS between phases. DS instructions
-// of a wave complete in order; the fences only stop the compiler from moving
-// LDS accesses across the phase boundary.
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// read-only tables through the constant address space: a wave-uniform index
-// may then become a scalar load
-template <typename T>
-__device__ __forceinline__ T ld_const(const T* p, int i) {
-  return ((const __attribute__((address_space(4))) T*)p)[i];
-}
-
-__device__ __forceinline__ long long uniform64(long long x) {
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)(uint64_t)x);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
-  return (long long)(((uint64_t)hi << 32) | lo);
-}
-
-// The persistent half-shot loop of the MS / BP kernels (decoder_kernels.hip,
-// HalfShotQueue): one static half-shot per wave, then guided chunks of a
-// global ticket counter (about remaining / (4 waves), 1 .. 64), claimed while
-// the last half-shot of the current chunk runs. NG's step count varies from 0
-// to 2n between half-shots: this is what balances it.
-struct HalfShotQueue {
-  long long hs, end, stride, batch;
-  uint32_t* q;
-  uint32_t tk, tlen, seen;
-  __device__ __forceinline__ HalfShotQueue(long long batch_, uint32_t* q_, int waves, int wid)
-      : hs(uniform64((long long)blockIdx.x * waves + wid)), end(0), stride((long long)gridDim.x * waves),
-        batch(batch_), q(q_), tk(0), tlen(1), seen(0) {
-    end = hs + 1;
-  }
-  __device__ __forceinline__ void prefetch(int lane) {
-    if (q && hs + 1 == end) {
-      const long long rem = batch - stride - (long long)seen;
-      long long len = rem / (4 * stride);
-      len = len < 1 ? 1 : (len > 64 ? 64 : len);
-      tlen = (uint32_t)len;
-      if (lane == 0) tk = atomicAdd(q, tlen);
-    }
-  }
-  __device__ __forceinline__ void advance() {
-    if (!q) {
-      hs = uniform64(hs + stride);
-      return;
-    }
-    hs = uniform64(hs + 1);
-    if (hs < end) return;
-    const uint32_t t = __builtin_amdgcn_readfirstlane(tk);
-    seen = t + tlen;
-    hs = uniform64(stride + (long long)t);
-    end = uniform64(hs + tlen);
-  }
-};
+// wave_sync, ld_const and the persistent half-shot loop (HalfShotQueue: one
+// static half-shot per wave, then guided chunks of a global ticket counter)
+// are wave_common.h's, shared with the MS / BP kernels. NG's step count varies
+// from 0 to 2n between half-shots: the queue is what balances it.
 
 // 64 predicate bits of the chunk starting at index i0 (a multiple of 64) into a word array
 __device__ __forceinline__ void store_chunk(uint32_t* words, int i0, uint64_t bits, int lane) {

@@ -1,5 +1,5 @@
 // ms_flood_qc.h — the register-resident body of ms_flood_kernel for lift-16
-// quasi-cyclic codes. Included by decoder_kernels.hip inside
+// quasi-cyclic codes. Included by ms_flood.h inside
 // namespace qldpc, after the check-node helpers it shares with the LDS body.
 //
 // A code whose 16 x 16 blocks are zero or weight-1 circulants (qc_tables.h)

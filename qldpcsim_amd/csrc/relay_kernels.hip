@@ -4,7 +4,7 @@
 //
 // One wavefront decodes one half-shot start to finish, graph image and state
 // in LDS, as decode_kernel does; the check node and the column sum are
-// decoder_kernels.hip's device functions (cn_ms_uniform / cn_update,
+// decode_generic.h's device functions (cn_ms_uniform / cn_update,
 // ms_colsum). A translation unit of its own, so the objects of every other
 // kernel are built exactly as without it.
 //
@@ -15,8 +15,7 @@
 //   stop test: H (M < 0) == s
 // The slice holds two float64 rows: M, and X for the next check pass, which
 // the variable pass forms from the Lam of the M it has just written.
-#define QLDPC_TU_RELAY 1
-#include "decoder_kernels.hip"
+#include "decode_generic.h"
 #include "relay_kernels.h"
 
 namespace qldpc {
@@ -64,7 +63,7 @@ __global__ void __launch_bounds__(QLDPC_MAX_THREADS) relay_ms_kernel(RelayArgs r
   const int ewords = 2 * a.wn;
   const double L = a.L;
 
-  for (HalfShotQueue Q(a, waves, wid); Q.hs < a.batch; Q.advance()) {
+  for (HalfShotQueue Q(a.batch, a.queue, waves, wid); Q.hs < a.batch; Q.advance()) {
     const long long hs = Q.hs;
     Q.prefetch(lane);
     int fl = 0;

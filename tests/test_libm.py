@@ -98,7 +98,7 @@ def test_special_values(probe):
 
 
 def test_tanh_saturates_at_bp_threshold(probe):
-    """decoder_kernels.hip's saturated check-node path (kBpTanhSat = 19.5)
+    """bp_team.h's saturated check-node path (kBpTanhSat = 19.5)
     takes tanh(x) = +-1.0 exactly for every |x| >= 19.5: dense and random
     arguments over [19.5, 24) (the polynomial interval) and beyond, against
     the restatement and NumPy; just below, tanh is not yet 1 everywhere."""

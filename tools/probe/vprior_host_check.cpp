@@ -1,7 +1,9 @@
 // vprior_host_check.cpp — the host side of the per-variable-prior and channel
 // handles under a sanitizer, without a device and without Python: create /
 // destroy, threshold-table formation and every validation path that returns
-// before a HIP call. Built from the library's own sources, e.g.
+// before a HIP call. Built from the library's own translation units (the
+// Makefile's SRC and the <unit>_kernels.hip of its UNITS; the kernel headers
+// wave_common.h ... bp_team.h come in through them), e.g.
 //   cd qldpcsim_amd/csrc && hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off \
 //     -Xarch_host -fsanitize=address,undefined ../../tools/probe/vprior_host_check.cpp \
 //     decoder_kernels.hip bp_team_kernels.hip ms_flood_kernels.hip decode_prior_kernels.hip \
