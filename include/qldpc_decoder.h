@@ -86,6 +86,7 @@ typedef struct qldpc_logicals qldpc_logicals; /* logical operators of a CSS pair
 typedef struct qldpc_relay qldpc_relay;       /* relay min-sum: legs and memory strengths of one code */
 typedef struct qldpc_prior qldpc_prior;       /* one prior probability per variable of one code */
 typedef struct qldpc_channel qldpc_channel;   /* per-qubit Pauli probabilities of a CSS pair */
+typedef struct qldpc_phenom qldpc_phenom;     /* logical table of one CSS half (phenomenological noise) */
 
 const char *qldpc_last_error(void);
 const char *qldpc_version(void);
@@ -567,6 +568,59 @@ int qldpc_count_logical_ex(const qldpc_code *hx, const qldpc_code *hz, const qld
                            int ehat_format, const int32_t *d_iters_x, const int32_t *d_iters_z,
                            int64_t *d_counters, uint8_t *d_class_x, uint8_t *d_class_z, uint64_t *d_flip_x,
                            uint64_t *d_flip_z, void *stream);
+
+/* ---- Phenomenological noise: multi-round space-time decoding -------------
+ * T = rounds rounds of syndrome extraction of one CSS half: `code` is the
+ * half's H [m][n] (the X half: Hz), L [k][n] its logical table (Lz). Round t
+ * draws a data error e_t (probability p_data per qubit) and, for t < T-1, a
+ * measurement error u_t (probability q per check); the last round is measured
+ * perfectly. Detectors d_t = H e_t ^ u_t ^ u_{t-1} (u_{-1} = u_{T-1} = 0).
+ * Space-time columns, round-major, N = T n + (T-1) m: round t owns data
+ * columns t (n+m) + j and, for t < T-1, measurement columns t (n+m) + n + c;
+ * detector rows M = T m, row t m + c. With T = 1 this is H itself. No
+ * reference counterpart.
+ *
+ * qldpc_phenom_sample: shots shot0 .. shot0+batch-1 of the stream `seed`.
+ * Column J of shot s fires iff u < thr_J with qldpc_channel_sample's draw,
+ * u = Philox4x32-10(key = seed, counter = (J % 64, (J / 64) / 4, s mod 2^32,
+ * s >> 32))[(J / 64) % 4], and thr_J = floor(prob 2^32), prob = p_data on
+ * data and q on measurement columns: bit for bit qldpc_channel_sample_vec on
+ * the materialised matrix with (px, py, pz) = (prior, 0, 0).
+ *   d_det    uint8 [batch][M] (QLDPC_FMT_BYTES) or uint64 [batch][ceil(M/64)]
+ *   d_E      uint64 [batch][ceil(n/64)]   XOR_t e_t, bit j % 64 of word j / 64
+ *   d_fired  uint64 [batch][ceil(N/64)]   the whole fired row (NULL: not written)
+ *
+ * qldpc_phenom_create: h_L is host uint8 [k][n] (0/1), 0 <= k <= n (k = 0: may
+ * be NULL); packs it word-major and uploads it once to the code's device.
+ * `code` must outlive the handle. Without a visible device the handle is
+ * still made. qldpc_phenom_destroy: NULL is accepted.
+ *
+ * qldpc_phenom_count: with Ehat the XOR of the estimate's T data blocks and
+ * r = E ^ Ehat, a shot is class 2 (decoder failure) if H_st ehat != d, else
+ * class 1 (logical error) if L r != 0 mod 2, else class 0 (success).
+ *   d_ehat      uint8 [batch][N] or uint64 [batch][ceil(N/64)] (ehat_format)
+ *   d_iters     int32 [batch]
+ *   d_counters  int64 [4], added to: failures, logical errors, successes,
+ *               sum of iterations
+ *   d_class     uint8 [batch]                                (NULL: not written)
+ *   d_flips     uint64 [batch][ceil(k/64)]  L r mod 2, as computed for every
+ *               class, nothing for k = 0                     (NULL: not written)
+ *   d_resid     uint64 [batch][ceil(n/64)]  r                (NULL: not written)
+ *
+ * Both: rounds < 1, a probability outside [0, 1), an unknown format, a
+ * negative batch, a null handle or required buffer -> QLDPC_EINVAL, before any
+ * HIP call. Limits (QLDPC_EUNSUP, before any launch): n <= 4096, m and E <=
+ * 65535, and N bounded by a wave's LDS slice (H's CSR, for the counter L's
+ * table up to 64 KiB, and 8 (ceil(N/64) + 1) bytes per wave, four waves).
+ * Asynchronous on `stream`: no allocation, copy or synchronisation. */
+int qldpc_phenom_create(const qldpc_code *code, const uint8_t *h_L, int k, qldpc_phenom **out);
+int qldpc_phenom_destroy(qldpc_phenom *ph);
+int qldpc_phenom_sample(const qldpc_code *code, int rounds, double p_data, double q, uint64_t seed, uint64_t shot0,
+                        int64_t batch, void *d_det, int det_format, uint64_t *d_E, uint64_t *d_fired, void *stream);
+int qldpc_phenom_count(const qldpc_code *code, const qldpc_phenom *ph, int rounds, int64_t batch, const void *d_det,
+                       int det_format, const uint64_t *d_E, const void *d_ehat, int ehat_format,
+                       const int32_t *d_iters, int64_t *d_counters, uint8_t *d_class, uint64_t *d_flips,
+                       uint64_t *d_resid, void *stream);
 
 /* Kernel timing (HIP events around each decode kernel launch, on the launch
  * stream). Enabled by qldpc_timing_enable(1); qldpc_timing_read returns the

@@ -40,6 +40,7 @@ EXPORTS = (
     "qldpc_count_outcomes_ex",
     "qldpc_channel_table", "qldpc_channel_create", "qldpc_channel_destroy", "qldpc_channel_sample_vec",
     "qldpc_logicals_create", "qldpc_logicals_destroy", "qldpc_count_logical_ex",
+    "qldpc_phenom_create", "qldpc_phenom_destroy", "qldpc_phenom_sample", "qldpc_phenom_count",
     "qldpc_timing_enable", "qldpc_timing_reset", "qldpc_timing_read",
     "qldpc_set_option", "qldpc_get_option",
 )
@@ -123,6 +124,10 @@ def _load():
         "qldpc_logicals_create": ([P, P, P, P, I, PP], I),
         "qldpc_logicals_destroy": ([P], I),
         "qldpc_count_logical_ex": ([P, P, P, I64, P, P, P, P, I, P, P, I, P, P, P, P, P, P, P, P], I),
+        "qldpc_phenom_create": ([P, P, I, PP], I),
+        "qldpc_phenom_destroy": ([P], I),
+        "qldpc_phenom_sample": ([P, I, D, D, ctypes.c_uint64, ctypes.c_uint64, I64, P, I, P, P, P], I),
+        "qldpc_phenom_count": ([P, P, I, I64, P, I, P, P, I, P, P, P, P, P, P], I),
         "qldpc_timing_enable": ([I], I),
         "qldpc_timing_reset": ([], I),
         "qldpc_timing_read": ([P, P], I),
@@ -404,6 +409,42 @@ class Channel:
         if h and lib is not None:
             lib.qldpc_channel_destroy(h)
             self.handle = None
+
+
+class PhenomTable:
+    """Logical table L [k, n] of one CSS half on the code's device
+    (qldpc_phenom), for qldpc_phenom_count. Keeps the Code alive."""
+
+    def __init__(self, code, L):
+        self.code = code
+        L = np.ascontiguousarray(np.asarray(L) % 2, dtype=np.uint8)
+        if L.ndim != 2 or (L.shape[0] and L.shape[1] != code.n):
+            raise ValueError(f"the logical table must be a [k, {code.n}] matrix")
+        self.k = int(L.shape[0])
+        self.kw = (self.k + 63) // 64
+        h = ctypes.c_void_p()
+        check(lib.qldpc_phenom_create(code.handle, ptr(L) if self.k else None, self.k, ctypes.byref(h)))
+        self.handle = h
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h and lib is not None:
+            lib.qldpc_phenom_destroy(h)
+            self.handle = None
+
+
+def phenom_sample(code, rounds, p_data, q, seed, shot0, batch, det, det_fmt, E, fired=None, stream=None):
+    """qldpc_phenom_sample on raw device addresses (ints; `fired` may be None)."""
+    check(lib.qldpc_phenom_sample(code.handle, int(rounds), float(p_data), float(q), int(seed) & ((1 << 64) - 1),
+                                  int(shot0) & ((1 << 64) - 1), int(batch), det, int(det_fmt), E, fired, stream))
+
+
+def phenom_count(code, table, rounds, batch, det, det_fmt, E, ehat, e_fmt, iters, acc, cls=None, flips=None,
+                 resid=None, stream=None):
+    """qldpc_phenom_count on raw device addresses (ints; the three per-shot
+    outputs may be None)."""
+    check(lib.qldpc_phenom_count(code.handle, table.handle, int(rounds), int(batch), det, int(det_fmt), E, ehat,
+                                 int(e_fmt), iters, acc, cls, flips, resid, stream))
 
 
 def logicals_for(Hx, Hz, device_index=None):

@@ -1,0 +1,62 @@
+// phenom_kernels.h — device shot source and outcome counter of the
+// phenomenological noise model (multi-round space-time decoding of one CSS
+// half), shared with capi_phenom.cpp.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace qldpc {
+
+// CSR of the half's H (original column order), as qldpc_code holds it on the
+// device, and the space-time shape it spans over `rounds` rounds.
+struct PhenomTabs {
+  const int32_t* rp;
+  const int32_t* ci;
+  int m, n, e;   // rows, columns, edges of H
+  int udeg;      // row degree shared by every row of H (6, 7, 8), else 0
+  int W;         // 64-bit words of an n-bit vector
+  int rounds;    // T
+  int N, M;      // T n + (T-1) m columns, T m detector rows
+  int NW, MW;    // 64-bit words of an N-bit / M-bit vector
+};
+
+struct PhenomSampleArgs {
+  PhenomTabs t;
+  uint8_t* det;      // [batch][M] bytes (det_bits: uint64 [batch][MW])
+  int det_bits;
+  uint64_t* E;       // [batch][W] XOR of the rounds' data errors
+  uint64_t* fired;   // [batch][NW] the whole fired row; may be null
+  long long batch;
+  uint64_t shot0;
+  uint32_t key0, key1;
+  uint64_t thr_data, thr_meas;  // a column fires iff its 32-bit draw u < thr
+};
+
+struct PhenomCountArgs {
+  PhenomTabs t;
+  const uint8_t* det;    // as the sampler wrote them
+  int det_bits;
+  const uint64_t* E;     // [batch][W]
+  const uint8_t* ehat;   // [batch][N] bytes (eh_bits: uint64 [batch][NW])
+  int eh_bits;
+  const int32_t* iters;  // [batch]
+  const uint64_t* tab;   // L, word-major [W][kp]: word w of logical row i at w * kp + i
+  int k, kp;             // logical rows; k padded to a multiple of 64 (padding rows are zero)
+  int tab_lds;           // the table is staged into LDS, else read from global memory
+  unsigned long long* acc;  // [4] accumulated: failures, logical errors, successes, iteration sum
+  uint8_t* cls;          // [batch] 0 success, 1 logical error, 2 decoder failure; may be null
+  uint64_t* flips;       // [batch][kp / 64] L r mod 2; may be null
+  uint64_t* resid;       // [batch][W] r = E ^ fold(ehat); may be null
+  long long batch;
+};
+
+constexpr int kPhenomWaves = 4;  // waves per workgroup (one shot per wave at a time)
+constexpr int kPhenomCounters = 4;
+
+// LDS bytes of a workgroup of each kernel
+long long phenom_sample_lds_bytes(const PhenomTabs& t);
+long long phenom_count_lds_bytes(const PhenomTabs& t, int kp, bool tab_lds);
+hipError_t launch_phenom_sample(const PhenomSampleArgs& a, int grid, hipStream_t stream);
+hipError_t launch_phenom_count(const PhenomCountArgs& a, int grid, hipStream_t stream);
+
+}  // namespace qldpc

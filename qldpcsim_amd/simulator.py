@@ -42,13 +42,17 @@ from . import _lib, decoders
 from .schedule import layerize, select_layers, pack_layers  # noqa: F401  (re-exported)
 
 __all__ = ["load_matrix", "simulate_p", "simulate", "main", "layerize", "sample_channel",
-           "count_outcomes", "count_logical_outcomes", "wilson_interval"]
+           "count_outcomes", "count_logical_outcomes", "wilson_interval", "simulate_phenomenological"]
 
 COUNTER_KEYS = ("DecFailures_X", "DecFailures_Z", "decSuccessExact", "decSuccessDegen",
                 "nIterAccX", "nIterAccZ")
 # the logical option's counters (class-1 half-shots per half; shots with both
 # halves class 0), after COUNTER_KEYS in the device accumulator
 LOGICAL_KEYS = ("logicalErrors_X", "logicalErrors_Z", "decSuccessLogical")
+# simulate_phenomenological's counters (the all-reduced vector, in this order)
+PHENOM_KEYS = ("DecFailures_X", "DecFailures_Z", "logicalErrors_X", "logicalErrors_Z", "nIterAccX", "nIterAccZ",
+               "decSuccessLogical")
+PHENOM_Z_KEY = 0x9E3779B97F4A7C15          # the Z half's Philox key is the X half's ^ this
 
 
 def load_matrix(path: str) -> np.ndarray:
@@ -745,6 +749,258 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
     return res
 
 
+class DevicePhenomHalf:
+    """Device-side shot source and outcome counter of one CSS half under
+    phenomenological noise (phenom_kernels.hip via qldpc_phenom_sample /
+    qldpc_phenom_count): `H` [m, n] detects the half's errors, `L` [k, n] is
+    its logical table, `rounds` = T. Shot s of key k is the same whatever the
+    batching. Packed outputs are int64 words, bit j % 64 of word j / 64."""
+
+    def __init__(self, H, L, rounds, device, seed, shot0=0):
+        import torch
+        from . import spacetime
+        self.torch = torch
+        self.dev = torch.device(device)
+        self.T = int(rounds)
+        self.m, self.n = H.shape
+        self.M, self.N = spacetime.spacetime_shape(self.n, self.m, self.T)
+        self.W, self.NW, self.MW = (self.n + 63) // 64, (self.N + 63) // 64, (self.M + 63) // 64
+        with torch.cuda.device(self.dev):
+            self.code = _lib.code_for(H, self.dev.index)
+            self.table = _lib.PhenomTable(self.code, L)
+        self.seed = int(seed) & ((1 << 64) - 1)
+        self.shot = int(shot0)
+
+    def _stream(self):
+        return self.torch.cuda.current_stream(self.dev).cuda_stream
+
+    def sample(self, p_data, q, B, bits=False, want_fired=False):
+        """(det, E) of the next B shots: det uint8 [B, M] (bits: int64
+        [B, ceil(M/64)]), E int64 [B, ceil(n/64)]; with want_fired also the
+        fired rows int64 [B, ceil(N/64)]."""
+        torch = self.torch
+        det = torch.empty((B, self.MW), dtype=torch.int64, device=self.dev) if bits else \
+            torch.empty((B, self.M), dtype=torch.uint8, device=self.dev)
+        E = torch.empty((B, self.W), dtype=torch.int64, device=self.dev)
+        fired = torch.empty((B, self.NW), dtype=torch.int64, device=self.dev) if want_fired else None
+        _lib.phenom_sample(self.code, self.T, p_data, q, self.seed, self.shot, B, det.data_ptr(),
+                           _lib.FMT_BITS if bits else _lib.FMT_BYTES, E.data_ptr(),
+                           fired.data_ptr() if want_fired else None, self._stream())
+        self.shot += int(B)
+        return (det, E, fired) if want_fired else (det, E)
+
+    def count_device(self, det, E, ehat, iters, acc=None, want_shots=False, want_class=False):
+        """Adds the batch's four counters (failures, logical errors, successes,
+        iteration sum) to `acc` (int64 [4] device tensor, created if None),
+        without a host sync. det as sample() wrote it; ehat uint8 [B, N] or
+        int64 [B, ceil(N/64)]; iters int32 [B]. want_class: returns (acc,
+        class uint8 [B]); want_shots: (acc, class, flip words int64
+        [B, ceil(k/64)], residual words int64 [B, ceil(n/64)])."""
+        torch = self.torch
+        if acc is None:
+            acc = torch.zeros(4, dtype=torch.int64, device=self.dev)
+        B = det.shape[0]
+        d_bits, e_bits = det.dtype == torch.int64, ehat.dtype == torch.int64
+        ts = (det, E, ehat, iters, acc)
+        if not all(t.is_contiguous() and t.device == self.dev for t in ts) or \
+                tuple(det.shape) != ((B, self.MW) if d_bits else (B, self.M)) or \
+                tuple(ehat.shape) != ((B, self.NW) if e_bits else (B, self.N)) or \
+                det.dtype not in (torch.uint8, torch.int64) or ehat.dtype not in (torch.uint8, torch.int64) or \
+                tuple(E.shape) != (B, self.W) or E.dtype != torch.int64 or tuple(iters.shape) != (B,) or \
+                iters.dtype != torch.int32 or tuple(acc.shape) != (4,) or acc.dtype != torch.int64:
+            raise ValueError("count_device: buffers do not match the batch layout")
+        cls = torch.empty(B, dtype=torch.uint8, device=self.dev) if (want_shots or want_class) else None
+        flips = torch.empty((B, self.table.kw), dtype=torch.int64, device=self.dev) if want_shots else None
+        resid = torch.empty((B, self.W), dtype=torch.int64, device=self.dev) if want_shots else None
+        P = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        F = lambda b: _lib.FMT_BITS if b else _lib.FMT_BYTES  # noqa: E731
+        _lib.phenom_count(self.code, self.table, self.T, B, det.data_ptr(), F(d_bits), E.data_ptr(), ehat.data_ptr(),
+                          F(e_bits), iters.data_ptr(), acc.data_ptr(), P(cls), P(flips), P(resid), self._stream())
+        if want_shots:
+            return acc, cls, flips, resid
+        return (acc, cls) if want_class else acc
+
+
+def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float, rounds: int, shots: int = 1000,
+                              decType: str = "MS", decIterations: int = 99, decSchedule: str = "F",
+                              OSDorder: int = -1, rngSeed: Optional[int] = None, *,
+                              batch_size: Optional[int] = None, sampler: Optional[str] = None,
+                              verbose: bool = True, **unsupported) -> dict:
+    """Phenomenological noise (extension; no reference counterpart): `rounds`
+    = T rounds of syndrome extraction with measurement error probability `q`,
+    the last round measured perfectly, decoded over each half's space-time
+    check matrix (spacetime.spacetime_matrix).
+
+    The two halves are independent channels: in every round each qubit carries
+    an X component (detected by Hz, the X half) with probability p_data = 2p/3
+    and a Z component (detected by Hx) with the same probability, the true
+    marginals of depolarizing noise of strength p, as with --bias. The Y
+    correlation between the halves is not modelled. Each half's detectors
+    d_t = H e_t ^ u_t ^ u_{t-1} are decoded with the priors p_data on data
+    columns and q on measurement columns: the scalar entry point when they are
+    equal (every specialised kernel and the HBM-resident one apply, at any
+    size), else decode_batch(prior=spacetime_prior(...)) with
+    decode_vprior_kernel's limits (its NotImplementedError is passed on).
+
+    decType "MS" or "BP"; decSchedule "F", or "L" / "S" with layers from
+    schedule.layerize of the half's own space-time matrix (none of the
+    reference's cross-wiring). OSDorder >= 0 (MS only, as in simulate_p) runs
+    decoders.apply_osd_device per half after its decode, unpipelined.
+    `sampler`: "device" (phenom_kernels.hip, the default with a device) or
+    "host" (the NumPy twins in spacetime.py, drawn from
+    np.random.default_rng([rngSeed, rank]), the X half first in every batch).
+    On the device the X half's Philox key is simulate_p's
+    (SeedSequence([rngSeed, rank])) and the Z half's is that ^
+    0x9E3779B97F4A7C15. With torch.distributed initialised the shots shard as
+    in simulate_p: contiguous shares, a key per rank, one all_reduce(SUM).
+
+    A half-shot is class 2 (decoder failure) if the estimate does not
+    reproduce the detectors, else class 1 (logical error) if L·(E ^ Ê) != 0
+    with E / Ê the XOR of the true / estimated data errors over the rounds,
+    else class 0. Returns DecFailures_X/Z, logicalErrors_X/Z, nIterAccX/Z,
+    decSuccessLogical (shots with both halves class 0), logical_error_rate =
+    1 - decSuccessLogical / shots, its 95 % Wilson interval
+    logical_error_rate_ci95, logical_error_rate_per_round =
+    1 - (1 - LER)^(1/rounds), and rounds, q, p_data.
+
+    ValueError: decType RELAY / NG / BF, correlated= and channel_weights= (not
+    defined for this model), probabilities outside [0, 1), rounds < 1, a pair
+    that is not CSS."""
+    from . import spacetime
+    from .logicals import css_logicals
+    for k_ in unsupported:
+        if k_ in ("correlated", "channel_weights", "correlated_q1", "logical", "samples"):
+            raise ValueError(f"simulate_phenomenological does not take {k_}=: the phenomenological model has "
+                             "independent halves with uniform data noise")
+        raise TypeError(f"simulate_phenomenological() got an unexpected keyword argument {k_!r}")
+    if decType in ("RELAY",) + tuple(_lib.HARD_ALGOS):
+        raise ValueError(f"decType {decType} is not available on space-time matrices (MS or BP)")
+    if decType not in ("MS", "BP"):
+        raise ValueError("Unrecognized decoder type.")
+    if decSchedule not in ("F", "L", "S"):
+        raise ValueError("Unrecognized decoder scheduling option.")
+    T = int(rounds)
+    if T < 1 or T != rounds:
+        raise ValueError("rounds must be an integer >= 1")
+    if not (0.0 <= float(p) < 1.0) or not (0.0 <= float(q) < 1.0):
+        raise ValueError("p and q must lie in [0, 1)")
+    if sampler not in (None, "device", "host"):
+        raise ValueError("sampler must be 'device', 'host' or None")
+    if int(shots) < 0:
+        raise ValueError("shots must be >= 0")
+    Hx, Hz = np.asarray(Hx), np.asarray(Hz)
+    n = Hx.shape[1]
+    Lx, Lz = css_logicals(Hx, Hz)                  # ValueError unless (Hx, Hz) is a CSS pair
+    p_data = 2.0 * float(p) / 3.0
+    q = float(q)
+    osd = OSDorder if decType == "MS" else -1      # as simulate_p
+    dist, rank, world = _dist()
+    my_shots = shots // world + (1 if rank < shots % world else 0)
+    seed = None if rngSeed is None else [int(rngSeed), int(rank)]
+    use_dev = sampler == "device" or (sampler is None and _device_ok())
+    if batch_size is None:
+        # posteriors (OSD) and byte rows cost 9 N bytes per half-shot
+        batch_size = ((1 << 18) if osd < 0 else (1 << 14)) if use_dev else (1 << 14)
+    halves = []                                    # X half: (Hz, Lz); Z half: (Hx, Lx)
+    for H_, L_ in ((Hz, Lz), (Hx, Lx)):
+        m_ = H_.shape[0]
+        Hst = spacetime.spacetime_matrix(H_, T)
+        layers = None if decSchedule == "F" else layerize(Hst, serial=decSchedule == "S")
+        lp, lr = pack_layers(layers, Hst.shape[0])
+        pd, pkw = _half_prior(spacetime.spacetime_prior(n, m_, T, p_data, q), False)
+        halves.append(dict(H=H_, L=L_, Hst=Hst, lp=lp, lr=lr, p=pd, pkw=pkw))
+    tot = {k: 0 for k in PHENOM_KEYS}
+    t0 = time.time()
+    done = 0
+
+    def progress():
+        if verbose and rank == 0:
+            print(f"\r(p={p:5.2e}, q={q:5.2e}, T={T}) Decoding block n. {done:3}/{my_shots:4}... "
+                  f"({done / max(time.time() - t0, 1e-9):.3g} shots/s)", end="", flush=True)
+
+    if use_dev:
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        key = int(np.random.SeedSequence(seed).generate_state(1, np.uint64)[0])
+        for h, k_ in zip(halves, (key, key ^ PHENOM_Z_KEY)):
+            h["ch"] = DevicePhenomHalf(h["H"], h["L"], T, dev, k_)
+            h["acc"] = torch.zeros(4, dtype=torch.int64, device=dev)
+        for h in halves:
+            if h["pkw"]:
+                # the vector-prior kernel's limits are met when its launch is
+                # planned: one all-zero detector row per half, so a shape past
+                # them is refused (NotImplementedError) before any shot is drawn
+                decoders.decode_batch(h["Hst"], torch.zeros((1, h["Hst"].shape[0]), dtype=torch.uint8, device=dev),
+                                      None, 1, algo=decType, layer_ptr=h["lp"], layer_rows=h["lr"], **h["pkw"])
+        both = torch.zeros(1, dtype=torch.int64, device=dev)
+        packed = osd < 0                           # bit-packed detectors and estimates unless OSD reads byte rows
+        while done < my_shots:
+            B = min(batch_size, my_shots - done)
+            cls = []
+            for h in halves:
+                det, E = h["ch"].sample(p_data, q, B, bits=packed)
+                r = decoders.decode_batch(h["Hst"], det, h["p"], decIterations, algo=decType, want_post=osd >= 0,
+                                          layer_ptr=h["lp"], layer_rows=h["lr"], ehat_bits=packed, **h["pkw"])
+                if osd >= 0:
+                    decoders.apply_osd_device(h["Hst"], det, r, osd)
+                cls.append(h["ch"].count_device(det, E, r.ehat, r.iters, h["acc"], want_class=True)[1])
+            both += ((cls[0] | cls[1]) == 0).sum()
+            done += B
+            progress()
+        aX, aZ = (h["acc"].cpu().tolist() for h in halves)
+        tot = dict(zip(PHENOM_KEYS, (int(v) for v in (aX[0], aZ[0], aX[1], aZ[1], aX[3], aZ[3], int(both.cpu())))))
+    else:
+        rng = np.random.default_rng(seed)
+        while done < my_shots:
+            B = min(batch_size, my_shots - done)
+            cls = []
+            for h, sfx in zip(halves, "XZ"):
+                det, E = spacetime.sample_phenomenological(h["H"], T, p_data, q, B, rng)
+                r = decoders.decode_batch(h["Hst"], det, h["p"], decIterations, algo=decType, osd_order=osd,
+                                          layer_ptr=h["lp"], layer_rows=h["lr"], **h["pkw"])
+                c, (cl, _, _) = spacetime.count_phenomenological(h["H"], h["L"], T, det, E, r.ehat, r.iters,
+                                                                 want_shots=True)
+                tot["DecFailures_" + sfx] += c["failures"]
+                tot["logicalErrors_" + sfx] += c["logical_errors"]
+                tot["nIterAcc" + sfx] += c["iterations"]
+                cls.append(cl)
+            tot["decSuccessLogical"] += int(((cls[0] | cls[1]) == 0).sum())
+            done += B
+            progress()
+    if dist is not None and world > 1:
+        import torch
+        backend = dist.get_backend()
+        dev = torch.device("cuda", torch.cuda.current_device()) if backend == "nccl" else torch.device("cpu")
+        t = torch.tensor([tot[k] for k in PHENOM_KEYS], dtype=torch.int64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)   # the only collective: seven values
+        tot = dict(zip(PHENOM_KEYS, (int(v) for v in t.cpu().tolist())))
+    if verbose and rank == 0:
+        print()
+    res = dict(tot)
+    ler = 1. - tot["decSuccessLogical"] / float(shots) if shots else 0.0
+    res["logical_error_rate"] = ler
+    res["logical_error_rate_ci95"] = wilson_interval(shots - tot["decSuccessLogical"], shots)
+    res["logical_error_rate_per_round"] = 1. - (1. - ler) ** (1. / T)
+    res["rounds"], res["q"], res["p_data"] = T, q, p_data
+    return res
+
+
+def format_phenomenological_results(p, results, shots):
+    """The phenomenological mode's table."""
+    lines = ["\n             ===          PHENOMENOLOGICAL NOISE: SPACE-TIME DECODING          ===\n",
+             "   Depolarizing probability | Meas. error |  T  | Logical error rate (per round) |"
+             "     95 % interval      | Failures (X,Z) | Logical errors (X,Z)",
+             "----------------------------+-------------+-----+--------------------------------+"
+             "------------------------+----------------+----------------------"]
+    for pT, r in zip(p, results):
+        lo, hi = r["logical_error_rate_ci95"]
+        lines.append(f"         {pT:10.2e}         |  {r['q']:9.2e}  | {r['rounds']:3} |      {r['logical_error_rate']:7.2e} "
+                     f"({r['logical_error_rate_per_round']:7.2e})       |  [{lo:8.2e}, {hi:8.2e}]  |  "
+                     f"{r['DecFailures_X']:6},{r['DecFailures_Z']:6} |     {r['logicalErrors_X']:6},"
+                     f"{r['logicalErrors_Z']:6}")
+    return "\n".join(lines)
+
+
 def format_results(p, results, shots):
     """The reference's results table (simulator.py:342-347)."""
     lines = ["\n                             ===          SIMULATION RESULTS          ===\n",
@@ -801,7 +1057,7 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
              correlated: Optional[str] = None, correlated_q1: float = 0.49,
              relay_legs: int = 11, relay_leg_iters: int = 60, relay_sols: int = 1, relay_gamma0: float = 0.125,
              relay_gamma_range=(-0.24, 0.66), relay_seed: int = 0, bias: Optional[float] = None,
-             channel_weights=None):
+             channel_weights=None, rounds: Optional[int] = None, meas_error: Optional[float] = None):
     """p-sweep + results table (simulator.py:319-347). Returns None like the
     reference unless return_results=True.
 
@@ -822,6 +1078,12 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
     the weights themselves ([3] or [3, n]). Both enter the results file's meta,
     the weights by a SHA-256 digest of their float64 bytes.
 
+    rounds, meas_error (extension): phenomenological noise —
+    simulate_phenomenological(rounds=rounds, q=meas_error) for every point
+    (meas_error defaults to each point's 2p/3), with a results table of its
+    own. "rounds" and "q" enter the results file's meta. meas_error without
+    rounds, logical, correlated, bias and channel_weights raise ValueError.
+
     resultsFile (extension): a JSON file the sweep writes after every
     p-point; a rerun with the same arguments skips the points already there
     (resumable long sweeps). Only rank 0 writes it.
@@ -831,6 +1093,37 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
     Hz = load_matrix(HzFile)
     assert max(p) <= 1. and min(p) >= 0.
     _, rank, world = _dist()
+    if rounds is None and meas_error is not None:
+        raise ValueError("meas_error needs rounds (the phenomenological model)")
+    if rounds is not None:
+        if logical or correlated is not None or bias is not None or channel_weights is not None:
+            raise ValueError("rounds= (phenomenological noise) cannot be combined with logical, correlated, bias or "
+                             "channel_weights")
+        if sampler is None:
+            sampler = "device" if _device_ok() else "host"
+        meta = {"Hx": HxFile, "Hz": HzFile, "shots": shots, "decType": decType, "decIterations": decIterations,
+                "decSchedule": decSchedule, "OSDorder": OSDorder, "rngSeed": rngSeed, "world": world,
+                "sampler": sampler, "rounds": int(rounds), "q": None if meas_error is None else float(meas_error)}
+        done = _load_results(resultsFile, meta)
+        results = []
+        for pT in p:
+            if float(pT) in done:
+                results.append(done[float(pT)])
+                continue
+            t0 = time.perf_counter()
+            r = simulate_phenomenological(Hx, Hz, pT, 2 * pT / 3 if meas_error is None else meas_error, rounds,
+                                          shots=shots, decType=decType, decIterations=decIterations,
+                                          decSchedule=decSchedule, OSDorder=OSDorder, rngSeed=rngSeed,
+                                          batch_size=batch_size, sampler=sampler, verbose=verbose)
+            if on_point is not None:
+                on_point(pT, r, time.perf_counter() - t0)
+            results.append(r)
+            done[float(pT)] = r
+            if resultsFile and rank == 0:
+                _save_results(resultsFile, meta, done)
+        if rank == 0:
+            print(format_phenomenological_results(p, results, shots))
+        return results if return_results else None
     if sampler is None:                       # the resolved shot source is part of the run
         sampler = "device" if (_device_ok() and _channel_ok(Hx, Hz)) else "host"
     meta = {"Hx": HxFile, "Hz": HzFile, "shots": shots, "decType": decType,
@@ -968,9 +1261,27 @@ def main(argv=None):
     parser.add_argument("--channel-weights", default=None, dest="channel_weights", metavar="FILE.npy",
                         help="Pauli weights, shape [3] or [3, n] (rows X, Y, Z): qubit j suffers X, Y, Z with "
                              "probabilities p * w[:, j]; the decoders get each qubit's true marginal as its prior.")
+    # (argparse.SUPPRESS: without the flags the printed namespace is what it was)
+    parser.add_argument("--rounds", type=int, default=argparse.SUPPRESS, metavar="T",
+                        help="Phenomenological noise: T rounds of syndrome extraction (the last one perfect), "
+                             "decoded over each half's space-time check matrix (MS, BP); data errors 2p/3 per "
+                             "half, qubit and round.")
+    parser.add_argument("--meas-error", type=float, default=argparse.SUPPRESS, dest="meas_error", metavar="Q",
+                        help="Phenomenological noise: measurement error probability per check and round "
+                             "(default with --rounds: 2p/3).")
     args = parser.parse_args(argv)
     if args.bias is not None and args.channel_weights is not None:
         parser.error("--bias and --channel-weights exclude each other")
+    rounds, meas_error = getattr(args, "rounds", None), getattr(args, "meas_error", None)
+    if meas_error is not None and rounds is None:
+        parser.error("--meas-error needs --rounds")
+    if rounds is not None:
+        if rounds < 1:
+            parser.error("--rounds must be >= 1")
+        if args.logical or args.correlated or args.bias is not None or args.channel_weights:
+            parser.error("--rounds cannot be combined with --logical, --correlated, --bias or --channel-weights")
+        if args.decType not in ("MS", "BP"):
+            parser.error("--rounds decodes with MS or BP")
     own_group = _init_dist_from_env()              # torchrun: shots shard over the ranks
     _, rank, _ = _dist()
     if rank == 0:
@@ -985,6 +1296,7 @@ def main(argv=None):
                  **({"correlated": args.correlated, "correlated_q1": args.correlated_q1} if args.correlated else {}),
                  **({"bias": args.bias} if args.bias is not None else {}),
                  **({"channel_weights": np.load(args.channel_weights)} if args.channel_weights else {}),
+                 **({"rounds": rounds, "meas_error": meas_error} if rounds is not None else {}),
                  **({k: getattr(args, k) for k in ("relay_legs", "relay_leg_iters", "relay_sols", "relay_gamma0",
                                                    "relay_gamma_range", "relay_seed")}
                     if args.decType == "RELAY" else {}))
