@@ -30,7 +30,8 @@ not reproducible; here they are).
 import argparse
 import sys
 import time
-from typing import Optional
+from dataclasses import dataclass
+from typing import NamedTuple, Optional
 
 # smallest tapered tail batch = batch_size // TAIL_DIV (see the tail tapering
 # below; 32 vs 8: +0.5 % on configs[3] p = 0.1, profiles/r04bb/)
@@ -38,7 +39,7 @@ TAIL_DIV = 32
 
 import numpy as np
 
-from . import _lib, decoders
+from . import _lib, decoders, spacetime
 from .schedule import layerize, select_layers, pack_layers  # noqa: F401  (re-exported)
 
 __all__ = ["load_matrix", "simulate_p", "simulate", "main", "layerize", "sample_channel",
@@ -160,6 +161,13 @@ def count_outcomes(Hx, Hz, sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ):
             breakpoint() there)
     failX/Z: syndrome of the estimate differs from the measured one (:300-303)
     """
+    return _count_outcomes(Hx, Hz, sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ)[0]
+
+
+def _count_outcomes(Hx, Hz, sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ):
+    """count_outcomes' dict and the two failure masks (bool [B]) it counted,
+    which count_logical_outcomes classifies by."""
+    eX, eZ = np.asarray(eX), np.asarray(eZ)
     exact = np.all(errX == eX, axis=1) & np.all(errZ == eZ, axis=1)
     dX = (errX ^ eX).astype(np.float32)
     dZ = (errZ ^ eZ).astype(np.float32)
@@ -176,7 +184,7 @@ def count_outcomes(Hx, Hz, sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ):
         "decSuccessDegen": int(degen.sum()),
         "nIterAccX": int(np.asarray(itX, dtype=np.int64).sum()),
         "nIterAccZ": int(np.asarray(itZ, dtype=np.int64).sum()),
-    }
+    }, failX, failZ
 
 
 def _pack_flips(F):
@@ -214,11 +222,7 @@ def count_logical_outcomes(Hx, Hz, sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ, log
         logicals = css_logicals(Hx, Hz)
     Lx, Lz = logicals
     f32 = np.float32
-    out = count_outcomes(Hx, Hz, sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ)
-    sX = (np.asarray(eX).astype(f32) @ Hz.T.astype(f32)).astype(np.int64) % 2
-    sZ = (np.asarray(eZ).astype(f32) @ Hx.T.astype(f32)).astype(np.int64) % 2
-    failX = np.any(sX != sy_z, axis=1)
-    failZ = np.any(sZ != sy_x, axis=1)
+    out, failX, failZ = _count_outcomes(Hx, Hz, sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ)
     fX = ((errX ^ eX).astype(f32) @ Lz.T.astype(f32)).astype(np.int64) % 2
     fZ = ((errZ ^ eZ).astype(f32) @ Lx.T.astype(f32)).astype(np.int64) % 2
     cX = np.where(failX, 2, np.any(fX != 0, axis=1).astype(np.uint8)).astype(np.uint8)
@@ -241,6 +245,17 @@ def wilson_interval(successes, trials, z=1.959963984540054):
     mid = (ph + z * z / (2.0 * trials)) / den
     half = z * np.sqrt(ph * (1.0 - ph) / trials + z * z / (4.0 * trials * trials)) / den
     return [float(max(0.0, mid - half)), float(min(1.0, mid + half))]
+
+
+def _fmt(bits):
+    """The C ABI's buffer format of bit-packed words (`bits`) or byte rows."""
+    return _lib.FMT_BITS if bits else _lib.FMT_BYTES
+
+
+def _stream(dev):
+    """torch's current HIP stream on `dev`, as the C ABI takes it."""
+    import torch
+    return torch.cuda.current_stream(dev).cuda_stream
 
 
 class DeviceChannel:
@@ -275,9 +290,6 @@ class DeviceChannel:
         with self.torch.cuda.device(self.dev):
             self._vec = _lib.Channel(self.cx, self.cz, probs[0], probs[1], probs[2])
 
-    def _stream(self):
-        return self.torch.cuda.current_stream(self.dev).cuda_stream
-
     def sample(self, p, B, bits=False):
         """`bits`: syndromes as int64 words [B, ceil(m/64)] (decode_batch
         reads either format) instead of uint8 [B, m]."""
@@ -293,12 +305,11 @@ class DeviceChannel:
         if self._vec is not None:
             _lib.check(_lib.lib.qldpc_channel_sample_vec(
                 self._vec.handle, self.seed, self.shot, int(B), errX.data_ptr(), errZ.data_ptr(), sy_z.data_ptr(),
-                sy_x.data_ptr(), _lib.FMT_BITS if bits else _lib.FMT_BYTES, self._stream()))
+                sy_x.data_ptr(), _fmt(bits), _stream(self.dev)))
         else:
             _lib.check(_lib.lib.qldpc_channel_sample_ex(
                 self.cx.handle, self.cz.handle, float(p), self.seed, self.shot, int(B), errX.data_ptr(),
-                errZ.data_ptr(), sy_z.data_ptr(), sy_x.data_ptr(), _lib.FMT_BITS if bits else _lib.FMT_BYTES,
-                self._stream()))
+                errZ.data_ptr(), sy_z.data_ptr(), sy_x.data_ptr(), _fmt(bits), _stream(self.dev)))
         self.shot += int(B)
         return sy_z, sy_x, errX, errZ
 
@@ -318,7 +329,7 @@ class DeviceChannel:
         _lib.check(_lib.lib.qldpc_count_outcomes_ex(
             self.cx.handle, self.cz.handle, int(B), errX.data_ptr(), errZ.data_ptr(), sy_z.data_ptr(),
             sy_x.data_ptr(), syn_fmt, eX.data_ptr(), eZ.data_ptr(), e_fmt, itX.data_ptr(),
-            itZ.data_ptr(), acc.data_ptr(), self._stream()))
+            itZ.data_ptr(), acc.data_ptr(), _stream(self.dev)))
         return acc
 
     def _layout(self, who, sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ):
@@ -335,8 +346,7 @@ class DeviceChannel:
                 eX.dtype not in (torch.uint8, torch.int64) or eZ.dtype != eX.dtype or \
                 sy_x.dtype != sy_z.dtype or itX.dtype != torch.int32 or itZ.dtype != torch.int32:
             raise ValueError(f"{who}: buffers do not match the batch layout")
-        F = lambda b: _lib.FMT_BITS if b else _lib.FMT_BYTES  # noqa: E731
-        return B, F(syn_bits), F(e_bits)
+        return B, _fmt(syn_bits), _fmt(e_bits)
 
     def count(self, sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ):
         v = self.count_device(sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ).cpu().tolist()
@@ -374,7 +384,7 @@ class DeviceChannel:
         _lib.check(_lib.lib.qldpc_count_logical_ex(
             self.cx.handle, self.cz.handle, lg.handle, int(B), errX.data_ptr(), errZ.data_ptr(), sy_z.data_ptr(),
             sy_x.data_ptr(), syn_fmt, eX.data_ptr(), eZ.data_ptr(), e_fmt, itX.data_ptr(), itZ.data_ptr(),
-            acc.data_ptr(), sp[0], sp[1], sp[2], sp[3], self._stream()))
+            acc.data_ptr(), sp[0], sp[1], sp[2], sp[3], _stream(self.dev)))
         return (acc,) + shots if want_shots else acc
 
     def count_logical(self, sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ):
@@ -425,6 +435,313 @@ def _host_orders_on(dev, staged):
     import torch
     torch.cuda.set_device(dev)
     return decoders.osd_host_orders(staged)
+
+
+def _shard(shots, rngSeed):
+    """This rank's contiguous share of the shots: (rank, its shots, its first
+    shot's index, its seed pair [rngSeed, rank] or None)."""
+    _, rank, world = _dist()
+    my_shots = shots // world + (1 if rank < shots % world else 0)
+    my_start = rank * (shots // world) + min(rank, shots % world)
+    return rank, my_shots, my_start, None if rngSeed is None else [int(rngSeed), int(rank)]
+
+
+def _device_key(seed):
+    """The device samplers' Philox key of _shard's seed pair."""
+    return int(np.random.SeedSequence(seed).generate_state(1, np.uint64)[0])
+
+
+def _progress(label, my_shots, on, rates=False):
+    """The progress line's printer show(done[, tot]), silent unless `on`.
+    `rates`: the host path's line, with the failure rates so far from its
+    counter dict `tot`."""
+    t0 = time.time()
+
+    def show(done, tot=None):
+        if on:
+            note = (f"Dec. failure rates (X,Z): {tot['DecFailures_X'] / done:.2e}, "
+                    f"{tot['DecFailures_Z'] / done:.2e} ") if rates else ""
+            print(f"\r{label} Decoding block n. {done:3}/{my_shots:4}... {note}"
+                  f"({done / max(time.time() - t0, 1e-9):.3g} shots/s)", end="", flush=True)
+    return show
+
+
+def _all_reduce(tot, keys):
+    """The counter dict `tot` summed over the ranks: a point's only collective
+    (six values, nine with logical, seven phenomenological)."""
+    dist, _, world = _dist()
+    if dist is None or world == 1:
+        return tot
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
+    t = torch.tensor([tot[k] for k in keys], dtype=torch.int64, device=dev)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return dict(zip(keys, (int(v) for v in t.cpu().tolist())))
+
+
+class _Half(NamedTuple):
+    """One CSS half as decode_batch takes it, built once per call."""
+    H: np.ndarray                # the matrix decoded (phenomenological: the half's space-time matrix)
+    lp: np.ndarray               # its packed layers
+    lr: np.ndarray
+    p: Optional[float]           # decode_batch's p (None with prior=)
+    kw: dict                     # relay= or prior=, if any
+    code: tuple = None           # phenomenological: the code's (H, L), for the sampler and the counter
+
+
+class _Decode(NamedTuple):
+    """What every decode of a call shares."""
+    algo: str
+    iters: int
+    osd: int                     # the effective OSD order (< 0: none)
+    packed: bool                 # device path without OSD: bit-packed syndromes and estimates
+    kw: dict                     # the path's keywords (_path_kw)
+    masked: tuple = None         # correlated: (p, p_masked) of the second half
+
+
+def _path_kw(use_dev, osd):
+    """decode_batch's keywords of a shot path -> (packed, keywords). Device:
+    bit-packed syndromes and estimates (one bit per check / qubit in HBM)
+    unless OSD needs posteriors and byte rows of the failing shots, and OSD
+    is the caller's step; host: decode_batch applies OSD itself."""
+    packed = use_dev and osd < 0
+    return packed, ({"want_post": osd >= 0, "ehat_bits": packed} if use_dev else {"osd_order": osd})
+
+
+def _decode_half(half, syn, dec, mask=None):
+    """Decode one half's syndromes. `mask`: the other half's estimate, for the
+    second half of a correlated decode (prior_mask=, p_masked=)."""
+    kw = dec.kw if mask is None else dict(dec.kw, prior_mask=mask, p_masked=dec.masked[1])
+    return decoders.decode_batch(half.H, syn, half.p if mask is None else dec.masked[0], dec.iters, algo=dec.algo,
+                                 layer_ptr=half.lp, layer_rows=half.lr, **kw, **half.kw)
+
+
+def _decode_pair(plan, sy_z, sy_x, finish=None):
+    """Decode a batch's halves in the plan's order -> [rX, rZ]. Correlated: the
+    second half gets the first one's final estimate as its prior mask, so
+    `finish(H, syn, r)`, the device path's OSD, runs before the estimate is
+    used (decoders.py:179-180)."""
+    syn, res, mask = (sy_z, sy_x), [None, None], None
+    for i in plan.order:
+        res[i] = r = _decode_half(plan.halves[i], syn[i], plan.dec, mask)
+        if finish is not None:
+            finish(plan.halves[i].H, syn[i], r)
+        if plan.dec.masked is not None:
+            mask = r.ehat
+    return res
+
+
+class _Plan(NamedTuple):
+    """simulate_p's checked arguments, as its loops use them."""
+    halves: tuple                # (_Half X: Hz with Hx's layers, _Half Z: Hx with Hz's layers)
+    order: tuple                 # the halves' indices in decode order
+    dec: _Decode
+    probs: Optional[np.ndarray]  # channel_weights: the samplers' per-qubit probabilities
+    logicals: Optional[tuple]    # logical: the pair's (Lx, Lz)
+    use_dev: bool
+
+
+def _plan(Hx, Hz, p, decType, decIterations, decSchedule, OSDorder, rngSeed, samples, sampler, logical, correlated,
+          correlated_q1, relay, channel_weights):
+    """simulate_p's argument checks, in the order they have always been made
+    (all before a shot is drawn or the device is touched), and what they
+    establish. `relay`: the six relay_* arguments by name."""
+    n = Hx.shape[1]
+    hard = decType in _lib.HARD_ALGOS
+    probs = None
+    priors = [(p / 3, {}), (p / 3, {})]           # decode_batch's p and prior= of the X and the Z half
+    if channel_weights is not None:
+        if correlated is not None:
+            raise ValueError("channel_weights cannot be combined with correlated= (its second-half prior "
+                             "assumes depolarizing noise)")
+        probs = channel_probs(p, channel_weights, n)
+        w = _weights_3n(channel_weights, n)
+        priors = [_half_prior(float(p) * (w[0] + w[1]), hard), _half_prior(float(p) * (w[2] + w[1]), hard)]
+        if decType == "RELAY" and (priors[0][1] or priors[1][1]):
+            raise ValueError("decType RELAY takes one scalar prior per half: channel_weights must give every "
+                             "qubit the same marginals")
+    if decType == "RELAY":
+        if OSDorder >= 0:
+            raise ValueError("decType RELAY has no OSD step (OSDorder must be < 0)")
+        if correlated is not None:
+            raise ValueError("decType RELAY cannot be combined with correlated=")
+        if decSchedule != "F":
+            raise ValueError("decType RELAY runs the flooding schedule only (decSchedule 'F')")
+        if int(relay["legs"]) < 1 or int(relay["leg_iters"]) < 1 or int(relay["sols"]) < 1 or int(decIterations) < 1:
+            raise ValueError("relay_legs, relay_leg_iters, relay_sols and decIterations must be >= 1")
+        lo, hi = (float(x) for x in relay["gamma_range"])
+        if not (np.isfinite([lo, hi, float(relay["gamma0"])]).all() and lo <= hi):
+            raise ValueError("relay_gamma0 and relay_gamma_range (lo <= hi) must be finite")
+    if rngSeed is not None:
+        np.random.seed(rngSeed)                    # reference side effect (:187-188); it refuses a bad seed here
+    if Hz.size and Hz.shape[1] != n:
+        raise ValueError("Hx and Hz must have the same number of columns (physical qubits).")
+    layersX, layersZ = select_layers(Hx, Hz, decSchedule)   # raises ValueError (:236)
+    if decType not in _lib.ALGO and decType != "RELAY":
+        raise ValueError("Unrecognized decoder type.")
+    relays = [{}, {}]                              # decode_batch's relay= of each half
+    if decType == "RELAY":
+        leg_iters = [int(decIterations)] + [int(relay["leg_iters"])] * (int(relay["legs"]) - 1)
+        grng = np.random.default_rng(relay["seed"])   # one generator: the Hz-decoded half draws first
+        for kw in relays:
+            gammas = np.empty((len(leg_iters), n), np.float64)
+            gammas[0] = relay["gamma0"]
+            gammas[1:] = grng.uniform(lo, hi, (len(leg_iters) - 1, n))
+            kw["relay"] = decoders.RelayConfig(leg_iters, gammas, int(relay["sols"]))
+    if correlated not in (None, "XZ", "ZX"):
+        raise ValueError("correlated must be 'XZ', 'ZX' or None")
+    masked = None
+    if correlated is not None:
+        if hard:
+            raise ValueError(f"correlated decoding needs a prior: {decType} is a hard-decision decoder")
+        if not (0.0 < float(correlated_q1) <= 0.5):
+            raise ValueError("correlated_q1 must lie in (0, 0.5]")
+        # P(second component | no first component); correlated_q1 stands for the 1/2 given one
+        masked = ((p / 3) / (1 - 2 * p / 3), float(correlated_q1))
+    # the reference never passes OSDorder to BP_decoder (:281-282); NG and BF
+    # get (H, syndrome) alone (:270-276): no prior, no decIterations (BF runs
+    # its default 50), no OSD
+    osd = OSDorder if decType == "MS" else -1
+    halves = (_Half(Hz, *pack_layers(layersX, Hz.shape[0]), priors[0][0], {**relays[0], **priors[0][1]}),
+              _Half(Hx, *pack_layers(layersZ, Hx.shape[0]), priors[1][0], {**relays[1], **priors[1][1]}))
+    pair_logicals = None
+    if logical:
+        from .logicals import css_logicals
+        pair_logicals = css_logicals(Hx, Hz)       # raises ValueError before any shot is drawn
+    if sampler not in (None, "device", "host"):
+        raise ValueError("sampler must be 'device', 'host' or None")
+    if samples is not None and sampler == "device":
+        raise ValueError("samples= decodes the given shots on the host path; it cannot be combined "
+                         "with sampler='device' (which draws its own Philox shots)")
+    use_dev = sampler == "device" or (sampler is None and samples is None and _device_ok()
+                                      and _channel_ok(Hx, Hz))
+    dec = _Decode(decType, 50 if hard else decIterations, osd, *_path_kw(use_dev, osd), masked)
+    return _Plan(halves, (1, 0) if correlated == "ZX" else (0, 1), dec, probs, pair_logicals, use_dev)
+
+
+class _HostChannel:
+    """The host path's shot source and counters, with DeviceChannel's two loop
+    operations. sample() takes the next batch from `samples` (a tuple
+    (sy_z, sy_x, errX, errZ), from row `start`) if given, else draws it from
+    `rng`: per-qubit probabilities `probs` if given, else depolarizing.
+    count() adds a batch's counters to a dict (nine with `logicals`)."""
+
+    def __init__(self, Hx, Hz, rng, samples=None, probs=None, start=0, logicals=None):
+        self.Hx, self.Hz, self.rng, self.samples, self.probs = Hx, Hz, rng, samples, probs
+        self.at, self.logicals = start, logicals
+
+    def sample(self, p, B, bits=False):
+        if self.samples is not None:
+            sl = slice(self.at, self.at + B)
+            self.at += B
+            return tuple(np.asarray(a)[sl].astype(np.uint8) for a in self.samples)
+        if self.probs is not None:
+            return sample_channel_vec(self.Hx, self.Hz, self.probs, B, self.rng)
+        return sample_channel(self.Hx, self.Hz, p, B, self.rng)
+
+    def count(self, sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ, acc):
+        if self.logicals is None:
+            c = count_outcomes(self.Hx, self.Hz, sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ)
+        else:
+            c = count_logical_outcomes(self.Hx, self.Hz, sy_z, sy_x, errX, errZ, eX, eZ, itX, itZ,
+                                       logicals=self.logicals)
+        for k in acc:
+            acc[k] += c[k]
+        return acc
+
+
+def _batch_loop(ch, count, acc, plan, p, my_shots, batch_size, show, finish=None):
+    """The unpipelined loop of both paths: draw a batch, decode its halves
+    (OSD inline: `finish` on the device, decode_batch's own on the host),
+    count into `acc` (device: an int64 tensor, nothing syncs; host: a dict of
+    ints). Returns acc."""
+    done = 0
+    while done < my_shots:
+        B = min(batch_size, my_shots - done)
+        sy_z, sy_x, errX, errZ = ch.sample(p, B, bits=plan.dec.packed)
+        rX, rZ = _decode_pair(plan, sy_z, sy_x, finish)
+        acc = count(sy_z, sy_x, errX, errZ, rX.ehat, rZ.ehat, rX.iters, rZ.iters, acc)
+        done += B
+        show(done, acc)
+    return acc
+
+
+@dataclass
+class _Batch:
+    """A batch in flight in the pipelined loop."""
+    sy_z: object
+    sy_x: object
+    errX: object
+    errZ: object
+    rX: object
+    rZ: object
+    staged: object = None        # decoders.osd_device_stage's result, once the batch's OSD is queued
+    orders: object = None        # the worker thread's future of its NumPy orders
+
+
+def _pipelined_loop(ch, count, acc, plan, p, my_shots, batch_size, osd_flags, show):
+    """Two-stage pipeline over batches: the host computes batch b-1's OSD
+    reliability orders (NumPy, the shots the device order leaves) while the
+    GPU runs batch b's decode and device OSD; counters accumulate on the device
+    (one sync per batch, in the OSD staging; none without OSD until the end).
+    `osd_flags` collects the IndexError flags, checked once at the end."""
+    Hz, Hx = plan.halves[0].H, plan.halves[1].H
+    osd = plan.dec.osd
+    done = 0
+    pending = None
+    phase = 0
+    stage_first = False                            # the last batch had device-ordered OSD shots
+    tail_min = max(1, batch_size // TAIL_DIV)
+    osd_frac = 0.0                                 # OSD shots / half-shots of the last staged batch
+
+    def stage(b):
+        """Queue b's device OSD (it waits for b's decode) and hand its NumPy
+        orders to the worker thread."""
+        nonlocal phase
+        b.staged = decoders.osd_device_stage([(Hz, b.sy_z, b.rX), (Hx, b.sy_x, b.rZ)], slot0=2 * phase, order=osd)
+        b.orders = _host_worker().submit(_host_orders_on, ch.dev, b.staged)
+        phase ^= 1
+
+    while done < my_shots or pending is not None:
+        cur = None
+        if done < my_shots:
+            rem = my_shots - done
+            B = min(batch_size, rem)
+            if osd >= 0 and osd_frac > 0.2 and tail_min < rem <= batch_size:
+                # the last batch's NumPy orders have no next batch to hide
+                # behind (the GPU idles until they finish): when OSD is a
+                # large share of the work, halve the tail batches, so the
+                # final wait is a small batch's (LP118_2 MS-L p = 0.1:
+                # +5 %; at low p the extra batches cost more than the
+                # short drain saves). Shots keep their indices (the
+                # sampler's counter): counters do not depend on batching.
+                B = max(tail_min, rem // 2)
+            sy_z, sy_x, errX, errZ = ch.sample(p, B, bits=plan.dec.packed)
+            cur = _Batch(sy_z, sy_x, errX, errZ, *_decode_pair(plan, sy_z, sy_x))
+            done += B
+        if cur is not None and osd >= 0 and stage_first:
+            # many OSD shots: this batch's device OSD is queued first
+            # (staging waits for its decode), so the GPU runs it while the
+            # worker thread finishes the previous batch's NumPy orders
+            stage(cur)
+        if pending is not None:
+            b = pending
+            items = [(Hz, b.sy_z, b.rX), (Hx, b.sy_x, b.rZ)]
+            if osd >= 0:                               # (decoders.py:179-180), on the GPU
+                # the status-2 shots' NumPy orders were computed on the
+                # worker thread while the GPU decoded this batch
+                decoders.osd_device_finish(items, b.staged, osd, host=b.orders.result())
+                decoders.osd_status_check(items, defer=osd_flags)
+            count(b.sy_z, b.sy_x, b.errX, b.errZ, b.rX.ehat, b.rZ.ehat, b.rX.iters, b.rZ.iters, acc)
+        if cur is not None and osd >= 0 and cur.staged is None:
+            # few OSD shots: stage (and sync on) this batch's decode now
+            stage(cur)
+        if cur is not None and osd >= 0:
+            stage_first = decoders.osd_staged_on_device(cur.staged)
+            osd_frac = sum(int(sg[0].numel()) for sg in cur.staged if sg is not None) / (2.0 * B)
+        pending = cur
+        if cur is not None:
+            show(done)
 
 
 def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decType: str = "MS",
@@ -485,252 +802,47 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
     take no prior: only the sampling changes. Not combinable with correlated=;
     decType "RELAY" needs uniform marginals in both halves (ValueError).
     """
-    n_ = Hx.shape[1]
-    probs = None
-    hard_ = decType in _lib.HARD_ALGOS
-    pX_, pkwX = p / 3, {}                          # decode_batch's p and prior= of each half
-    pZ_, pkwZ = p / 3, {}
-    if channel_weights is not None:
-        if correlated is not None:
-            raise ValueError("channel_weights cannot be combined with correlated= (its second-half prior "
-                             "assumes depolarizing noise)")
-        probs = channel_probs(p, channel_weights, n_)
-        w_ = _weights_3n(channel_weights, n_)
-        pX_, pkwX = _half_prior(float(p) * (w_[0] + w_[1]), hard_)
-        pZ_, pkwZ = _half_prior(float(p) * (w_[2] + w_[1]), hard_)
-        if decType == "RELAY" and (pkwX or pkwZ):
-            raise ValueError("decType RELAY takes one scalar prior per half: channel_weights must give every "
-                             "qubit the same marginals")
-    if decType == "RELAY":
-        if OSDorder >= 0:
-            raise ValueError("decType RELAY has no OSD step (OSDorder must be < 0)")
-        if correlated is not None:
-            raise ValueError("decType RELAY cannot be combined with correlated=")
-        if decSchedule != "F":
-            raise ValueError("decType RELAY runs the flooding schedule only (decSchedule 'F')")
-        if int(relay_legs) < 1 or int(relay_leg_iters) < 1 or int(relay_sols) < 1 or int(decIterations) < 1:
-            raise ValueError("relay_legs, relay_leg_iters, relay_sols and decIterations must be >= 1")
-        lo_, hi_ = (float(x) for x in relay_gamma_range)
-        if not (np.isfinite([lo_, hi_, float(relay_gamma0)]).all() and lo_ <= hi_):
-            raise ValueError("relay_gamma0 and relay_gamma_range (lo <= hi) must be finite")
-    if rngSeed is not None:
-        np.random.seed(rngSeed)                    # reference side effect (:187-188)
-    dist, rank, world = _dist()
-    m_z = Hz.shape[0] if Hz.size else 0
-    m_x = Hx.shape[0] if Hx.size else 0
-    n = Hx.shape[1]
-    if Hz.size and Hz.shape[1] != n:
-        raise ValueError("Hx and Hz must have the same number of columns (physical qubits).")
-    layersX, layersZ = select_layers(Hx, Hz, decSchedule)   # raises ValueError (:236)
-    if decType not in _lib.ALGO and decType != "RELAY":
-        raise ValueError("Unrecognized decoder type.")
-    rkwX, rkwZ = {}, {}                            # decode_batch's relay= of each half
-    if decType == "RELAY":
-        T_ = [int(decIterations)] + [int(relay_leg_iters)] * (int(relay_legs) - 1)
-        grng = np.random.default_rng(relay_seed)   # one generator: the Hz-decoded half draws first
-        for kw_ in (rkwX, rkwZ):
-            G_ = np.empty((len(T_), n), np.float64)
-            G_[0] = relay_gamma0
-            G_[1:] = grng.uniform(lo_, hi_, (len(T_) - 1, n))
-            kw_["relay"] = decoders.RelayConfig(T_, G_, int(relay_sols))
-    if correlated not in (None, "XZ", "ZX"):
-        raise ValueError("correlated must be 'XZ', 'ZX' or None")
-    if correlated is not None:
-        if decType in _lib.HARD_ALGOS:
-            raise ValueError(f"correlated decoding needs a prior: {decType} is a hard-decision decoder")
-        if not (0.0 < float(correlated_q1) <= 0.5):
-            raise ValueError("correlated_q1 must lie in (0, 0.5]")
-        q1 = float(correlated_q1)
-        p0c = (p / 3) / (1 - 2 * p / 3)            # P(second component | no first component)
-    # the reference never passes OSDorder to BP_decoder (:281-282); NG and BF
-    # get (H, syndrome) alone (:270-276): no prior, no decIterations (BF runs
-    # its default 50), no OSD
-    osd = OSDorder if decType == "MS" else -1
-    if decType in _lib.HARD_ALGOS:
-        decIterations = 50
-    lpX, lrX = pack_layers(layersX, Hz.shape[0])    # X half decodes Hz with Hx's layers
-    lpZ, lrZ = pack_layers(layersZ, Hx.shape[0])    # Z half decodes Hx with Hz's layers
-
-    # this rank's contiguous share of the shots
-    my_shots = shots // world + (1 if rank < shots % world else 0)
-    my_start = rank * (shots // world) + min(rank, shots % world)
-    seed = None if rngSeed is None else [int(rngSeed), int(rank)]
-    rng = np.random.default_rng(seed)
+    plan = _plan(Hx, Hz, p, decType, decIterations, decSchedule, OSDorder, rngSeed, samples, sampler, logical,
+                 correlated, correlated_q1,
+                 dict(legs=relay_legs, leg_iters=relay_leg_iters, sols=relay_sols, gamma0=relay_gamma0,
+                      gamma_range=relay_gamma_range, seed=relay_seed), channel_weights)
+    osd = plan.dec.osd
+    rank, my_shots, my_start, seed = _shard(shots, rngSeed)
     keys = COUNTER_KEYS + LOGICAL_KEYS if logical else COUNTER_KEYS
-    if logical:
-        from .logicals import css_logicals
-        pair_logicals = css_logicals(Hx, Hz)       # raises ValueError before any shot is drawn
-    tot = {k: 0 for k in keys}
-    t0 = time.time()
-    done = 0
-    if sampler not in (None, "device", "host"):
-        raise ValueError("sampler must be 'device', 'host' or None")
-    if samples is not None and sampler == "device":
-        raise ValueError("samples= decodes the given shots on the host path; it cannot be combined "
-                         "with sampler='device' (which draws its own Philox shots)")
-    use_dev = sampler == "device" or (sampler is None and samples is None and _device_ok()
-                                      and _channel_ok(Hx, Hz))
+    show = _progress(f"(p={p:5.2e})", my_shots, verbose and rank == 0, rates=not plan.use_dev)
     if batch_size is None:
         # shots per batch. Without OSD nothing syncs per batch, and 2^20-shot
         # batches amortise the per-batch host work (LP118_0 MS-F p = 0.01:
         # 107 -> 130 M shots/s vs 2^18); with OSD, 2^18 keeps the host's
         # reliability order of one batch overlapped with the next one's decode.
-        batch_size = ((1 << 20) if osd < 0 else (1 << 18)) if use_dev else (1 << 16)
-    if use_dev:
+        batch_size = ((1 << 20) if osd < 0 else (1 << 18)) if plan.use_dev else (1 << 16)
+    if plan.use_dev:
         import torch
         dev = torch.device("cuda", torch.cuda.current_device())
-        ch = DeviceChannel(Hx, Hz, dev, np.random.SeedSequence(seed).generate_state(1, np.uint64)[0])
-        if probs is not None:
-            ch.set_probs(probs)
-    if use_dev and correlated is not None:
-        # Correlated mode: the second half's decode waits for the first half's
-        # final estimate, so each batch runs decode, (OSD,) decode, (OSD,)
-        # count in stream order. Without OSD the mask is the first decode's
-        # bit-packed estimate tensor itself: no kernel, copy or sync between.
+        ch = DeviceChannel(Hx, Hz, dev, _device_key(seed))
+        if plan.probs is not None:
+            ch.set_probs(plan.probs)
+        count = ch.count_logical_device if logical else ch.count_device
         acc = torch.zeros(len(keys), dtype=torch.int64, device=dev)
-        count_dev = ch.count_logical_device if logical else ch.count_device
-        osd_flags = []
-        while done < my_shots:
-            B = min(batch_size, my_shots - done)
-            packed = osd < 0
-            sy_z, sy_x, errX, errZ = ch.sample(p, B, bits=packed)
-            halves = [(Hz, sy_z, lpX, lrX), (Hx, sy_x, lpZ, lrZ)]
-            if correlated == "ZX":
-                halves.reverse()
-            res, mask = [], None
-            for H_, sy_, lp_, lr_ in halves:
-                kw = {} if mask is None else {"prior_mask": mask, "p_masked": q1}
-                r_ = decoders.decode_batch(H_, sy_, p / 3 if mask is None else p0c, decIterations, algo=decType,
-                                           want_post=osd >= 0, layer_ptr=lp_, layer_rows=lr_, ehat_bits=packed, **kw)
-                if osd >= 0:                           # (decoders.py:179-180) before the estimate is used
-                    items = [(H_, sy_, r_)]
-                    decoders.osd_device_finish(items, decoders.osd_device_stage(items, order=osd), osd)
-                    decoders.osd_status_check(items, defer=osd_flags)
-                res.append(r_)
-                mask = r_.ehat
-            rX, rZ = res if correlated == "XZ" else res[::-1]
-            count_dev(sy_z, sy_x, errX, errZ, rX.ehat, rZ.ehat, rX.iters, rZ.iters, acc)
-            done += B
-            if verbose and rank == 0:
-                print(f"\r(p={p:5.2e}) Decoding block n. {done:3}/{my_shots:4}... "
-                      f"({done / (time.time() - t0):.3g} shots/s)", end="", flush=True)
-        decoders.osd_status_raise(osd_flags)
-        tot = dict(zip(keys, (int(x) for x in acc.cpu().tolist())))
-    elif use_dev:
-        # Two-stage pipeline over batches: the host computes batch b-1's OSD
-        # reliability orders (NumPy, the shots the device order leaves) while
-        # the GPU runs batch b's decode and device OSD;
-        # counters accumulate on the device (one sync per batch, in the OSD
-        # staging; none without OSD until the end).
-        acc = torch.zeros(len(keys), dtype=torch.int64, device=dev)
-        count_dev = ch.count_logical_device if logical else ch.count_device
-        pending = None
-        phase = 0
         osd_flags = []                             # IndexError flags, checked once at the end
-        stage_first = False                        # the last batch had device-ordered OSD shots
-        tail_min = max(1, batch_size // TAIL_DIV)
-        osd_frac = 0.0                             # OSD shots / half-shots of the last staged batch
-        while done < my_shots or pending is not None:
-            cur = None
-            if done < my_shots:
-                rem = my_shots - done
-                B = min(batch_size, rem)
-                if osd >= 0 and osd_frac > 0.2 and tail_min < rem <= batch_size:
-                    # the last batch's NumPy orders have no next batch to hide
-                    # behind (the GPU idles until they finish): when OSD is a
-                    # large share of the work, halve the tail batches, so the
-                    # final wait is a small batch's (LP118_2 MS-L p = 0.1:
-                    # +5 %; at low p the extra batches cost more than the
-                    # short drain saves). Shots keep their indices (the
-                    # sampler's counter): counters do not depend on batching.
-                    B = max(tail_min, rem // 2)
-                # bit-packed syndromes and estimates (one bit per check / qubit
-                # in HBM) unless OSD needs byte rows of the failing shots
-                packed = osd < 0
-                sy_z, sy_x, errX, errZ = ch.sample(p, B, bits=packed)
-                want_post = osd >= 0
-                rX = decoders.decode_batch(Hz, sy_z, pX_, decIterations, algo=decType, want_post=want_post,
-                                           layer_ptr=lpX, layer_rows=lrX, ehat_bits=packed, **rkwX, **pkwX)
-                rZ = decoders.decode_batch(Hx, sy_x, pZ_, decIterations, algo=decType, want_post=want_post,
-                                           layer_ptr=lpZ, layer_rows=lrZ, ehat_bits=packed, **rkwZ, **pkwZ)
-                cur = [sy_z, sy_x, errX, errZ, rX, rZ, None]
-                done += B
-            if cur is not None and osd >= 0 and stage_first:
-                # many OSD shots: this batch's device OSD is queued first
-                # (staging waits for its decode), so the GPU runs it while the
-                # worker thread finishes the previous batch's NumPy orders
-                cur[6] = decoders.osd_device_stage([(Hz, cur[0], cur[4]), (Hx, cur[1], cur[5])],
-                                                   slot0=2 * phase, order=osd)
-                cur.append(_host_worker().submit(_host_orders_on, dev, cur[6]))
-                phase ^= 1
-            if pending is not None:
-                sy_z_, sy_x_, errX_, errZ_, rX_, rZ_, staged = pending[:7]
-                items = [(Hz, sy_z_, rX_), (Hx, sy_x_, rZ_)]
-                if osd >= 0:                           # (decoders.py:179-180), on the GPU
-                    # the status-2 shots' NumPy orders were computed on the
-                    # worker thread while the GPU decoded this batch
-                    decoders.osd_device_finish(items, staged, osd, host=pending[7].result())
-                    decoders.osd_status_check(items, defer=osd_flags)
-                count_dev(sy_z_, sy_x_, errX_, errZ_, rX_.ehat, rZ_.ehat, rX_.iters, rZ_.iters, acc)
-            if cur is not None and osd >= 0 and cur[6] is None:
-                # few OSD shots: stage (and sync on) this batch's decode now
-                cur[6] = decoders.osd_device_stage([(Hz, cur[0], cur[4]), (Hx, cur[1], cur[5])],
-                                                   slot0=2 * phase, order=osd)
-                cur.append(_host_worker().submit(_host_orders_on, dev, cur[6]))
-                phase ^= 1
-            if cur is not None and osd >= 0:
-                stage_first = decoders.osd_staged_on_device(cur[6])
-                osd_frac = sum(int(sg[0].numel()) for sg in cur[6] if sg is not None) / (2.0 * B)
-            pending = cur
-            if verbose and rank == 0 and cur is not None:
-                print(f"\r(p={p:5.2e}) Decoding block n. {done:3}/{my_shots:4}... "
-                      f"({done / (time.time() - t0):.3g} shots/s)", end="", flush=True)
+        if plan.dec.masked is None:
+            _pipelined_loop(ch, count, acc, plan, p, my_shots, batch_size, osd_flags, show)
+        else:
+            # Correlated mode: the second half's decode waits for the first half's
+            # final estimate, so each batch runs decode, (OSD,) decode, (OSD,)
+            # count in stream order. Without OSD the mask is the first decode's
+            # bit-packed estimate tensor itself: no kernel, copy or sync between.
+            def osd_now(H, syn, r):
+                items = [(H, syn, r)]
+                decoders.osd_device_finish(items, decoders.osd_device_stage(items, order=osd), osd)
+                decoders.osd_status_check(items, defer=osd_flags)
+            _batch_loop(ch, count, acc, plan, p, my_shots, batch_size, show, osd_now if osd >= 0 else None)
         decoders.osd_status_raise(osd_flags)
         tot = dict(zip(keys, (int(x) for x in acc.cpu().tolist())))
-    while not use_dev and done < my_shots:
-        B = min(batch_size, my_shots - done)
-        if samples is not None:
-            sl = slice(my_start + done, my_start + done + B)
-            sy_z, sy_x, errX, errZ = (np.asarray(a)[sl].astype(np.uint8) for a in samples)
-        elif probs is not None:
-            sy_z, sy_x, errX, errZ = sample_channel_vec(Hx, Hz, probs, B, rng)
-        else:
-            sy_z, sy_x, errX, errZ = sample_channel(Hx, Hz, p, B, rng)
-        if correlated is None:
-            rX = decoders.decode_batch(Hz, sy_z, pX_, decIterations, algo=decType, osd_order=osd,
-                                       layer_ptr=lpX, layer_rows=lrX, **rkwX, **pkwX)
-            rZ = decoders.decode_batch(Hx, sy_x, pZ_, decIterations, algo=decType, osd_order=osd,
-                                       layer_ptr=lpZ, layer_rows=lrZ, **rkwZ, **pkwZ)
-        else:
-            halves = [(Hz, sy_z, lpX, lrX), (Hx, sy_x, lpZ, lrZ)]
-            if correlated == "ZX":
-                halves.reverse()
-            (H1, s1, lp1, lr1), (H2, s2, lp2, lr2) = halves
-            r1 = decoders.decode_batch(H1, s1, p / 3, decIterations, algo=decType, osd_order=osd,
-                                       layer_ptr=lp1, layer_rows=lr1)
-            r2 = decoders.decode_batch(H2, s2, p0c, decIterations, algo=decType, osd_order=osd,
-                                       layer_ptr=lp2, layer_rows=lr2, prior_mask=r1.ehat, p_masked=q1)
-            rX, rZ = (r1, r2) if correlated == "XZ" else (r2, r1)
-        if logical:
-            c = count_logical_outcomes(Hx, Hz, sy_z, sy_x, errX, errZ, rX.ehat, rZ.ehat, rX.iters, rZ.iters,
-                                       logicals=pair_logicals)
-        else:
-            c = count_outcomes(Hx, Hz, sy_z, sy_x, errX, errZ, rX.ehat, rZ.ehat, rX.iters, rZ.iters)
-        for k in tot:
-            tot[k] += c[k]
-        done += B
-        if verbose and rank == 0:
-            print(f"\r(p={p:5.2e}) Decoding block n. {done:3}/{my_shots:4}... "
-                  f"Dec. failure rates (X,Z): {tot['DecFailures_X'] / done:.2e}, "
-                  f"{tot['DecFailures_Z'] / done:.2e} ({done / (time.time() - t0):.3g} shots/s)",
-                  end="", flush=True)
-    if dist is not None and world > 1:
-        import torch
-        backend = dist.get_backend()
-        dev = torch.device("cuda", torch.cuda.current_device()) if backend == "nccl" else torch.device("cpu")
-        t = torch.tensor([tot[k] for k in keys], dtype=torch.int64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)   # the sweep's only collective (six values, nine with logical)
-        tot = dict(zip(keys, (int(v) for v in t.cpu().tolist())))
+    else:
+        ch = _HostChannel(Hx, Hz, np.random.default_rng(seed), samples, plan.probs, my_start, plan.logicals)
+        tot = _batch_loop(ch, ch.count, {k: 0 for k in keys}, plan, p, my_shots, batch_size, show)
+    tot = _all_reduce(tot, keys)
     if verbose and rank == 0:
         print()
     res = {
@@ -758,7 +870,6 @@ class DevicePhenomHalf:
 
     def __init__(self, H, L, rounds, device, seed, shot0=0):
         import torch
-        from . import spacetime
         self.torch = torch
         self.dev = torch.device(device)
         self.T = int(rounds)
@@ -771,9 +882,6 @@ class DevicePhenomHalf:
         self.seed = int(seed) & ((1 << 64) - 1)
         self.shot = int(shot0)
 
-    def _stream(self):
-        return self.torch.cuda.current_stream(self.dev).cuda_stream
-
     def sample(self, p_data, q, B, bits=False, want_fired=False):
         """(det, E) of the next B shots: det uint8 [B, M] (bits: int64
         [B, ceil(M/64)]), E int64 [B, ceil(n/64)]; with want_fired also the
@@ -784,8 +892,7 @@ class DevicePhenomHalf:
         E = torch.empty((B, self.W), dtype=torch.int64, device=self.dev)
         fired = torch.empty((B, self.NW), dtype=torch.int64, device=self.dev) if want_fired else None
         _lib.phenom_sample(self.code, self.T, p_data, q, self.seed, self.shot, B, det.data_ptr(),
-                           _lib.FMT_BITS if bits else _lib.FMT_BYTES, E.data_ptr(),
-                           fired.data_ptr() if want_fired else None, self._stream())
+                           _fmt(bits), E.data_ptr(), fired.data_ptr() if want_fired else None, _stream(self.dev))
         self.shot += int(B)
         return (det, E, fired) if want_fired else (det, E)
 
@@ -813,12 +920,29 @@ class DevicePhenomHalf:
         flips = torch.empty((B, self.table.kw), dtype=torch.int64, device=self.dev) if want_shots else None
         resid = torch.empty((B, self.W), dtype=torch.int64, device=self.dev) if want_shots else None
         P = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
-        F = lambda b: _lib.FMT_BITS if b else _lib.FMT_BYTES  # noqa: E731
-        _lib.phenom_count(self.code, self.table, self.T, B, det.data_ptr(), F(d_bits), E.data_ptr(), ehat.data_ptr(),
-                          F(e_bits), iters.data_ptr(), acc.data_ptr(), P(cls), P(flips), P(resid), self._stream())
+        _lib.phenom_count(self.code, self.table, self.T, B, det.data_ptr(), _fmt(d_bits), E.data_ptr(),
+                          ehat.data_ptr(), _fmt(e_bits), iters.data_ptr(), acc.data_ptr(), P(cls), P(flips), P(resid),
+                          _stream(self.dev))
         if want_shots:
             return acc, cls, flips, resid
         return (acc, cls) if want_class else acc
+
+
+class _HostPhenomHalf:
+    """DevicePhenomHalf's two loop operations on the host (the NumPy twins in
+    spacetime.py): sample() draws from `rng`, which the halves share, and
+    count_device() adds to an int64 [4] NumPy array."""
+
+    def __init__(self, H, L, rounds, rng):
+        self.H, self.L, self.T, self.rng = H, L, rounds, rng
+
+    def sample(self, p_data, q, B, bits=False):
+        return spacetime.sample_phenomenological(self.H, self.T, p_data, q, B, self.rng)
+
+    def count_device(self, det, E, ehat, iters, acc, want_class=True):
+        c, (cls, _, _) = spacetime.count_phenomenological(self.H, self.L, self.T, det, E, ehat, iters, want_shots=True)
+        acc += (c["failures"], c["logical_errors"], c["successes"], c["iterations"])
+        return acc, cls
 
 
 def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float, rounds: int, shots: int = 1000,
@@ -866,7 +990,6 @@ def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float
     ValueError: decType RELAY / NG / BF, correlated= and channel_weights= (not
     defined for this model), probabilities outside [0, 1), rounds < 1, a pair
     that is not CSS."""
-    from . import spacetime
     from .logicals import css_logicals
     for k_ in unsupported:
         if k_ in ("correlated", "channel_weights", "correlated_q1", "logical", "samples"):
@@ -894,86 +1017,53 @@ def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float
     p_data = 2.0 * float(p) / 3.0
     q = float(q)
     osd = OSDorder if decType == "MS" else -1      # as simulate_p
-    dist, rank, world = _dist()
-    my_shots = shots // world + (1 if rank < shots % world else 0)
-    seed = None if rngSeed is None else [int(rngSeed), int(rank)]
+    rank, my_shots, _, seed = _shard(shots, rngSeed)
     use_dev = sampler == "device" or (sampler is None and _device_ok())
     if batch_size is None:
         # posteriors (OSD) and byte rows cost 9 N bytes per half-shot
         batch_size = ((1 << 18) if osd < 0 else (1 << 14)) if use_dev else (1 << 14)
+    dec = _Decode(decType, decIterations, osd, *_path_kw(use_dev, osd))
     halves = []                                    # X half: (Hz, Lz); Z half: (Hx, Lx)
-    for H_, L_ in ((Hz, Lz), (Hx, Lx)):
-        m_ = H_.shape[0]
-        Hst = spacetime.spacetime_matrix(H_, T)
+    for H, L in ((Hz, Lz), (Hx, Lx)):
+        Hst = spacetime.spacetime_matrix(H, T)
         layers = None if decSchedule == "F" else layerize(Hst, serial=decSchedule == "S")
         lp, lr = pack_layers(layers, Hst.shape[0])
-        pd, pkw = _half_prior(spacetime.spacetime_prior(n, m_, T, p_data, q), False)
-        halves.append(dict(H=H_, L=L_, Hst=Hst, lp=lp, lr=lr, p=pd, pkw=pkw))
-    tot = {k: 0 for k in PHENOM_KEYS}
-    t0 = time.time()
-    done = 0
-
-    def progress():
-        if verbose and rank == 0:
-            print(f"\r(p={p:5.2e}, q={q:5.2e}, T={T}) Decoding block n. {done:3}/{my_shots:4}... "
-                  f"({done / max(time.time() - t0, 1e-9):.3g} shots/s)", end="", flush=True)
-
+        halves.append(_Half(Hst, lp, lr, *_half_prior(spacetime.spacetime_prior(n, H.shape[0], T, p_data, q), False),
+                            (H, L)))
+    show = _progress(f"(p={p:5.2e}, q={q:5.2e}, T={T})", my_shots, verbose and rank == 0)
     if use_dev:
         import torch
         dev = torch.device("cuda", torch.cuda.current_device())
-        key = int(np.random.SeedSequence(seed).generate_state(1, np.uint64)[0])
-        for h, k_ in zip(halves, (key, key ^ PHENOM_Z_KEY)):
-            h["ch"] = DevicePhenomHalf(h["H"], h["L"], T, dev, k_)
-            h["acc"] = torch.zeros(4, dtype=torch.int64, device=dev)
+        key = _device_key(seed)
+        src = [DevicePhenomHalf(*h.code, T, dev, k) for h, k in zip(halves, (key, key ^ PHENOM_Z_KEY))]
         for h in halves:
-            if h["pkw"]:
+            if h.kw:
                 # the vector-prior kernel's limits are met when its launch is
                 # planned: one all-zero detector row per half, so a shape past
                 # them is refused (NotImplementedError) before any shot is drawn
-                decoders.decode_batch(h["Hst"], torch.zeros((1, h["Hst"].shape[0]), dtype=torch.uint8, device=dev),
-                                      None, 1, algo=decType, layer_ptr=h["lp"], layer_rows=h["lr"], **h["pkw"])
-        both = torch.zeros(1, dtype=torch.int64, device=dev)
-        packed = osd < 0                           # bit-packed detectors and estimates unless OSD reads byte rows
-        while done < my_shots:
-            B = min(batch_size, my_shots - done)
-            cls = []
-            for h in halves:
-                det, E = h["ch"].sample(p_data, q, B, bits=packed)
-                r = decoders.decode_batch(h["Hst"], det, h["p"], decIterations, algo=decType, want_post=osd >= 0,
-                                          layer_ptr=h["lp"], layer_rows=h["lr"], ehat_bits=packed, **h["pkw"])
-                if osd >= 0:
-                    decoders.apply_osd_device(h["Hst"], det, r, osd)
-                cls.append(h["ch"].count_device(det, E, r.ehat, r.iters, h["acc"], want_class=True)[1])
-            both += ((cls[0] | cls[1]) == 0).sum()
-            done += B
-            progress()
-        aX, aZ = (h["acc"].cpu().tolist() for h in halves)
-        tot = dict(zip(PHENOM_KEYS, (int(v) for v in (aX[0], aZ[0], aX[1], aZ[1], aX[3], aZ[3], int(both.cpu())))))
+                _decode_half(h, torch.zeros((1, h.H.shape[0]), dtype=torch.uint8, device=dev),
+                             dec._replace(iters=1, kw={}))
+        accs = [torch.zeros(k, dtype=torch.int64, device=dev) for k in (4, 4, 1)]
     else:
-        rng = np.random.default_rng(seed)
-        while done < my_shots:
-            B = min(batch_size, my_shots - done)
-            cls = []
-            for h, sfx in zip(halves, "XZ"):
-                det, E = spacetime.sample_phenomenological(h["H"], T, p_data, q, B, rng)
-                r = decoders.decode_batch(h["Hst"], det, h["p"], decIterations, algo=decType, osd_order=osd,
-                                          layer_ptr=h["lp"], layer_rows=h["lr"], **h["pkw"])
-                c, (cl, _, _) = spacetime.count_phenomenological(h["H"], h["L"], T, det, E, r.ehat, r.iters,
-                                                                 want_shots=True)
-                tot["DecFailures_" + sfx] += c["failures"]
-                tot["logicalErrors_" + sfx] += c["logical_errors"]
-                tot["nIterAcc" + sfx] += c["iterations"]
-                cls.append(cl)
-            tot["decSuccessLogical"] += int(((cls[0] | cls[1]) == 0).sum())
-            done += B
-            progress()
-    if dist is not None and world > 1:
-        import torch
-        backend = dist.get_backend()
-        dev = torch.device("cuda", torch.cuda.current_device()) if backend == "nccl" else torch.device("cpu")
-        t = torch.tensor([tot[k] for k in PHENOM_KEYS], dtype=torch.int64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)   # the only collective: seven values
-        tot = dict(zip(PHENOM_KEYS, (int(v) for v in t.cpu().tolist())))
+        rng = np.random.default_rng(seed)          # one generator: the X half draws first in every batch
+        src = [_HostPhenomHalf(*h.code, T, rng) for h in halves]
+        accs = [np.zeros(k, np.int64) for k in (4, 4, 1)]
+    both = accs[2]                                 # shots with both halves class 0
+    done = 0
+    while done < my_shots:
+        B = min(batch_size, my_shots - done)
+        cls = []
+        for h, s, acc in zip(halves, src, accs):    # (the two halves and their accumulators)
+            det, E = s.sample(p_data, q, B, bits=dec.packed)
+            r = _decode_half(h, det, dec)
+            if use_dev and osd >= 0:
+                decoders.apply_osd_device(h.H, det, r, osd)
+            cls.append(s.count_device(det, E, r.ehat, r.iters, acc, want_class=True)[1])
+        both += ((cls[0] | cls[1]) == 0).sum()
+        done += B
+        show(done)
+    aX, aZ, ok = (a.cpu().tolist() if use_dev else a.tolist() for a in accs)
+    tot = _all_reduce(dict(zip(PHENOM_KEYS, (aX[0], aZ[0], aX[1], aZ[1], aX[3], aZ[3], ok[0]))), PHENOM_KEYS)
     if verbose and rank == 0:
         print()
     res = dict(tot)
@@ -1049,6 +1139,27 @@ def _save_results(path, meta, done):
     os.replace(tmp, path)                      # atomic: a killed run leaves the last good file
 
 
+def _sweep(p, meta, resultsFile, on_point, rank, point):
+    """The resumable p-sweep: point(pT) for every pT the results file does not
+    hold yet (its run parameters must equal `meta`), timed for on_point; rank 0
+    saves the file after each. Returns every point's result, in p's order."""
+    done = _load_results(resultsFile, meta)
+    results = []
+    for pT in p:
+        if float(pT) in done:
+            results.append(done[float(pT)])
+            continue
+        t0 = time.perf_counter()
+        r = point(pT)
+        if on_point is not None:
+            on_point(pT, r, time.perf_counter() - t0)
+        results.append(r)
+        done[float(pT)] = r
+        if resultsFile and rank == 0:
+            _save_results(resultsFile, meta, done)
+    return results
+
+
 def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS",
              decIterations: int = 99, decSchedule: str = "F", OSDorder: int = -1,
              rngSeed: Optional[int] = None, *, batch_size: Optional[int] = None, verbose: bool = True,
@@ -1104,23 +1215,10 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
         meta = {"Hx": HxFile, "Hz": HzFile, "shots": shots, "decType": decType, "decIterations": decIterations,
                 "decSchedule": decSchedule, "OSDorder": OSDorder, "rngSeed": rngSeed, "world": world,
                 "sampler": sampler, "rounds": int(rounds), "q": None if meas_error is None else float(meas_error)}
-        done = _load_results(resultsFile, meta)
-        results = []
-        for pT in p:
-            if float(pT) in done:
-                results.append(done[float(pT)])
-                continue
-            t0 = time.perf_counter()
-            r = simulate_phenomenological(Hx, Hz, pT, 2 * pT / 3 if meas_error is None else meas_error, rounds,
-                                          shots=shots, decType=decType, decIterations=decIterations,
-                                          decSchedule=decSchedule, OSDorder=OSDorder, rngSeed=rngSeed,
-                                          batch_size=batch_size, sampler=sampler, verbose=verbose)
-            if on_point is not None:
-                on_point(pT, r, time.perf_counter() - t0)
-            results.append(r)
-            done[float(pT)] = r
-            if resultsFile and rank == 0:
-                _save_results(resultsFile, meta, done)
+        results = _sweep(p, meta, resultsFile, on_point, rank, lambda pT: simulate_phenomenological(
+            Hx, Hz, pT, 2 * pT / 3 if meas_error is None else meas_error, rounds, shots=shots, decType=decType,
+            decIterations=decIterations, decSchedule=decSchedule, OSDorder=OSDorder, rngSeed=rngSeed,
+            batch_size=batch_size, sampler=sampler, verbose=verbose))
         if rank == 0:
             print(format_phenomenological_results(p, results, shots))
         return results if return_results else None
@@ -1156,23 +1254,9 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
     if "channel_weights" in extra:
         for pT in p:                          # every point is checked before the first one runs
             channel_probs(pT, extra["channel_weights"], Hx.shape[1])
-    done = _load_results(resultsFile, meta)
-    results = []
-    for pT in p:
-        if float(pT) in done:
-            results.append(done[float(pT)])
-            continue
-        t0 = time.perf_counter()
-        r = simulate_p(Hx, Hz, p=pT, shots=shots, rngSeed=rngSeed, decType=decType,
-                       decIterations=decIterations, decSchedule=decSchedule,
-                       OSDorder=OSDorder, batch_size=batch_size, verbose=verbose,
-                       sampler=sampler, **extra)
-        if on_point is not None:
-            on_point(pT, r, time.perf_counter() - t0)
-        results.append(r)
-        done[float(pT)] = r
-        if resultsFile and rank == 0:
-            _save_results(resultsFile, meta, done)
+    results = _sweep(p, meta, resultsFile, on_point, rank, lambda pT: simulate_p(
+        Hx, Hz, p=pT, shots=shots, rngSeed=rngSeed, decType=decType, decIterations=decIterations,
+        decSchedule=decSchedule, OSDorder=OSDorder, batch_size=batch_size, verbose=verbose, sampler=sampler, **extra))
     if rank == 0:
         print(format_results(p, results, shots))
         if logical:
