@@ -64,6 +64,8 @@ class DecodeResult:
     post: object          # float64 [B, n] or None
     flags: object         # int32 [B]
     info: object = None   # algo "RELAY": int32 [B, 2] (solutions found, leg of the one returned or -1)
+    osd_status: object = None   # after the device OSD: int32 per OSD shot, 1 = the reference's IndexError case
+    osd_host_order: int = 0     # after the device OSD: shots whose reliability order the host computed
 
     @property
     def converged(self):
@@ -194,105 +196,24 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
         layer_ptr, layer_rows = pack_layers(layers, m)
     if int(max_iter) < 1:
         raise ValueError("max_iter must be >= 1")
-    if _is_torch(syndromes):
-        import torch
-        dev = syndromes.device
-        code = _lib.code_for(H, dev.index)
-        sched = code.schedule(layer_ptr, layer_rows)
-        syn = syndromes.contiguous()
-        wm, wn = (m + 63) // 64, (n + 63) // 64
-        if syn.dim() == 2 and syn.dtype == torch.uint8 and syn.shape[1] == m:
-            syn_fmt = _lib.FMT_BYTES
-        elif syn.dim() == 2 and syn.dtype == torch.int64 and syn.shape[1] == wm:
-            syn_fmt = _lib.FMT_BITS
-        else:
-            raise ValueError(f"syndromes must be uint8 [B, {m}] or int64 words [B, {wm}]")
-        B = syn.shape[0]
-        mask_fmt = None
-        if prior_mask is not None:
-            if not (_is_torch(prior_mask) and prior_mask.device == dev and prior_mask.dim() == 2):
-                raise ValueError("prior_mask must be a 2-D tensor on the syndromes' device")
-            prior_mask = prior_mask.contiguous()
-            if prior_mask.dtype == torch.uint8 and tuple(prior_mask.shape) == (B, n):
-                mask_fmt = _lib.FMT_BYTES
-            elif prior_mask.dtype == torch.int64 and tuple(prior_mask.shape) == (B, wn):
-                mask_fmt = _lib.FMT_BITS
-            else:
-                raise ValueError(f"prior_mask must be uint8 [{B}, {n}] or int64 words [{B}, {wn}]")
-        e_shape, e_dtype = ((B, wn), torch.int64) if ehat_bits else ((B, n), torch.uint8)
-        if out is not None:
-            ehat, iters, flags, post = out.ehat, out.iters, out.flags, out.post if want_post else None
-            ok = (ehat.shape == e_shape and ehat.dtype == e_dtype and iters.shape == (B,) and
-                  iters.dtype == torch.int32 and flags.shape == (B,) and flags.dtype == torch.int32 and
-                  all(t.device == dev and t.is_contiguous() for t in (ehat, iters, flags)) and
-                  (not want_post or (post is not None and post.shape == (B, n) and
-                                     post.dtype == torch.float64 and post.device == dev and
-                                     post.is_contiguous())))
-            if not ok:
-                raise ValueError("out buffers do not match the batch (uint8 [B, n] or int64 [B, ceil(n/64)], "
-                                 "int32 [B], int32 [B], float64 [B, n] if want_post) on the syndromes' device")
-        else:
-            ehat = torch.empty(e_shape, dtype=e_dtype, device=dev)
-            iters = torch.empty(B, dtype=torch.int32, device=dev)
-            flags = torch.empty(B, dtype=torch.int32, device=dev)
-            post = torch.empty((B, n), dtype=torch.float64, device=dev) if want_post else None
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        e_fmt = _lib.FMT_BITS if ehat_bits else _lib.FMT_BYTES
-        post_p = post.data_ptr() if post is not None else None
-        if prior is not None:
-            _lib.check(_lib.lib.qldpc_decode_device_vprior(
-                code.handle, sched.handle, _lib.ALGO[algo], syn.data_ptr(), syn_fmt, B, code.prior(prior, eps).handle,
-                int(max_iter), float(beta), ehat.data_ptr(), e_fmt, iters.data_ptr(), post_p, flags.data_ptr(), st))
-        elif prior_mask is not None:
-            _lib.check(_lib.lib.qldpc_decode_device_prior(
-                code.handle, sched.handle, _lib.ALGO[algo], syn.data_ptr(), syn_fmt, B, float(p), float(p_masked),
-                prior_mask.data_ptr(), mask_fmt, int(max_iter), float(beta), float(eps), ehat.data_ptr(), e_fmt,
-                iters.data_ptr(), post_p, flags.data_ptr(), st))
-        else:
-            _lib.check(_lib.lib.qldpc_decode_device_ex(
-                code.handle, sched.handle, _lib.ALGO[algo], syn.data_ptr(), syn_fmt, B, float(p), int(max_iter),
-                float(beta), float(eps), ehat.data_ptr(), e_fmt, iters.data_ptr(), post_p, flags.data_ptr(), st))
-        return DecodeResult(ehat, iters, post, flags)
-
-    syn = np.ascontiguousarray(syndromes)
-    if syn.ndim != 2 or syn.shape[1] != m:
-        raise ValueError(f"syndromes must be [B, {m}]")
-    if syn.size and (syn.min() < 0 or syn.max() > 1):
-        raise ValueError("syndrome entries must be 0 or 1")
-    syn = syn.astype(np.uint8, copy=False)
-    B = syn.shape[0]
-    if prior_mask is not None:
-        if _is_torch(prior_mask):
-            raise ValueError("prior_mask must be a NumPy array on the host path (the syndromes are)")
-        prior_mask = np.ascontiguousarray(prior_mask)
-        if prior_mask.shape != (B, n):
-            raise ValueError(f"prior_mask must be [{B}, {n}]")
-        if prior_mask.size and (prior_mask.min() < 0 or prior_mask.max() > 1):
-            raise ValueError("prior_mask entries must be 0 or 1")
-        prior_mask = prior_mask.astype(np.uint8, copy=False)
-    code = _lib.code_for(H)
-    sched = code.schedule(layer_ptr, layer_rows)
-    ehat = np.zeros((B, n), np.uint8)
-    iters = np.zeros(B, np.int32)
-    flags = np.zeros(B, np.int32)
-    need_post = want_post or osd_order >= 0
-    post = np.zeros((B, n), np.float64) if need_post else None
+    host = not _is_torch(syndromes)
+    code, sched, res, ins, mask, outs, held = (_host_batch if host else _device_batch)(
+        H, syndromes, _lib.Code.schedule, (layer_ptr, layer_rows), want_post, osd=osd_order >= 0,
+        prior_mask=prior_mask, out=out, stream=stream, ehat_bits=ehat_bits)
+    L = _lib.lib
+    head = (code.handle, sched.handle, _lib.ALGO[algo])
     if prior is not None:
-        _lib.check(_lib.lib.qldpc_decode_host_vprior(
-            code.handle, sched.handle, _lib.ALGO[algo], _lib.ptr(syn), B, code.prior(prior, eps).handle,
-            int(max_iter), float(beta), _lib.ptr(ehat), _lib.ptr(iters), _lib.ptr(post), _lib.ptr(flags)))
+        _lib.check((L.qldpc_decode_host_vprior if host else L.qldpc_decode_device_vprior)(
+            *head, *ins, code.prior(prior, eps).handle, int(max_iter), float(beta), *outs))
     elif prior_mask is not None:
-        _lib.check(_lib.lib.qldpc_decode_host_prior(
-            code.handle, sched.handle, _lib.ALGO[algo], _lib.ptr(syn), B, float(p), float(p_masked),
-            _lib.ptr(prior_mask), int(max_iter), float(beta), float(eps), _lib.ptr(ehat), _lib.ptr(iters),
-            _lib.ptr(post), _lib.ptr(flags)))
+        _lib.check((L.qldpc_decode_host_prior if host else L.qldpc_decode_device_prior)(
+            *head, *ins, float(p), float(p_masked), *mask, int(max_iter), float(beta), float(eps), *outs))
     else:
-        _lib.check(_lib.lib.qldpc_decode_host(
-            code.handle, sched.handle, _lib.ALGO[algo], _lib.ptr(syn), B, float(p), int(max_iter),
-            float(beta), float(eps), _lib.ptr(ehat), _lib.ptr(iters), _lib.ptr(post), _lib.ptr(flags)))
-    res = DecodeResult(ehat, iters, post if want_post else None, flags)
-    if osd_order >= 0:
-        apply_osd(H, syn, ehat, post, flags, osd_order)
+        _lib.check((L.qldpc_decode_host if host else L.qldpc_decode_device_ex)(
+            *head, *ins, float(p), int(max_iter), float(beta), float(eps), *outs))
+    if host and osd_order >= 0:
+        syn, post = held[:2]
+        apply_osd(H, syn, res.ehat, post, res.flags, osd_order)
     return res
 
 
@@ -317,66 +238,14 @@ def _decode_batch_relay(H, syndromes, p, relay, layers, beta, eps, want_post, os
     G = np.asarray(relay.gammas, np.float64)
     if G.shape != (len(T), n):
         raise ValueError(f"relay.gammas must be float64 [{len(T)}, {n}] (one row per leg, one entry per variable)")
-    if _is_torch(syndromes):
-        import torch
-        dev = syndromes.device
-        code = _lib.code_for(H, dev.index)
-        rl = code.relay(T, G, relay.sols)
-        syn = syndromes.contiguous()
-        wm, wn = (m + 63) // 64, (n + 63) // 64
-        if syn.dim() == 2 and syn.dtype == torch.uint8 and syn.shape[1] == m:
-            syn_fmt = _lib.FMT_BYTES
-        elif syn.dim() == 2 and syn.dtype == torch.int64 and syn.shape[1] == wm:
-            syn_fmt = _lib.FMT_BITS
-        else:
-            raise ValueError(f"syndromes must be uint8 [B, {m}] or int64 words [B, {wm}]")
-        B = syn.shape[0]
-        e_shape, e_dtype = ((B, wn), torch.int64) if ehat_bits else ((B, n), torch.uint8)
-        if out is not None:
-            ehat, iters, flags, info = out.ehat, out.iters, out.flags, out.info
-            post = out.post if want_post else None
-            ok = (ehat.shape == e_shape and ehat.dtype == e_dtype and iters.shape == (B,) and
-                  iters.dtype == torch.int32 and flags.shape == (B,) and flags.dtype == torch.int32 and
-                  info is not None and info.shape == (B, 2) and info.dtype == torch.int32 and
-                  all(t.device == dev and t.is_contiguous() for t in (ehat, iters, flags, info)) and
-                  (not want_post or (post is not None and post.shape == (B, n) and
-                                     post.dtype == torch.float64 and post.device == dev and
-                                     post.is_contiguous())))
-            if not ok:
-                raise ValueError("out buffers do not match the batch (uint8 [B, n] or int64 [B, ceil(n/64)], "
-                                 "int32 [B], int32 [B], int32 info [B, 2], float64 [B, n] if want_post) on the "
-                                 "syndromes' device")
-        else:
-            ehat = torch.empty(e_shape, dtype=e_dtype, device=dev)
-            iters = torch.empty(B, dtype=torch.int32, device=dev)
-            flags = torch.empty(B, dtype=torch.int32, device=dev)
-            info = torch.empty((B, 2), dtype=torch.int32, device=dev)
-            post = torch.empty((B, n), dtype=torch.float64, device=dev) if want_post else None
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(_lib.lib.qldpc_decode_device_relay(
-            code.handle, rl.handle, syn.data_ptr(), syn_fmt, B, float(p), float(beta), float(eps), ehat.data_ptr(),
-            _lib.FMT_BITS if ehat_bits else _lib.FMT_BYTES, iters.data_ptr(),
-            post.data_ptr() if post is not None else None, flags.data_ptr(), info.data_ptr(), st))
-        return DecodeResult(ehat, iters, post, flags, info)
-
-    syn = np.ascontiguousarray(syndromes)
-    if syn.ndim != 2 or syn.shape[1] != m:
-        raise ValueError(f"syndromes must be [B, {m}]")
-    if syn.size and (syn.min() < 0 or syn.max() > 1):
-        raise ValueError("syndrome entries must be 0 or 1")
-    syn = syn.astype(np.uint8, copy=False)
-    B = syn.shape[0]
-    code = _lib.code_for(H)
-    rl = code.relay(T, G, relay.sols)
-    ehat = np.zeros((B, n), np.uint8)
-    iters = np.zeros(B, np.int32)
-    flags = np.zeros(B, np.int32)
-    info = np.zeros((B, 2), np.int32)
-    post = np.zeros((B, n), np.float64) if want_post else None
-    _lib.check(_lib.lib.qldpc_decode_host_relay(
-        code.handle, rl.handle, _lib.ptr(syn), B, float(p), float(beta), float(eps), _lib.ptr(ehat),
-        _lib.ptr(iters), _lib.ptr(post), _lib.ptr(flags), _lib.ptr(info)))
-    return DecodeResult(ehat, iters, post, flags, info)
+    host = not _is_torch(syndromes)
+    code, rl, res, ins, _, outs, held = (_host_batch if host else _device_batch)(
+        H, syndromes, _lib.Code.relay, (T, G, relay.sols), want_post, out=out, stream=stream, ehat_bits=ehat_bits,
+        has_info=True)
+    L = _lib.lib
+    _lib.check((L.qldpc_decode_host_relay if host else L.qldpc_decode_device_relay)(
+        code.handle, rl.handle, *ins, float(p), float(beta), float(eps), *outs))
+    return res
 
 
 def _decode_batch_hard(H, syndromes, max_iter, algo, want_post, osd_order, stream, out, ehat_bits):
@@ -389,42 +258,37 @@ def _decode_batch_hard(H, syndromes, max_iter, algo, want_post, osd_order, strea
     H = np.asarray(H)
     if H.ndim != 2 or H.size == 0:
         raise ValueError("H must be a non-empty 2-D matrix")
-    m, n = H.shape
     max_iter = int(max_iter) if algo == "BF" else 1
     if max_iter < 1:
         raise ValueError("max_iter must be >= 1")
-    A = _lib.ALGO[algo]
-    if _is_torch(syndromes):
-        import torch
-        dev = syndromes.device
-        code = _lib.code_for(H, dev.index)
-        syn = syndromes.contiguous()
-        wm, wn = (m + 63) // 64, (n + 63) // 64
-        if syn.dim() == 2 and syn.dtype == torch.uint8 and syn.shape[1] == m:
-            syn_fmt = _lib.FMT_BYTES
-        elif syn.dim() == 2 and syn.dtype == torch.int64 and syn.shape[1] == wm:
-            syn_fmt = _lib.FMT_BITS
-        else:
-            raise ValueError(f"syndromes must be uint8 [B, {m}] or int64 words [B, {wm}]")
-        B = syn.shape[0]
-        e_shape, e_dtype = ((B, wn), torch.int64) if ehat_bits else ((B, n), torch.uint8)
-        if out is not None:
-            ehat, iters, flags = out.ehat, out.iters, out.flags
-            if not (ehat.shape == e_shape and ehat.dtype == e_dtype and iters.shape == (B,) and
-                    iters.dtype == torch.int32 and flags.shape == (B,) and flags.dtype == torch.int32 and
-                    all(t.device == dev and t.is_contiguous() for t in (ehat, iters, flags))):
-                raise ValueError("out buffers do not match the batch (uint8 [B, n] or int64 [B, ceil(n/64)], "
-                                 "int32 [B], int32 [B]) on the syndromes' device")
-        else:
-            ehat = torch.empty(e_shape, dtype=e_dtype, device=dev)
-            iters = torch.empty(B, dtype=torch.int32, device=dev)
-            flags = torch.empty(B, dtype=torch.int32, device=dev)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(_lib.lib.qldpc_hard_decode_device(
-            code.handle, A, syn.data_ptr(), syn_fmt, B, max_iter, ehat.data_ptr(),
-            _lib.FMT_BITS if ehat_bits else _lib.FMT_BYTES, iters.data_ptr(), flags.data_ptr(), st))
-        return DecodeResult(ehat, iters, None, flags)
+    host = not _is_torch(syndromes)
+    code, _, res, ins, _, outs, held = (_host_batch if host else _device_batch)(
+        H, syndromes, None, (), False, out=out, stream=stream, ehat_bits=ehat_bits, has_post=False)
+    L = _lib.lib
+    _lib.check((L.qldpc_hard_decode_host if host else L.qldpc_hard_decode_device)(
+        code.handle, _lib.ALGO[algo], *ins, max_iter, *outs))
+    return res
 
+
+# _host_batch and _device_batch: what every decode_batch family does alike on its path. They take the same
+# arguments (each ignores the other path's) and return (code, handle, res, ins, mask, outs, held):
+#   code, handle  the _lib.Code of H and the family's handle on it, `make`(code, *made_from) (_lib.Code.schedule /
+#                 .relay; None: no handle)
+#   res           the DecodeResult, outputs in place
+#   ins, mask, outs   the runs of an entry's arguments that every family shares, around its own handles and scalars,
+#                 as addresses; post only where the entry has the slot (`has_post`; None where no posteriors are
+#                 kept), info likewise (`has_info`):
+#                     host    ins (syndromes, B)          mask (mask,)         outs (ehat, iters, post, flags, info)
+#                     device  ins (syndromes, format, B)  mask (mask, format)  outs (ehat, format, iters, post, flags,
+#                                                                                    info, stream)
+#   held          the (syndromes, posteriors, mask) those addresses point into, to be kept until the entry returns
+def _host_batch(H, syndromes, make, made_from, want_post, osd=False, prior_mask=None, out=None, stream=None,
+                ehat_bits=False, has_post=True, has_info=False):
+    """Staged and synchronous. The syndromes and the mask are looked at before
+    the code and the handle are made; posteriors are kept for OSD (`osd`) even
+    where the result returns none."""
+    ptr = _lib.ptr
+    m, n = H.shape
     syn = np.ascontiguousarray(syndromes)
     if syn.ndim != 2 or syn.shape[1] != m:
         raise ValueError(f"syndromes must be [B, {m}]")
@@ -432,13 +296,83 @@ def _decode_batch_hard(H, syndromes, max_iter, algo, want_post, osd_order, strea
         raise ValueError("syndrome entries must be 0 or 1")
     syn = syn.astype(np.uint8, copy=False)
     B = syn.shape[0]
+    mask = ()
+    if prior_mask is not None:
+        if _is_torch(prior_mask):
+            raise ValueError("prior_mask must be a NumPy array on the host path (the syndromes are)")
+        prior_mask = np.ascontiguousarray(prior_mask)
+        if prior_mask.shape != (B, n):
+            raise ValueError(f"prior_mask must be [{B}, {n}]")
+        if prior_mask.size and (prior_mask.min() < 0 or prior_mask.max() > 1):
+            raise ValueError("prior_mask entries must be 0 or 1")
+        prior_mask = prior_mask.astype(np.uint8, copy=False)
+        mask = (ptr(prior_mask),)
     code = _lib.code_for(H)
-    ehat = np.zeros((B, n), np.uint8)
-    iters = np.zeros(B, np.int32)
-    flags = np.zeros(B, np.int32)
-    _lib.check(_lib.lib.qldpc_hard_decode_host(code.handle, A, _lib.ptr(syn), B, max_iter, _lib.ptr(ehat),
-                                               _lib.ptr(iters), _lib.ptr(flags)))
-    return DecodeResult(ehat, iters, None, flags)
+    handle = make(code, *made_from) if make is not None else None
+    post = np.zeros((B, n), np.float64) if want_post or osd else None
+    res = DecodeResult(np.zeros((B, n), np.uint8), np.zeros(B, np.int32), post if want_post else None,
+                       np.zeros(B, np.int32), np.zeros((B, 2), np.int32) if has_info else None)
+    if has_info:
+        outs = (ptr(res.ehat), ptr(res.iters), ptr(post), ptr(res.flags), ptr(res.info))
+    elif has_post:
+        outs = (ptr(res.ehat), ptr(res.iters), ptr(post), ptr(res.flags))
+    else:
+        outs = (ptr(res.ehat), ptr(res.iters), ptr(res.flags))
+    return code, handle, res, (ptr(syn), B), mask, outs, (syn, post, prior_mask)
+
+
+def _device_batch(H, syndromes, make, made_from, want_post, osd=False, prior_mask=None, out=None, stream=None,
+                  ehat_bits=False, has_post=True, has_info=False):
+    """Asynchronous on `stream` (or torch's current one); it syncs on nothing.
+    The code and the handle are made before the syndromes are looked at; with
+    out= nothing is allocated."""
+    import torch
+    m, n = H.shape
+    dev = syndromes.device
+    code = _lib.code_for(H, dev.index)
+    handle = make(code, *made_from) if make is not None else None
+    syn = syndromes.contiguous()
+    wm, wn = (m + 63) // 64, (n + 63) // 64
+    if syn.dim() == 2 and syn.dtype == torch.uint8 and syn.shape[1] == m:
+        syn_fmt = _lib.FMT_BYTES
+    elif syn.dim() == 2 and syn.dtype == torch.int64 and syn.shape[1] == wm:
+        syn_fmt = _lib.FMT_BITS
+    else:
+        raise ValueError(f"syndromes must be uint8 [B, {m}] or int64 words [B, {wm}]")
+    B = syn.shape[0]
+    mask = ()
+    if prior_mask is not None:
+        if not (_is_torch(prior_mask) and prior_mask.device == dev and prior_mask.dim() == 2):
+            raise ValueError("prior_mask must be a 2-D tensor on the syndromes' device")
+        prior_mask = prior_mask.contiguous()
+        if prior_mask.dtype == torch.uint8 and tuple(prior_mask.shape) == (B, n):
+            mask = (prior_mask.data_ptr(), _lib.FMT_BYTES)
+        elif prior_mask.dtype == torch.int64 and tuple(prior_mask.shape) == (B, wn):
+            mask = (prior_mask.data_ptr(), _lib.FMT_BITS)
+        else:
+            raise ValueError(f"prior_mask must be uint8 [{B}, {n}] or int64 words [{B}, {wn}]")
+    want = {"ehat": ((B, wn), torch.int64) if ehat_bits else ((B, n), torch.uint8),
+            "iters": ((B,), torch.int32), "flags": ((B,), torch.int32)}
+    if has_info:
+        want["info"] = ((B, 2), torch.int32)
+    if want_post:
+        want["post"] = ((B, n), torch.float64)
+    if out is not None:
+        t = {k: getattr(out, k) for k in want}
+        if not all(x is not None and x.shape == shape and x.dtype == dtype and x.device == dev and x.is_contiguous()
+                   for x, (shape, dtype) in zip(t.values(), want.values())):
+            raise ValueError("out buffers do not match the batch (uint8 [B, n] or int64 [B, ceil(n/64)], int32 [B], "
+                             "int32 [B]" + (", int32 info [B, 2]" if has_info else "")
+                             + (", float64 [B, n] if want_post" if has_post else "") + ") on the syndromes' device")
+    else:
+        t = {k: torch.empty(shape, dtype=dtype, device=dev) for k, (shape, dtype) in want.items()}
+    res = DecodeResult(t["ehat"], t["iters"], t.get("post"), t["flags"], t.get("info"))
+    st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    post_p = (res.post.data_ptr() if want_post else None,) if has_post else ()
+    info_p = (res.info.data_ptr(),) if has_info else ()
+    outs = (res.ehat.data_ptr(), _lib.FMT_BITS if ehat_bits else _lib.FMT_BYTES, res.iters.data_ptr(), *post_p,
+            res.flags.data_ptr(), *info_p, st)
+    return code, handle, res, (syn.data_ptr(), syn_fmt, B), mask, outs, (syn, res.post, prior_mask)
 
 
 def osd_perm(posteriorLLRs):
@@ -707,19 +641,10 @@ def reset_osd_stats():
     OSD_STATS.update(osd_shots=0, host_order_shots=0)
 
 
-def _host_order_only():
-    return OSD_POLICY["host_order"] or not numpy_order_pinned()
-
-
-def _device_order_min():
-    return OSD_POLICY["device_min"]
-
-
 def _on_stream(stream):
     """Context that makes `stream` (a raw HIP stream handle, or None = torch's
     current stream) the current stream, so every kernel, copy and event of
     one OSD stage is ordered on it."""
-    import contextlib
     import torch
     if stream is None:
         return contextlib.nullcontext()
@@ -752,6 +677,28 @@ def osd_device_stage(items, stream=None, slot0=0, order=0):
     return staged
 
 
+@dataclass
+class _Staged:
+    """One decode's OSD work as osd_device_stage queued it, for
+    osd_host_orders and osd_device_finish."""
+    bad: object           # int64 [shots]: the batch's non-converged shots (device)
+    post_b: object        # their posteriors, syndromes and estimates, gathered (device)
+    syn_b: object
+    e_b: object
+    status: object        # int32 [shots] (device): 0 done, 1 the IndexError case, 2 needs NumPy's order
+    status_h: object      # its pinned host copy, valid after `ev`
+    ev: object            # recorded on the launch stream after everything queued here
+    slot: int             # the pinned / spill buffer set
+    on_dev: bool          # the device computed the reliability order (else every shot has status 2)
+    shots: int
+    # on_dev: the posteriors of the status-2 shots as the kernels spilled them, their shot indices, the pinned
+    # copy of their count (valid after `ev`), and the rows the spill buffers hold
+    sp_post: object = None
+    sp_idx: object = None
+    cnt_h: object = None
+    cap: int = 0
+
+
 def _osd_stage_one(H, syn, res, slot, order):
     import torch
     if res.post is None:
@@ -770,7 +717,6 @@ def _osd_stage_one(H, syn, res, slot, order):
     if k == 0:
         return None
     OSD_STATS["osd_shots"] += k
-    n = res.post.shape[1]
     code = _lib.code_for(H, dev.index)
     post_b = res.post.index_select(0, bad)
     syn_b = syn.index_select(0, bad)
@@ -779,8 +725,9 @@ def _osd_stage_one(H, syn, res, slot, order):
     cs = torch.cuda.current_stream(dev)
     st = cs.cuda_stream
     status_h = _pinned(("status", slot), (k,), torch.int32)
-    on_dev = n <= 2048 and k >= _device_order_min() and not _host_order_only()
-    spill = None
+    on_dev = (n <= 2048 and k >= OSD_POLICY["device_min"] and not OSD_POLICY["host_order"]
+              and numpy_order_pinned())
+    spill = ()
     if on_dev:
         perm = torch.empty((k, n), dtype=torch.int32, device=dev)
         tie = torch.empty(k, dtype=torch.int32, device=dev)
@@ -805,13 +752,13 @@ def _osd_stage_one(H, syn, res, slot, order):
     status_h.copy_(status, non_blocking=True)
     ev = torch.cuda.Event()
     ev.record(cs)
-    return (bad, post_b, syn_b, e_b, status, status_h, ev, slot, on_dev, spill)
+    return _Staged(bad, post_b, syn_b, e_b, status, status_h, ev, slot, on_dev, k, *spill)
 
 
 def osd_staged_on_device(staged):
     """Whether osd_device_stage queued any decode's shots with the device
     reliability order (rather than leaving them all to NumPy's)."""
-    return any(sg is not None and sg[8] for sg in staged)
+    return any(sg is not None and sg.on_dev for sg in staged)
 
 
 _DEVBUF = {}
@@ -859,10 +806,10 @@ def osd_host_orders(staged):
         if sg is None:
             out.append(None)
             continue
-        bad, post_b, syn_b, e_b, status, status_h, ev, slot, _, spill = sg
+        post_b, ev, slot = sg.post_b, sg.ev, sg.slot
         dev = post_b.device
         ev.synchronize()
-        redo = (status_h.numpy() == 2).nonzero()[0]
+        redo = (sg.status_h.numpy() == 2).nonzero()[0]
         if redo.size == 0:
             out.append((redo, None))
             continue
@@ -873,14 +820,13 @@ def osd_host_orders(staged):
         # (decode, device OSD) keeps running
         side = _side_stream(dev)
         side.wait_event(ev)
-        if spill is not None and k2 <= spill[3] and int(spill[2][0]) == k2:
+        if sg.on_dev and k2 <= sg.cap and int(sg.cnt_h[0]) == k2:
             # the kernels spilled exactly these rows: one contiguous DMA copy
             # (no gather kernel waiting for free CUs behind other work)
-            sp_post, sp_idx, _, _ = spill
             idx_h = _pinned(("spill_idx", slot), (k2,), torch.int32)
             with torch.cuda.stream(side):
-                hostp.copy_(sp_post[:k2], non_blocking=True)
-                idx_h.copy_(sp_idx[:k2], non_blocking=True)
+                hostp.copy_(sg.sp_post[:k2], non_blocking=True)
+                idx_h.copy_(sg.sp_idx[:k2], non_blocking=True)
             side.synchronize()
             redo = idx_h.numpy().astype(np.int64)
         else:
@@ -907,7 +853,7 @@ def osd_host_orders(staged):
 
 def _osd_finish_device(H, syn, res, sg, hr, order):
     import torch
-    bad, post_b, syn_b, e_b, status, status_h, ev, slot, _, spill = sg
+    e_b, status = sg.e_b, sg.status
     dev = res.ehat.device
     code = _lib.code_for(H, dev.index)
     redo, perm_h = hr
@@ -917,7 +863,7 @@ def _osd_finish_device(H, syn, res, sg, hr, order):
         k2 = int(redo.size)
         idx = torch.as_tensor(redo, device=dev)
         perms = perm_h.to(dev, non_blocking=True)
-        syn_r = syn_b.index_select(0, idx)
+        syn_r = sg.syn_b.index_select(0, idx)
         e_r = e_b.index_select(0, idx)
         st2 = torch.empty(k2, dtype=torch.int32, device=dev)
         st = torch.cuda.current_stream(dev).cuda_stream
@@ -925,7 +871,7 @@ def _osd_finish_device(H, syn, res, sg, hr, order):
                                              e_r.data_ptr(), st2.data_ptr(), st))
         e_b.index_copy_(0, idx, e_r)
         status.index_copy_(0, idx, st2)
-    res.ehat.index_copy_(0, bad, e_b)
+    res.ehat.index_copy_(0, sg.bad, e_b)
     res.osd_status = status      # checked by the caller (raises IndexError like the reference)
 
 
@@ -935,7 +881,7 @@ def osd_status_check(items, defer=None):
     `defer` list, the per-decode flags are appended there as device tensors
     instead (no sync; the caller checks them with osd_status_raise)."""
     for _, _, res in items:
-        st = getattr(res, "osd_status", None)
+        st = res.osd_status
         if st is None:
             continue
         if defer is not None:
@@ -972,51 +918,58 @@ def apply_osd(H, syn, ehat, post, flags, order, nthreads=None):
     return ehat
 
 
-def _single(H, syndrome, p, max_iter, layers, algo, beta, eps):
-    H = np.asarray(H)
-    syndrome = np.asarray(syndrome)
+def _shot(H, syndrome):
+    """A single-shot wrapper's (H, syndrome) as arrays, and the reference's
+    answer where either is empty: a bare int8 array, no tuple (decoders.py:86-87,
+    :138-139, :215-216; NG and relay do as MS / BP / BF), else None."""
+    H, syndrome = np.asarray(H), np.asarray(syndrome)
+    empty = H.size == 0 or syndrome.size == 0
+    return H, syndrome, np.zeros(H.shape[1] if H.size else 0, dtype=np.int8) if empty else None
+
+
+def _row(H, syndrome):
+    """The syndrome as a batch of one."""
     m, n = H.shape
     if syndrome.shape != (m,):
         raise ValueError(f"syndrome must have shape ({m},), got {syndrome.shape}")
+    return syndrome.reshape(1, m)
+
+
+def _soft(H, syndrome, p, max_iter, layers, algo, beta, eps, OSDorder, dtype):
+    """MS_decoder / BP_decoder of a non-empty shot: (e_hat of `dtype`, n_iter)."""
+    row = _row(H, syndrome)
     if int(max_iter) < 1:
         # the reference's iteration loop never binds e_hat (decoders.py:153/:182)
         raise UnboundLocalError("local variable 'e_hat' referenced before assignment")
-    lp, lr = pack_layers(layers, m)
+    lp, lr = pack_layers(layers, H.shape[0])
     # p may be an array of n probabilities, one per column (the reference
     # raises on max(array, eps) there: DESIGN.md §7)
     vec = np.ndim(p) > 0
-    r = decode_batch(H, syndrome.reshape(1, m), None if vec else p, max_iter, algo=algo, beta=beta, eps=eps,
+    r = decode_batch(H, row, None if vec else p, max_iter, algo=algo, beta=beta, eps=eps,
                      want_post=True, layer_ptr=lp, layer_rows=lr, prior=p if vec else None)
-    return r.ehat[0], int(r.iters[0]), r.post[0], bool(r.converged[0])
+    e_hat = r.ehat[0].astype(dtype)
+    if OSDorder >= 0 and not r.converged[0]:       # (:179-180, :287-288)
+        e_hat = OSDdec(H, e_hat, syndrome, r.post[0], OSDorder)
+    return e_hat, int(r.iters[0])
 
 
 def MS_decoder(H: np.ndarray, syndrome: np.ndarray, p: float, max_iter: int = 99,
                layers: Optional[list] = None, beta: float = 0.75, OSDorder: int = -1,
                eps: float = 1e-9):
     """Normalized min-sum (reference decoders.py:110-182) on the GPU."""
-    H = np.asarray(H)
-    syndrome = np.asarray(syndrome)
-    if H.size == 0 or syndrome.size == 0:          # reference quirk: bare array (:138-139)
-        return np.zeros(H.shape[1] if H.size else 0, dtype=np.int8)
-    e, it, post, conv = _single(H, syndrome, p, max_iter, layers, "MS", beta, eps)
-    e_hat = e.astype(np.int8)
-    if not conv and OSDorder >= 0:                 # (:179-180)
-        e_hat = OSDdec(H, e_hat, syndrome, post, OSDorder)
-    return e_hat, it
+    H, syndrome, bare = _shot(H, syndrome)
+    if bare is not None:
+        return bare
+    return _soft(H, syndrome, p, max_iter, layers, "MS", beta, eps, OSDorder, np.int8)
 
 
 def BP_decoder(H: np.ndarray, syndrome: np.ndarray, p: float, max_iter: int = 99,
                layers: Optional[list] = None, OSDorder: int = -1, eps: float = 1e-9):
     """Sum-product BP (reference decoders.py:189-290) on the GPU."""
-    H = np.asarray(H)
-    syndrome = np.asarray(syndrome)
-    if H.size == 0 or syndrome.size == 0:          # (:215-216)
-        return np.zeros(H.shape[1] if H.size else 0, dtype=np.int8)
-    e, it, post, conv = _single(H, syndrome, p, max_iter, layers, "BP", 0.75, eps)
-    e_hat = e.astype(int)                          # (L_post < 0).astype(int) (:280)
-    if not conv and OSDorder >= 0:                 # (:287-288)
-        e_hat = OSDdec(H, e_hat, syndrome, post, OSDorder)
-    return e_hat, it
+    H, syndrome, bare = _shot(H, syndrome)
+    if bare is not None:
+        return bare
+    return _soft(H, syndrome, p, max_iter, layers, "BP", 0.75, eps, OSDorder, int)   # (L_post < 0).astype(int) (:280)
 
 
 def Relay_decoder(H: np.ndarray, syndrome: np.ndarray, p: float, leg_iters, gammas, sols: int = 1,
@@ -1024,48 +977,32 @@ def Relay_decoder(H: np.ndarray, syndrome: np.ndarray, p: float, leg_iters, gamm
     """Relay min-sum of one syndrome on the GPU, in the style
     of MS_decoder: (e_hat int8 [n], passes run over all legs). `gammas` is
     float64 [len(leg_iters), n] (relay_gammas)."""
-    H = np.asarray(H)
-    syndrome = np.asarray(syndrome)
-    if H.size == 0 or syndrome.size == 0:          # the bare array of MS_decoder
-        return np.zeros(H.shape[1] if H.size else 0, dtype=np.int8)
-    m, n = H.shape
-    if syndrome.shape != (m,):
-        raise ValueError(f"syndrome must have shape ({m},), got {syndrome.shape}")
-    r = decode_batch(H, syndrome.reshape(1, m), p, 0, algo="RELAY", beta=beta, eps=eps,
+    H, syndrome, bare = _shot(H, syndrome)
+    if bare is not None:
+        return bare
+    r = decode_batch(H, _row(H, syndrome), p, 0, algo="RELAY", beta=beta, eps=eps,
                      relay=RelayConfig(leg_iters, gammas, sols))
     return r.ehat[0].astype(np.int8), int(r.iters[0])
 
 
-def _single_hard(H, syndrome, algo, max_iter=1):
-    H = np.asarray(H)
-    syndrome = np.asarray(syndrome)
-    m, n = H.shape
-    if syndrome.shape != (m,):
-        raise ValueError(f"syndrome must have shape ({m},), got {syndrome.shape}")
-    r = decode_batch(H, syndrome.reshape(1, m), 0.0, max_iter, algo=algo)
-    return r.ehat[0], int(r.iters[0])
-
-
 def NG_decoder(H: np.ndarray, syndrome: np.ndarray):
     """Naive greedy (reference decoders.py:27-66) on the GPU: (int8 [n], steps)."""
-    H = np.asarray(H)
-    syndrome = np.asarray(syndrome)
-    if H.size == 0 or syndrome.size == 0:          # the bare array of MS / BP / BF (:86-87, DESIGN.md §7)
-        return np.zeros(H.shape[1] if H.size else 0, dtype=np.int8)
-    e, steps = _single_hard(H, syndrome, "NG")
-    return e.astype(np.int8), steps
+    H, syndrome, bare = _shot(H, syndrome)
+    if bare is not None:
+        return bare
+    r = decode_batch(H, _row(H, syndrome), 0.0, 1, algo="NG")
+    return r.ehat[0].astype(np.int8), int(r.iters[0])
 
 
 def BF_decoder(H: np.ndarray, syndrome: np.ndarray, max_iter: int = 50):
     """Bit flipping (reference decoders.py:74-102) on the GPU: (bool [n], iterations)."""
-    H = np.asarray(H)
-    syndrome = np.asarray(syndrome)
-    if H.size == 0 or syndrome.size == 0:          # reference quirk: bare array (:86-87)
-        return np.zeros(H.shape[1] if H.size else 0, dtype=np.int8)
+    H, syndrome, bare = _shot(H, syndrome)
+    if bare is not None:
+        return bare
     if max_iter < 1:                               # the loop does not run (:89, :102): float zeros
         return np.zeros(H.shape[1]), max_iter
-    e, it = _single_hard(H, syndrome, "BF", max_iter)
-    return e.astype(bool), it
+    r = decode_batch(H, _row(H, syndrome), 0.0, max_iter, algo="BF")
+    return r.ehat[0].astype(bool), int(r.iters[0])
 
 
 def OSDdec(H: np.ndarray, e_hat: np.ndarray, syndrome: np.ndarray, posteriorLLRs: np.ndarray,

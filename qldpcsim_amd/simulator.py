@@ -738,7 +738,7 @@ def _pipelined_loop(ch, count, acc, plan, p, my_shots, batch_size, osd_flags, sh
             stage(cur)
         if cur is not None and osd >= 0:
             stage_first = decoders.osd_staged_on_device(cur.staged)
-            osd_frac = sum(int(sg[0].numel()) for sg in cur.staged if sg is not None) / (2.0 * B)
+            osd_frac = sum(sg.shots for sg in cur.staged if sg is not None) / (2.0 * B)
         pending = cur
         if cur is not None:
             show(done)
