@@ -371,11 +371,67 @@ __device__ __forceinline__ void min12_tree(const double* v, double& lo, double& 
   }
 }
 
+// Unsigned minimum / median of three (non-negative float32 bit patterns order
+// as unsigned integers; no canonicalisation, no denormal mode)
+__device__ __forceinline__ uint32_t umin3(uint32_t x, uint32_t y, uint32_t z) {
+  uint32_t r;
+  asm("v_min3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(y), "v"(z));
+  return r;
+}
+__device__ __forceinline__ uint32_t umed3(uint32_t x, uint32_t y, uint32_t z) {
+  uint32_t r;
+  asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(y), "v"(z));
+  return r;
+}
+
+// Smallest and second smallest (with multiplicity) of w[0..N) as unsigned
+// integers. A group of three gives its pair as (min3, med3), a group of two as
+// (min, max), a single value has no second. Three pairs (l, h) merge as
+//   lo = min3(l1, l2, l3),  hi = min(med3(l1, l2, l3), min3(h1, h2, h3)):
+// with the smallest value taken out, what remains is the other two l (their
+// smaller one is the median of the three) and every h. N = 8 as 3 + 3 + 2 and
+// N = 7 as 3 + 2 + 2: 10 instructions each (pairwise merging as min12_tree's: 17).
+template <int N>
+__device__ __forceinline__ void min12_tree_u32(const uint32_t* w, uint32_t& lo, uint32_t& hi) {
+  if constexpr (N == 1) {
+    lo = w[0];
+    hi = 0xffffffffu;
+  } else if constexpr (N == 2) {
+    lo = w[0] < w[1] ? w[0] : w[1];
+    hi = w[0] < w[1] ? w[1] : w[0];
+  } else if constexpr (N == 3) {
+    lo = umin3(w[0], w[1], w[2]);
+    hi = umed3(w[0], w[1], w[2]);
+  } else {
+    constexpr int A = (N + 2) / 3, B = (N + 1) / 3, C = N / 3;   // A >= B >= C >= 1, A >= 2
+    uint32_t l1, h1, l2, h2, l3, h3;
+    min12_tree_u32<A>(w, l1, h1);
+    min12_tree_u32<B>(w + A, l2, h2);
+    min12_tree_u32<C>(w + A + B, l3, h3);
+    lo = umin3(l1, l2, l3);
+    const uint32_t m = umed3(l1, l2, l3);
+    if constexpr (C >= 2) {
+      const uint32_t h = umin3(h1, h2, h3);
+      hi = m < h ? m : h;
+    } else if constexpr (B >= 2) {
+      hi = umin3(m, h1, h2);
+    } else {
+      hi = m < h1 ? m : h1;
+    }
+  }
+}
+
 // XOR of N words as a balanced tree (v_xor3_b32-friendly)
 __device__ __forceinline__ uint32_t xor3(uint32_t x, uint32_t y, uint32_t z) {
   uint32_t r;
   // gfx950 has no v_xor3_b32; v_bitop3_b32 truth table 0x96 = S0 ^ S1 ^ S2
   asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(r) : "v"(x), "v"(y), "v"(z));
+  return r;
+}
+// (x & m) ^ y in one instruction, m wave-uniform (truth table 0x6c = (S0 & S2) ^ S1)
+__device__ __forceinline__ uint32_t and_xor(uint32_t x, uint32_t m, uint32_t y) {
+  uint32_t r;
+  asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x6c" : "=v"(r) : "v"(x), "v"(y), "s"(m));
   return r;
 }
 template <int N>

@@ -8,7 +8,10 @@
 // register-resident body (ms_flood_qc.h): 33.59 ms with max-ilp against 33.81
 // with the default scheduler (make FLOOD_SCHED=; profiles/r07a/); and for its
 // per-variable float64 posteriors: 30.94 against 30.97 ms (medians of 5, the
-// ranges overlap; profiles/r08a/), so max-ilp stays.
+// ranges overlap; profiles/r08a/); and with the check node's sign word formed
+// ahead of the tournament: 30.53 against 31.09 ms (profiles/r09a/), so
+// max-ilp stays. (The float32-domain check node, -DQLDPC_QC_CN32, spills
+// under it and was timed with the default scheduler, make FLOOD_SCHED=.)
 #include "ms_flood.h"
 
 namespace qldpc {

@@ -136,6 +136,54 @@ struct RowQueue {
   }
 };
 
+// Where check block B's minimum and select are taken (-DQLDPC_QC_CN32=n for
+// A/B; DESIGN.md §3.1.1 for the measured choice):
+//   0  on the float64 |v|: min12_tree, fl32(beta * min) twice, a float64
+//      compare and select per edge (qc_min_select_f64)
+//   1  on w_e = bits(fl32(beta * |v_e|)) as unsigned integers: min12_tree_u32,
+//      then per edge med3(w_e, w1, w2) ^ (w1 ^ w2), the other one of the two
+// Rounding to float32 and multiplying by beta > 0 are monotone, so the smallest
+// and second smallest w_e (with multiplicity) are fl32(beta * min1) and
+// fl32(beta * min2), and (w_e == w1 ? w2 : w1) has the bits of the float64
+// select: where w_e == w1 for an edge that is not the float64 argmin, w2 == w1.
+// (A NaN v_e, inf - inf, exists only after a message overflowed float32, outside
+// the contract of DESIGN.md §4; the integer order ranks it last, v_min_f64 /
+// v_max_f64 skip it, and the two forms may then differ.)
+#ifndef QLDPC_QC_CN32
+#define QLDPC_QC_CN32 0
+#endif
+
+// The float64 minimum and select of one check (decoders.py:160-169), with the
+// reference's substitutions for infinite and zero minima and FLAG_MIN_ZERO
+template <int DC>
+__device__ __forceinline__ void qc_min_select_f64(const DecodeArgs& a, const double (&v)[DC], const uint32_t (&hv)[DC],
+                                                  uint32_t npm, float (&cv)[DC], int& fl) {
+  double min1, min2;                                      // first min / min of the rest (:160-164)
+  min12_tree<DC>(v, min1, min2);
+  double m1 = min1, m2 = min2;
+  if (__builtin_expect(ballot((min1 == 0.0) | (min2 == __builtin_inf())) != 0, 0)) {
+    m1 = __builtin_isinf(min1) ? 0.0 : min1;              // (:165)
+    m2 = __builtin_isinf(min2) ? 0.0 : min2;              // (:166)
+    if (m1 == 0.0) fl |= FLAG_MIN_ZERO;
+  }
+  const uint32_t c1n = opaque_always(__builtin_bit_cast(uint32_t, (float)(a.beta * m1)) ^ npm);
+  const uint32_t c2n = opaque_always(__builtin_bit_cast(uint32_t, (float)(a.beta * m2)) ^ npm);
+  static_for<DC>([&](auto E) __attribute__((always_inline)) {
+    constexpr int e = E;
+    const uint32_t c = (__builtin_fabs(v[e]) == min1) ? c2n : c1n;
+    cv[e] = __builtin_bit_cast(float, c ^ (hv[e] & 0x80000000u));
+  });
+}
+
+// posterior of the variable behind edge E of check block B, rotated to the
+// check's lane
+template <typename T, int B, int E>
+__device__ __forceinline__ double qc_edge_post(double L, const float (&S)[T::NB], const double (&P)[T::NB]) {
+  constexpr int c = T::cvar[B][E], s = T::cshift[B][E];
+  if constexpr (qc_post64<T>(c)) return row_ror_f64<(16 - s) & 15>(P[c]);
+  else return L + (double)row_ror_f32<(16 - s) & 15>(S[c]);
+}
+
 // Min-sum update of check block B (decoders.py:155-169 for the lane's check):
 // cn_ms_compute with the posteriors rotated in from P (or formed from the
 // rotated S) and the messages in registers. Returns the check's "unsatisfied"
@@ -160,32 +208,37 @@ __device__ __forceinline__ uint32_t qc_check(const DecodeArgs& a, double L, floa
   double v[DC];
   uint32_t hv[DC], hp[DC];
   static_for<DC>([&](auto E) __attribute__((always_inline)) {
-    constexpr int e = E, c = T::cvar[B][e], s = T::cshift[B][e];
-    double post;
-    if constexpr (qc_post64<T>(c)) post = row_ror_f64<(16 - s) & 15>(P[c]);
-    else post = L + (double)row_ror_f32<(16 - s) & 15>(S[c]);
-    v[e] = post - (double)c2v[B][e];                      // v2c = post - c2v (:177)
-    hv[e] = hi_word(v[e]);
-    hp[e] = hi_word(post);
+    const double post = qc_edge_post<T, B, E>(L, S, P);
+    v[E] = post - (double)c2v[B][E];                      // v2c = post - c2v (:177)
+    hv[E] = hi_word(v[E]);
+    hp[E] = hi_word(post);
   });
-  double min1, min2;                                      // first min / min of the rest (:160-164)
-  min12_tree<DC>(v, min1, min2);
   const uint32_t ph = xor_tree<DC>(hp);                   // hard-decision parity (:174)
   const uint32_t sh = xor_tree<DC>(hv);                   // np.sign product (:157-159)
-  double m1 = min1, m2 = min2;
-  if (__builtin_expect(ballot((min1 == 0.0) | (min2 == __builtin_inf())) != 0, 0)) {
-    m1 = __builtin_isinf(min1) ? 0.0 : min1;              // (:165)
-    m2 = __builtin_isinf(min2) ? 0.0 : min2;              // (:166)
-    if (m1 == 0.0) fl |= FLAG_MIN_ZERO;
-  }
   const uint32_t npm = ((sh >> 31) ^ synb) << 31;
-  const uint32_t c1n = opaque_always(__builtin_bit_cast(uint32_t, (float)(a.beta * m1)) ^ npm);
-  const uint32_t c2n = opaque_always(__builtin_bit_cast(uint32_t, (float)(a.beta * m2)) ^ npm);
+#if QLDPC_QC_CN32
+  uint32_t w[DC];
   static_for<DC>([&](auto E) __attribute__((always_inline)) {
-    constexpr int e = E;
-    const uint32_t c = (__builtin_fabs(v[e]) == min1) ? c2n : c1n;
-    c2v[B][e] = __builtin_bit_cast(float, c ^ (hv[e] & 0x80000000u));
+    w[E] = __builtin_bit_cast(uint32_t, (float)(a.beta * __builtin_fabs(v[E])));
   });
+  uint32_t w1, w2;                                        // bits of fl32(beta * min1), fl32(beta * min2)
+  min12_tree_u32<DC>(w, w1, w2);
+  w1 = opaque_always(w1), w2 = opaque_always(w2);
+  // the reference's rules for zero and infinite minima (:165-166) and the
+  // flag are defined on the float64 minima: a wave with a zero or a
+  // non-finite float32 minimum takes the float64 check node as a whole
+  if (__builtin_expect(ballot((w1 == 0u) | (w2 >= 0x7f800000u)) != 0, 0)) {
+    qc_min_select_f64<DC>(a, v, hv, npm, c2v[B], fl);
+  } else {
+    // the median is w1 where w_e == w1 and w2 elsewhere: ^ (w1 ^ w2) gives the other one
+    const uint32_t w12n = xor3(w1, w2, npm);
+    static_for<DC>([&](auto E) __attribute__((always_inline)) {
+      c2v[B][E] = __builtin_bit_cast(float, umed3(w[E], w1, w2) ^ and_xor(hv[E], 0x80000000u, w12n));
+    });
+  }
+#else
+  qc_min_select_f64<DC>(a, v, hv, npm, c2v[B], fl);
+#endif
   uint32_t unsat = (ph >> 31) ^ synb;
   static_for<DC>([&](auto E) __attribute__((always_inline)) {
     float& cx = c2v[B][E];
