@@ -622,6 +622,46 @@ int qldpc_phenom_count(const qldpc_code *code, const qldpc_phenom *ph, int round
                        const int32_t *d_iters, int64_t *d_counters, uint8_t *d_class, uint64_t *d_flips,
                        uint64_t *d_resid, void *stream);
 
+/* qldpc_phenom_window: the step between two windows of sliding-window
+ * decoding, one launch of phenom_window_kernel. A window (start a, rounds R)
+ * covers rounds [a, a + R) of [0, T). An open window's matrix has R (n+m)
+ * columns (every round has its measurement columns); a closed one ends at
+ * round T, has the space-time matrix's R n + (R-1) m columns and commits all
+ * of its rounds. Each of the four rows is QLDPC_FMT_BYTES or QLDPC_FMT_BITS on
+ * its own format argument.
+ *   done_*   the window just decoded (done_rounds = 0: none, the first step):
+ *            its first done_commit (n+m) columns of d_west (closed: all) are
+ *            copied to columns done_start (n+m) + . of d_ehat, the other
+ *            columns of d_ehat stay as they are, and d_witers is added to
+ *            d_iters.
+ *     d_west    uint8 [batch][N_w] or uint64 [batch][ceil(N_w/64)]
+ *     d_witers  int32 [batch]
+ *     d_ehat    uint8 [batch][N] or uint64 [batch][ceil(N/64)], read and
+ *               written; in words the padding bits past N are cleared by the
+ *               step that commits column N - 1
+ *     d_iters   int32 [batch], added to
+ *   next_*   the window decoded next (next_rounds = 0: none, the last step;
+ *            with a decoded window next_start = done_start + done_commit):
+ *            d_syn = detectors next_start m .. (next_start + next_rounds) m of
+ *            d_det, the first m of them XORed with the committed measurement
+ *            estimate, columns (done_commit - 1) (n+m) + n + c of d_west.
+ *     d_det     as qldpc_phenom_sample wrote it
+ *     d_syn     uint8 [batch][next_rounds m] or uint64 words, padding bits zero
+ * QLDPC_EINVAL, before any HIP call: a window outside [0, T), done_commit
+ * outside [1, done_rounds], a closed window that does not end at T, commit all
+ * its rounds or has a successor, an open window that ends at T (its last
+ * round has measurement columns), neither window, an unknown format, a null
+ * buffer of a window that is given, a negative batch. The code's limits are
+ * those of qldpc_phenom_sample (QLDPC_EUNSUP); the kernel uses no LDS. The
+ * wave that owns a shot's row merges the first and last word of a commit, so
+ * successive windows are successive launches on one stream. Asynchronous on
+ * `stream`: no allocation, copy or synchronisation. */
+int qldpc_phenom_window(const qldpc_code *code, int rounds, int64_t batch, int done_start, int done_rounds,
+                        int done_closed, int done_commit, const void *d_west, int west_format,
+                        const int32_t *d_witers, void *d_ehat, int ehat_format, int32_t *d_iters, int next_start,
+                        int next_rounds, const void *d_det, int det_format, void *d_syn, int syn_format,
+                        void *stream);
+
 /* Kernel timing (HIP events around each decode kernel launch, on the launch
  * stream). Enabled by qldpc_timing_enable(1); qldpc_timing_read returns the
  * summed kernel milliseconds and launch count since the last reset. */

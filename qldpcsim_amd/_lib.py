@@ -41,6 +41,7 @@ EXPORTS = (
     "qldpc_channel_table", "qldpc_channel_create", "qldpc_channel_destroy", "qldpc_channel_sample_vec",
     "qldpc_logicals_create", "qldpc_logicals_destroy", "qldpc_count_logical_ex",
     "qldpc_phenom_create", "qldpc_phenom_destroy", "qldpc_phenom_sample", "qldpc_phenom_count",
+    "qldpc_phenom_window",
     "qldpc_timing_enable", "qldpc_timing_reset", "qldpc_timing_read",
     "qldpc_set_option", "qldpc_get_option",
 )
@@ -128,6 +129,7 @@ def _load():
         "qldpc_phenom_destroy": ([P], I),
         "qldpc_phenom_sample": ([P, I, D, D, ctypes.c_uint64, ctypes.c_uint64, I64, P, I, P, P, P], I),
         "qldpc_phenom_count": ([P, P, I, I64, P, I, P, P, I, P, P, P, P, P, P], I),
+        "qldpc_phenom_window": ([P, I, I64, I, I, I, I, P, I, P, P, I, P, I, I, P, I, P, I, P], I),
         "qldpc_timing_enable": ([I], I),
         "qldpc_timing_reset": ([], I),
         "qldpc_timing_read": ([P, P], I),
@@ -445,6 +447,18 @@ def phenom_count(code, table, rounds, batch, det, det_fmt, E, ehat, e_fmt, iters
     outputs may be None)."""
     check(lib.qldpc_phenom_count(code.handle, table.handle, int(rounds), int(batch), det, int(det_fmt), E, ehat,
                                  int(e_fmt), iters, acc, cls, flips, resid, stream))
+
+
+def phenom_window(code, rounds, batch, done, west, w_fmt, witers, ehat, e_fmt, iters, nxt, det, det_fmt, syn, syn_fmt,
+                  stream=None):
+    """qldpc_phenom_window on raw device addresses (ints). `done` = (start,
+    rounds, closed, commit) of the window just decoded or None; `nxt` = (start,
+    rounds) of the next one or None; a window's buffers may be None with it."""
+    a, R, closed, C = (int(v) for v in done) if done is not None else (0, 0, 0, 0)
+    a2, R2 = (int(nxt[0]), int(nxt[1])) if nxt is not None else (0, 0)
+    check(lib.qldpc_phenom_window(code.handle, int(rounds), int(batch), a, R, int(bool(closed)), C, west, int(w_fmt),
+                                  witers, ehat, int(e_fmt), iters, a2, R2, det, int(det_fmt), syn, int(syn_fmt),
+                                  stream))
 
 
 def logicals_for(Hx, Hz, device_index=None):

@@ -1,6 +1,6 @@
 // capi_phenom.cpp — phenomenological noise (multi-round space-time decoding of
-// one CSS half): the device shot source, the outcome counter and the half's
-// logical table (phenom_kernels.hip).
+// one CSS half): the device shot source, the outcome counter, the half's
+// logical table and the step between sliding windows (phenom_kernels.hip).
 
 #include <cmath>
 #include <memory>
@@ -183,5 +183,72 @@ extern "C" int qldpc_phenom_count(const qldpc_code* code, const qldpc_phenom* ph
   a.resid = d_resid;
   a.batch = batch;
   HIP_TRY(qldpc::launch_phenom_count(a, phenom_grid(batch), (hipStream_t)stream));
+  return QLDPC_OK;
+}
+
+extern "C" int qldpc_phenom_window(const qldpc_code* code, int rounds, int64_t batch, int done_start, int done_rounds,
+                                   int done_closed, int done_commit, const void* d_west, int west_format,
+                                   const int32_t* d_witers, void* d_ehat, int ehat_format, int32_t* d_iters,
+                                   int next_start, int next_rounds, const void* d_det, int det_format, void* d_syn,
+                                   int syn_format, void* stream) {
+  // every argument check comes before the first HIP call
+  qldpc::PhenomWindowArgs a{};
+  qldpc::PhenomTabs t{};
+  auto fmt_ok = [](int f) { return f == QLDPC_FMT_BYTES || f == QLDPC_FMT_BITS; };
+  if (!code) return fail(QLDPC_EINVAL, "code is null");
+  if (rounds < 1) return fail(QLDPC_EINVAL, "rounds must be >= 1 (got %d)", rounds);
+  if (batch < 0) return fail(QLDPC_EINVAL, "negative batch");
+  if (done_rounds < 0 || next_rounds < 0 || (done_rounds == 0 && next_rounds == 0))
+    return fail(QLDPC_EINVAL, "neither a decoded window nor a next one");
+  if (int rc = phenom_tabs(code, rounds, &t)) return rc;
+  const int nm = t.n + t.m;
+  if (done_rounds > 0) {
+    if (done_start < 0 || done_start > rounds - done_rounds)
+      return fail(QLDPC_EINVAL, "window [%d, %d + %d) lies outside [0, %d)", done_start, done_start, done_rounds,
+                  rounds);
+    if (done_commit < 1 || done_commit > done_rounds)
+      return fail(QLDPC_EINVAL, "commit = %d rounds of a window of %d", done_commit, done_rounds);
+    if (done_closed && (done_start + done_rounds != rounds || done_commit != done_rounds || next_rounds > 0))
+      return fail(QLDPC_EINVAL, "a closed window ends at the last round, commits all its rounds and has no successor");
+    if (!done_closed && done_start + done_rounds >= rounds)
+      return fail(QLDPC_EINVAL, "an open window has measurement columns in every round: it ends before round %d",
+                  rounds - 1);
+    if (!fmt_ok(west_format) || !fmt_ok(ehat_format)) return fail(QLDPC_EINVAL, "unknown estimate format");
+    if (!d_west || !d_witers || !d_ehat || !d_iters) return fail(QLDPC_EINVAL, "null device buffer");
+    a.has_done = 1;
+    a.commit_off = done_start * nm;
+    a.west_len = done_closed ? done_rounds * t.n + (done_rounds - 1) * t.m : done_rounds * nm;
+    a.commit_len = done_closed ? a.west_len : done_commit * nm;
+    a.corr_off = (done_commit - 1) * nm + t.n;
+  }
+  if (next_rounds > 0) {
+    if (next_start < 0 || next_start > rounds - next_rounds)
+      return fail(QLDPC_EINVAL, "window [%d, %d + %d) lies outside [0, %d)", next_start, next_start, next_rounds,
+                  rounds);
+    if (done_rounds > 0 && next_start != done_start + done_commit)
+      return fail(QLDPC_EINVAL, "the next window starts at round %d, the decoded one committed up to %d", next_start,
+                  done_start + done_commit);
+    if (!fmt_ok(det_format) || !fmt_ok(syn_format)) return fail(QLDPC_EINVAL, "unknown detector / syndrome format");
+    if (t.m && (!d_det || !d_syn)) return fail(QLDPC_EINVAL, "null device buffer");
+    a.has_next = t.m > 0;
+    a.syn_off = next_start * t.m;
+    a.syn_len = next_rounds * t.m;
+  }
+  if (batch == 0) return QLDPC_OK;
+  int max_lds = 0;                                   // the kernel uses no LDS
+  if (int rc = phenom_device(code, &max_lds)) return rc;
+  a.n = t.n, a.m = t.m, a.N = t.N, a.M = t.M;
+  a.west = (const uint8_t*)d_west;
+  a.west_bits = west_format == QLDPC_FMT_BITS;
+  a.witers = d_witers;
+  a.ehat = (uint8_t*)d_ehat;
+  a.eh_bits = ehat_format == QLDPC_FMT_BITS;
+  a.iters = d_iters;
+  a.det = (const uint8_t*)d_det;
+  a.det_bits = det_format == QLDPC_FMT_BITS;
+  a.syn = (uint8_t*)d_syn;
+  a.syn_bits = syn_format == QLDPC_FMT_BITS;
+  a.batch = batch;
+  HIP_TRY(qldpc::launch_phenom_window(a, phenom_grid(batch), (hipStream_t)stream));
   return QLDPC_OK;
 }

@@ -1,6 +1,6 @@
-// phenom_kernels.h — device shot source and outcome counter of the
-// phenomenological noise model (multi-round space-time decoding of one CSS
-// half), shared with capi_phenom.cpp.
+// phenom_kernels.h — device shot source, outcome counter and sliding-window
+// step of the phenomenological noise model (multi-round space-time decoding
+// of one CSS half), shared with capi_phenom.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -50,6 +50,37 @@ struct PhenomCountArgs {
   long long batch;
 };
 
+// One step of sliding-window decoding: commit the decoded
+// window's first columns into the full estimate, add its iteration counts,
+// and cut the next window's syndrome out of the detector row, its first round
+// corrected by the committed measurement estimate. Every buffer is bytes or
+// 64-bit words on its own flag.
+struct PhenomWindowArgs {
+  int n, m;              // H's shape
+  int N, M;              // the full space-time shape (T rounds)
+  // the window just decoded (has_done), already checked against [0, T)
+  int has_done;
+  int commit_off;        // a (n+m): first destination column
+  int commit_len;        // committed columns: C (n+m), closed: R n + (R-1) m
+  int west_len;          // the window estimate's columns N_w
+  int corr_off;          // (C-1) (n+m) + n: the committed measurement estimate u_{a'-1} in west
+  const uint8_t* west;   // [batch][west_len] bytes (west_bits: uint64 [batch][ceil(west_len/64)])
+  int west_bits;
+  const int32_t* witers; // [batch]
+  uint8_t* ehat;         // [batch][N] bytes (eh_bits: uint64 [batch][ceil(N/64)]), merged in place
+  int eh_bits;
+  int32_t* iters;        // [batch] += witers
+  // the next window (has_next)
+  int has_next;
+  int syn_off;           // a' m: first detector of the next window
+  int syn_len;           // R' m
+  const uint8_t* det;    // [batch][M] bytes (det_bits: uint64 [batch][ceil(M/64)])
+  int det_bits;
+  uint8_t* syn;          // [batch][syn_len] bytes (syn_bits: uint64 [batch][ceil(syn_len/64)])
+  int syn_bits;
+  long long batch;
+};
+
 constexpr int kPhenomWaves = 4;  // waves per workgroup (one shot per wave at a time)
 constexpr int kPhenomCounters = 4;
 
@@ -58,5 +89,6 @@ long long phenom_sample_lds_bytes(const PhenomTabs& t);
 long long phenom_count_lds_bytes(const PhenomTabs& t, int kp, bool tab_lds);
 hipError_t launch_phenom_sample(const PhenomSampleArgs& a, int grid, hipStream_t stream);
 hipError_t launch_phenom_count(const PhenomCountArgs& a, int grid, hipStream_t stream);
+hipError_t launch_phenom_window(const PhenomWindowArgs& a, int grid, hipStream_t stream);
 
 }  // namespace qldpc

@@ -27,7 +27,16 @@
 // 2, L r != 0), 0 success. Four int64 counters: failures, logical errors,
 // successes, iteration sum.
 //
-// Both kernels: one wavefront per shot (grid-stride), H's CSR staged once per
+// phenom_window_kernel is the step between two windows of sliding-window
+// decoding: it copies the decoded window's committed columns
+// into the shot's full estimate row at bit offset a (n+m), adds the window's
+// iteration count, and cuts the next window's syndrome from bit offset a' m of
+// the detector row, its first m entries XORed with the committed measurement
+// estimate. Each of the four rows is bytes or words on its own; in words
+// neither offset is a multiple of 64, so reads are funnel shifts and the
+// first and last destination word of a commit are merged with the row's.
+//
+// Sampler and counter: one wavefront per shot (grid-stride), H's CSR staged once per
 // workgroup into LDS as 16-bit column indices (and, for the counter, L's
 // word-major table) — neither depends on T; lane l owns bit l of every 64-bit
 // word (ballots assemble the words); detectors are lane-parallel over checks.
@@ -249,6 +258,103 @@ __global__ void __launch_bounds__(64 * kPhenomWaves) phenom_count_kernel(PhenomC
   }
 }
 
+// One shot's row of a 0/1 vector in either wire format: one byte per entry
+// (`bytes`), else 64-bit words. Entries outside [0, len) read as zero, the
+// words' padding bits included.
+struct BitRow {
+  const uint8_t* bytes;
+  const uint64_t* words;
+  int len;
+  __device__ __forceinline__ uint32_t bit(int pos) const {
+    if (pos < 0 || pos >= len) return 0u;
+    return bytes ? (uint32_t)(bytes[pos] & 1) : (uint32_t)(words[pos >> 6] >> (pos & 63)) & 1u;
+  }
+  // entries [pos, pos + 64) of a words row (pos at any bit, negative too): a
+  // funnel shift of two adjacent words
+  __device__ __forceinline__ uint64_t word(int pos) const {
+    const int nw = (len + 63) >> 6, w0 = pos >> 6, sh = pos & 63;  // pos >> 6 floors
+    const uint64_t lo = (w0 >= 0 && w0 < nw) ? words[w0] : 0;
+    const uint64_t hi = (sh && w0 + 1 >= 0 && w0 + 1 < nw) ? words[w0 + 1] : 0;
+    const uint64_t x = sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
+    const int left = len - pos;  // entries of this word that lie in the row
+    return left >= 64 ? x : (left <= 0 ? 0 : x & ((1ull << left) - 1));
+  }
+};
+
+__device__ __forceinline__ BitRow bit_row(const uint8_t* base, int bits, long long b, int len) {
+  if (bits) return BitRow{nullptr, reinterpret_cast<const uint64_t*>(base) + b * ((len + 63) >> 6), len};
+  return BitRow{base + b * len, nullptr, len};
+}
+
+// dst[dst_off + j] = a[a_off + j] ^ x[x_off + j] for j < len (> 0), by one
+// wave; `x` is clipped by its len (len 0: none). dst is a shot's row, bytes
+// or (dst_bits) words. Words: entries below dst_off in the first word keep
+// what the row holds, and so do those above the end in the last word unless
+// zero_tail, which clears them (the row's padding). The wave owns the row, so
+// the merge is a plain read and write.
+__device__ __forceinline__ void copy_bits(const BitRow& a, int a_off, const BitRow& x, int x_off, uint8_t* dst,
+                                          int dst_bits, int dst_off, int len, bool zero_tail, int lane) {
+  if (!dst_bits) {
+    for (int j = lane; j < len; j += 64) dst[dst_off + j] = (uint8_t)(a.bit(a_off + j) ^ x.bit(x_off + j));
+    return;
+  }
+  uint64_t* dw = reinterpret_cast<uint64_t*>(dst);
+  const int end = dst_off + len, w0 = dst_off >> 6, w1 = (end - 1) >> 6;
+  const bool words = !a.bytes && !x.bytes;           // every source is words: a lane per destination word
+  // word w of the row from `val`, whose bit 0 is source entry j0 = 64 w - dst_off
+  auto store = [&](int w, uint64_t val) {
+    const int j0 = 64 * w - dst_off, left = end - 64 * w;
+    uint64_t in = ~0ull, keep = 0;                   // bits inside [dst_off, end); bits left as the row holds them
+    if (j0 < 0) {
+      in = ~0ull << -j0;
+      keep = ~in;
+    }
+    if (left < 64) {
+      const uint64_t above = ~0ull << left;
+      in &= ~above;
+      if (!zero_tail) keep |= above;
+    }
+    dw[w] = keep ? (dw[w] & keep) | (val & in) : val & in;
+  };
+  if (words) {
+    for (int w = w0 + lane; w <= w1; w += 64) {
+      const int j0 = 64 * w - dst_off;               // negative in the first word
+      store(w, a.word(a_off + j0) ^ x.word(x_off + j0));
+    }
+  } else {                                           // a byte source: a ballot per word
+    for (int w = w0; w <= w1; ++w) {
+      const int j = 64 * w - dst_off + lane;
+      const uint64_t val = __ballot(a.bit(a_off + j) ^ x.bit(x_off + j));
+      if (lane == 0) store(w, val);
+    }
+  }
+}
+
+// Sliding-window step: one wavefront per shot (grid-stride). No tables and no
+// LDS: a lane owns 64-bit words of the shot's rows.
+__global__ void __launch_bounds__(64 * kPhenomWaves) phenom_window_kernel(PhenomWindowArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const BitRow none{nullptr, nullptr, 0};
+  for (long long b = (long long)blockIdx.x * kPhenomWaves + wave; b < a.batch;
+       b += (long long)gridDim.x * kPhenomWaves) {
+    BitRow corr = none;
+    if (a.has_done) {
+      const BitRow west = bit_row(a.west, a.west_bits, b, a.west_len);
+      uint8_t* row = a.eh_bits ? a.ehat + 8 * b * ((a.N + 63) >> 6) : a.ehat + b * a.N;
+      copy_bits(west, 0, none, 0, row, a.eh_bits, a.commit_off, a.commit_len, a.commit_off + a.commit_len == a.N,
+                lane);
+      if (lane == 0) a.iters[b] += a.witers[b];
+      corr = west;
+      corr.len = a.corr_off + a.m;                   // u_{a'-1}: m entries from corr_off
+    }
+    if (a.has_next) {
+      const BitRow det = bit_row(a.det, a.det_bits, b, a.M);
+      uint8_t* row = a.syn_bits ? a.syn + 8 * b * ((a.syn_len + 63) >> 6) : a.syn + b * a.syn_len;
+      copy_bits(det, a.syn_off, corr, a.corr_off, row, a.syn_bits, 0, a.syn_len, true, lane);
+    }
+  }
+}
+
 template <typename K>
 hipError_t launch(K kernel, const void* args, int grid, long long lds, hipStream_t stream) {
   hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -287,6 +393,10 @@ hipError_t launch_phenom_count(const PhenomCountArgs& a, int grid, hipStream_t s
     case 8: return launch(phenom_count_kernel<8>, &a, grid, lds, stream);
     default: return launch(phenom_count_kernel<0>, &a, grid, lds, stream);
   }
+}
+
+hipError_t launch_phenom_window(const PhenomWindowArgs& a, int grid, hipStream_t stream) {
+  return launch(phenom_window_kernel, &a, grid, 0, stream);
 }
 
 }  // namespace qldpc

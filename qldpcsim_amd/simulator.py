@@ -927,6 +927,60 @@ class DevicePhenomHalf:
             return acc, cls, flips, resid
         return (acc, cls) if want_class else acc
 
+    def advance(self, det, ehat, iters, done=None, west=None, witers=None, nxt=None, bits=False):
+        """The step between two windows of sliding-window decoding
+        (spacetime.window_advance on the device, one launch of
+        phenom_window_kernel, no host sync). `done` = (a, R, closed, C), the
+        window just decoded, with its estimate `west` (uint8 [B, N_w] or int64
+        [B, ceil(N_w/64)]) and iteration counts `witers` int32 [B]: its
+        committed columns go into `ehat` (uint8 [B, N] or int64
+        [B, ceil(N/64)], in place) and witers is added to `iters` (int32 [B], in
+        place). `nxt` = (a', R', ..), the next window: returns its syndrome,
+        uint8 [B, R' m] (bits: int64 [B, ceil(R' m / 64)]), cut from `det` (as
+        sample() wrote it) and corrected by the committed measurement estimate.
+        Each buffer's format is its own."""
+        torch = self.torch
+        B = det.shape[0]
+        d_bits, e_bits = det.dtype == torch.int64, ehat.dtype == torch.int64
+        ts = [det, ehat, iters]
+        ok = det.dtype in (torch.uint8, torch.int64) and ehat.dtype in (torch.uint8, torch.int64) and \
+            tuple(det.shape) == ((B, self.MW) if d_bits else (B, self.M)) and \
+            tuple(ehat.shape) == ((B, self.NW) if e_bits else (B, self.N)) and \
+            tuple(iters.shape) == (B,) and iters.dtype == torch.int32
+        w_bits = False
+        if done is not None:
+            a, R, closed, C = (int(v) for v in done)
+            if not (0 <= a and 1 <= R and a + R <= self.T and 1 <= C <= R) or \
+                    (a + R == self.T) != bool(closed) or (closed and C != R):
+                raise ValueError(f"window {tuple(done)} does not lie in [0, {self.T})")
+            Nw = spacetime.window_shape(self.n, self.m, R, closed)[1]
+            ok = ok and west is not None and witers is not None and west.dtype in (torch.uint8, torch.int64)
+            if ok:
+                w_bits = west.dtype == torch.int64
+                ts += [west, witers]
+                ok = tuple(west.shape) == ((B, (Nw + 63) // 64) if w_bits else (B, Nw)) and \
+                    tuple(witers.shape) == (B,) and witers.dtype == torch.int32
+        if nxt is not None:
+            a2, R2 = int(nxt[0]), int(nxt[1])
+            if not (0 <= a2 and 1 <= R2 and a2 + R2 <= self.T) or (done is not None and (closed or a2 != a + C)):
+                raise ValueError(f"next window {tuple(nxt)} does not follow {done} in [0, {self.T})")
+        elif done is None:
+            raise ValueError("advance: neither a decoded window nor a next one")
+        if not ok or not all(t.is_contiguous() and t.device == self.dev for t in ts):
+            raise ValueError("advance: buffers do not match the batch layout")
+        syn = None
+        if nxt is not None:
+            syn = torch.empty((B, (R2 * self.m + 63) // 64), dtype=torch.int64, device=self.dev) if bits else \
+                torch.empty((B, R2 * self.m), dtype=torch.uint8, device=self.dev)
+        if B == 0:
+            return syn
+        P = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        _lib.phenom_window(self.code, self.T, B, done, P(west) if done is not None else None, _fmt(w_bits),
+                           P(witers) if done is not None else None, P(ehat), _fmt(e_bits), P(iters),
+                           None if nxt is None else (a2, R2), P(det), _fmt(d_bits), P(syn), _fmt(bits),
+                           _stream(self.dev))
+        return syn
+
 
 class _HostPhenomHalf:
     """DevicePhenomHalf's two loop operations on the host (the NumPy twins in
@@ -944,12 +998,55 @@ class _HostPhenomHalf:
         acc += (c["failures"], c["logical_errors"], c["successes"], c["iterations"])
         return acc, cls
 
+    def advance(self, det, ehat, iters, done=None, west=None, witers=None, nxt=None, bits=False):
+        m, n = self.H.shape
+        return spacetime.window_advance(n, m, self.T, det, ehat, iters, done, west, witers, nxt)
+
+
+def _window_schedule(T, window, commit):
+    """spacetime.window_schedule of window= / commit= (None without window=),
+    with the ValueErrors every entry point raises."""
+    if window is None:
+        if commit is not None:
+            raise ValueError("commit needs window (sliding-window decoding)")
+        return None
+    return spacetime.window_schedule(T, window, 1 if commit is None else commit)
+
+
+def _decode_windows(recs, s, wins, det, dec, use_dev):
+    """One half-batch window by window: advance (commit the last window, cut
+    and correct the next syndrome), decode, OSD if asked; the last advance
+    commits the closed window. Returns (the full estimate, summed iterations),
+    in the decode path's formats. Nothing here syncs with the host."""
+    B = det.shape[0]
+    if use_dev:
+        torch = s.torch
+        ehat = torch.empty((B, s.NW), dtype=torch.int64, device=s.dev) if dec.packed else \
+            torch.empty((B, s.N), dtype=torch.uint8, device=s.dev)
+        iters = torch.zeros(B, dtype=torch.int32, device=s.dev)
+    else:
+        m, n = s.H.shape
+        ehat = np.zeros((B, spacetime.spacetime_shape(n, m, s.T)[1]), np.uint8)
+        iters = np.zeros(B, np.int32)
+    last, r = None, None
+    for w in wins:
+        syn = s.advance(det, ehat, iters, last, None if r is None else r.ehat, None if r is None else r.iters, w,
+                        bits=dec.packed)
+        h = recs[w[1], w[2]]
+        r = _decode_half(h, syn, dec)
+        if use_dev and dec.osd >= 0:
+            decoders.apply_osd_device(h.H, syn, r, dec.osd)
+        last = w
+    s.advance(det, ehat, iters, last, r.ehat, r.iters, None)
+    return ehat, iters
+
 
 def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float, rounds: int, shots: int = 1000,
                               decType: str = "MS", decIterations: int = 99, decSchedule: str = "F",
                               OSDorder: int = -1, rngSeed: Optional[int] = None, *,
                               batch_size: Optional[int] = None, sampler: Optional[str] = None,
-                              verbose: bool = True, **unsupported) -> dict:
+                              verbose: bool = True, window: Optional[int] = None, commit: Optional[int] = None,
+                              **unsupported) -> dict:
     """Phenomenological noise (extension; no reference counterpart): `rounds`
     = T rounds of syndrome extraction with measurement error probability `q`,
     the last round measured perfectly, decoded over each half's space-time
@@ -987,9 +1084,24 @@ def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float
     logical_error_rate_ci95, logical_error_rate_per_round =
     1 - (1 - LER)^(1/rounds), and rounds, q, p_data.
 
+    `window` = W, `commit` = F (default 1): sliding-window decoding (DESIGN.md
+    §3.14). Each half is decoded W rounds at a time (spacetime.window_schedule):
+    an open window (spacetime.window_matrix) commits its first F rounds into
+    the full estimate, the next window's first detector round is corrected by
+    the committed measurement estimate, and the last window is the closed
+    space-time matrix of the rounds left. Between windows runs one launch of
+    phenom_window_kernel (DevicePhenomHalf.advance); the host does nothing per
+    window. Every decode path applies to the window matrices (at most two per
+    half, each with its own layers and priors), so the decoder's state is
+    bounded by W whatever T is; shots are sampled and scored at full T as
+    without `window`, and the iterations are summed over the windows. T <= W is
+    the whole-matrix decode. The results gain window, commit and windows (their
+    number).
+
     ValueError: decType RELAY / NG / BF, correlated= and channel_weights= (not
     defined for this model), probabilities outside [0, 1), rounds < 1, a pair
-    that is not CSS."""
+    that is not CSS, window < 1, commit outside [1, window], either one not an
+    integer, commit without window."""
     from .logicals import css_logicals
     for k_ in unsupported:
         if k_ in ("correlated", "channel_weights", "correlated_q1", "logical", "samples"):
@@ -1007,6 +1119,7 @@ def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float
         raise ValueError("rounds must be an integer >= 1")
     if not (0.0 <= float(p) < 1.0) or not (0.0 <= float(q) < 1.0):
         raise ValueError("p and q must lie in [0, 1)")
+    wins = _window_schedule(T, window, commit)      # None without window=
     if sampler not in (None, "device", "host"):
         raise ValueError("sampler must be 'device', 'host' or None")
     if int(shots) < 0:
@@ -1023,42 +1136,55 @@ def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float
         # posteriors (OSD) and byte rows cost 9 N bytes per half-shot
         batch_size = ((1 << 18) if osd < 0 else (1 << 14)) if use_dev else (1 << 14)
     dec = _Decode(decType, decIterations, osd, *_path_kw(use_dev, osd))
+    # the matrices decoded: (rounds, closed) -> a _Half per CSS half. Without
+    # window= (and with T <= W) that is the closed matrix of all T rounds
+    kinds = sorted({(R, closed) for _, R, closed, _ in (wins or [(0, T, True, T)])})
     halves = []                                    # X half: (Hz, Lz); Z half: (Hx, Lx)
     for H, L in ((Hz, Lz), (Hx, Lx)):
-        Hst = spacetime.spacetime_matrix(H, T)
-        layers = None if decSchedule == "F" else layerize(Hst, serial=decSchedule == "S")
-        lp, lr = pack_layers(layers, Hst.shape[0])
-        halves.append(_Half(Hst, lp, lr, *_half_prior(spacetime.spacetime_prior(n, H.shape[0], T, p_data, q), False),
-                            (H, L)))
+        recs = {}
+        for R, closed in kinds:
+            Hw = spacetime.spacetime_matrix(H, R) if closed else spacetime.window_matrix(H, R)
+            pr = (spacetime.spacetime_prior if closed else spacetime.window_prior)(n, H.shape[0], R, p_data, q)
+            layers = None if decSchedule == "F" else layerize(Hw, serial=decSchedule == "S")
+            lp, lr = pack_layers(layers, Hw.shape[0])
+            recs[R, closed] = _Half(Hw, lp, lr, *_half_prior(pr, False), (H, L))
+        halves.append(recs)
+    sliding = wins is not None and len(wins) > 1
     show = _progress(f"(p={p:5.2e}, q={q:5.2e}, T={T})", my_shots, verbose and rank == 0)
     if use_dev:
         import torch
         dev = torch.device("cuda", torch.cuda.current_device())
         key = _device_key(seed)
-        src = [DevicePhenomHalf(*h.code, T, dev, k) for h, k in zip(halves, (key, key ^ PHENOM_Z_KEY))]
-        for h in halves:
-            if h.kw:
-                # the vector-prior kernel's limits are met when its launch is
-                # planned: one all-zero detector row per half, so a shape past
-                # them is refused (NotImplementedError) before any shot is drawn
-                _decode_half(h, torch.zeros((1, h.H.shape[0]), dtype=torch.uint8, device=dev),
-                             dec._replace(iters=1, kw={}))
+        src = [DevicePhenomHalf(*recs[kinds[0]].code, T, dev, k) for recs, k in zip(halves, (key, key ^ PHENOM_Z_KEY))]
+        for recs in halves:
+            for h in recs.values():
+                if h.kw:
+                    # the vector-prior kernel's limits are met when its launch is
+                    # planned: one all-zero detector row per matrix, so a shape past
+                    # them is refused (NotImplementedError) before any shot is drawn
+                    _decode_half(h, torch.zeros((1, h.H.shape[0]), dtype=torch.uint8, device=dev),
+                                 dec._replace(iters=1, kw={}))
         accs = [torch.zeros(k, dtype=torch.int64, device=dev) for k in (4, 4, 1)]
     else:
         rng = np.random.default_rng(seed)          # one generator: the X half draws first in every batch
-        src = [_HostPhenomHalf(*h.code, T, rng) for h in halves]
+        src = [_HostPhenomHalf(*recs[kinds[0]].code, T, rng) for recs in halves]
         accs = [np.zeros(k, np.int64) for k in (4, 4, 1)]
     both = accs[2]                                 # shots with both halves class 0
     done = 0
     while done < my_shots:
         B = min(batch_size, my_shots - done)
         cls = []
-        for h, s, acc in zip(halves, src, accs):    # (the two halves and their accumulators)
+        for recs, s, acc in zip(halves, src, accs):  # (the two halves and their accumulators)
             det, E = s.sample(p_data, q, B, bits=dec.packed)
-            r = _decode_half(h, det, dec)
-            if use_dev and osd >= 0:
-                decoders.apply_osd_device(h.H, det, r, osd)
-            cls.append(s.count_device(det, E, r.ehat, r.iters, acc, want_class=True)[1])
+            if sliding:
+                ehat, iters = _decode_windows(recs, s, wins, det, dec, use_dev)
+            else:
+                h = recs[kinds[0]]
+                r = _decode_half(h, det, dec)
+                if use_dev and osd >= 0:
+                    decoders.apply_osd_device(h.H, det, r, osd)
+                ehat, iters = r.ehat, r.iters
+            cls.append(s.count_device(det, E, ehat, iters, acc, want_class=True)[1])
         both += ((cls[0] | cls[1]) == 0).sum()
         done += B
         show(done)
@@ -1072,6 +1198,8 @@ def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float
     res["logical_error_rate_ci95"] = wilson_interval(shots - tot["decSuccessLogical"], shots)
     res["logical_error_rate_per_round"] = 1. - (1. - ler) ** (1. / T)
     res["rounds"], res["q"], res["p_data"] = T, q, p_data
+    if wins is not None:
+        res["window"], res["commit"], res["windows"] = int(window), 1 if commit is None else int(commit), len(wins)
     return res
 
 
@@ -1082,12 +1210,18 @@ def format_phenomenological_results(p, results, shots):
              "     95 % interval      | Failures (X,Z) | Logical errors (X,Z)",
              "----------------------------+-------------+-----+--------------------------------+"
              "------------------------+----------------+----------------------"]
+    win = any("window" in r for r in results)      # sliding-window decoding: a W/F column
+    if win:
+        lines[1] += " | Window W/F"
+        lines[2] += "-+-----------"
     for pT, r in zip(p, results):
         lo, hi = r["logical_error_rate_ci95"]
         lines.append(f"         {pT:10.2e}         |  {r['q']:9.2e}  | {r['rounds']:3} |      {r['logical_error_rate']:7.2e} "
                      f"({r['logical_error_rate_per_round']:7.2e})       |  [{lo:8.2e}, {hi:8.2e}]  |  "
                      f"{r['DecFailures_X']:6},{r['DecFailures_Z']:6} |     {r['logicalErrors_X']:6},"
                      f"{r['logicalErrors_Z']:6}")
+        if win:
+            lines[-1] += f"        |   {r['window']:3}/{r['commit']:<3}" if "window" in r else "        |"
     return "\n".join(lines)
 
 
@@ -1168,7 +1302,8 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
              correlated: Optional[str] = None, correlated_q1: float = 0.49,
              relay_legs: int = 11, relay_leg_iters: int = 60, relay_sols: int = 1, relay_gamma0: float = 0.125,
              relay_gamma_range=(-0.24, 0.66), relay_seed: int = 0, bias: Optional[float] = None,
-             channel_weights=None, rounds: Optional[int] = None, meas_error: Optional[float] = None):
+             channel_weights=None, rounds: Optional[int] = None, meas_error: Optional[float] = None,
+             window: Optional[int] = None, commit: Optional[int] = None):
     """p-sweep + results table (simulator.py:319-347). Returns None like the
     reference unless return_results=True.
 
@@ -1194,6 +1329,11 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
     (meas_error defaults to each point's 2p/3), with a results table of its
     own. "rounds" and "q" enter the results file's meta. meas_error without
     rounds, logical, correlated, bias and channel_weights raise ValueError.
+    window, commit (extension; with rounds): simulate_phenomenological's
+    sliding-window decoding; when given they enter the results file's meta (a
+    resumed sweep with other values is a different sweep) and the table shows
+    W/F. window without rounds, commit without window, window < 1, commit
+    outside [1, window] and non-integers raise ValueError.
 
     resultsFile (extension): a JSON file the sweep writes after every
     p-point; a rerun with the same arguments skips the points already there
@@ -1206,6 +1346,8 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
     _, rank, world = _dist()
     if rounds is None and meas_error is not None:
         raise ValueError("meas_error needs rounds (the phenomenological model)")
+    if rounds is None and (window is not None or commit is not None):
+        raise ValueError("window / commit need rounds (the phenomenological model)")
     if rounds is not None:
         if logical or correlated is not None or bias is not None or channel_weights is not None:
             raise ValueError("rounds= (phenomenological noise) cannot be combined with logical, correlated, bias or "
@@ -1215,10 +1357,14 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
         meta = {"Hx": HxFile, "Hz": HzFile, "shots": shots, "decType": decType, "decIterations": decIterations,
                 "decSchedule": decSchedule, "OSDorder": OSDorder, "rngSeed": rngSeed, "world": world,
                 "sampler": sampler, "rounds": int(rounds), "q": None if meas_error is None else float(meas_error)}
+        win = {}                                   # window= / commit=: passed on and recorded only when given
+        if _window_schedule(rounds, window, commit) is not None:
+            win = {"window": int(window), "commit": 1 if commit is None else int(commit)}
+            meta.update(win)
         results = _sweep(p, meta, resultsFile, on_point, rank, lambda pT: simulate_phenomenological(
             Hx, Hz, pT, 2 * pT / 3 if meas_error is None else meas_error, rounds, shots=shots, decType=decType,
             decIterations=decIterations, decSchedule=decSchedule, OSDorder=OSDorder, rngSeed=rngSeed,
-            batch_size=batch_size, sampler=sampler, verbose=verbose))
+            batch_size=batch_size, sampler=sampler, verbose=verbose, **win))
         if rank == 0:
             print(format_phenomenological_results(p, results, shots))
         return results if return_results else None
@@ -1353,12 +1499,26 @@ def main(argv=None):
     parser.add_argument("--meas-error", type=float, default=argparse.SUPPRESS, dest="meas_error", metavar="Q",
                         help="Phenomenological noise: measurement error probability per check and round "
                              "(default with --rounds: 2p/3).")
+    parser.add_argument("--window", type=int, default=argparse.SUPPRESS, metavar="W",
+                        help="With --rounds: sliding-window decoding, W rounds at a time (the decoder's state is "
+                             "bounded by W whatever T is); T <= W is the whole-matrix decode.")
+    parser.add_argument("--commit", type=int, default=argparse.SUPPRESS, metavar="F",
+                        help="With --window: rounds committed per window, 1 <= F <= W (default 1).")
     args = parser.parse_args(argv)
     if args.bias is not None and args.channel_weights is not None:
         parser.error("--bias and --channel-weights exclude each other")
     rounds, meas_error = getattr(args, "rounds", None), getattr(args, "meas_error", None)
     if meas_error is not None and rounds is None:
         parser.error("--meas-error needs --rounds")
+    window, commit = getattr(args, "window", None), getattr(args, "commit", None)
+    if window is not None and rounds is None:
+        parser.error("--window needs --rounds")
+    if commit is not None and window is None:
+        parser.error("--commit needs --window")
+    if window is not None and window < 1:
+        parser.error("--window must be >= 1")
+    if commit is not None and not (1 <= commit <= window):
+        parser.error("--commit must lie in [1, --window]")
     if rounds is not None:
         if rounds < 1:
             parser.error("--rounds must be >= 1")
@@ -1381,6 +1541,7 @@ def main(argv=None):
                  **({"bias": args.bias} if args.bias is not None else {}),
                  **({"channel_weights": np.load(args.channel_weights)} if args.channel_weights else {}),
                  **({"rounds": rounds, "meas_error": meas_error} if rounds is not None else {}),
+                 **({"window": window, "commit": commit} if window is not None else {}),
                  **({k: getattr(args, k) for k in ("relay_legs", "relay_leg_iters", "relay_sols", "relay_gamma0",
                                                    "relay_gamma_range", "relay_seed")}
                     if args.decType == "RELAY" else {}))

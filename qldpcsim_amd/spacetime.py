@@ -23,11 +23,15 @@ estimate's data blocks) and r = E ^ Ehat:
     class 0  success:         not 2, and L r mod 2 == 0
 When the detectors match, H r = 0 follows by telescoping, so the test
 against L decides membership in the stabiliser group.
+
+Sliding-window decoding (the window_* functions at the end): the decoder
+works on W rounds at a time instead of the whole matrix; see there.
 """
 import numpy as np
 
 __all__ = ["spacetime_shape", "spacetime_matrix", "spacetime_prior", "fold_data", "column_thresholds", "detectors",
-           "sample_phenomenological", "count_phenomenological"]
+           "sample_phenomenological", "count_phenomenological", "window_matrix", "window_prior", "window_shape",
+           "window_schedule", "window_advance"]
 
 
 def _rounds(rounds):
@@ -172,3 +176,101 @@ def count_phenomenological(H, L, rounds, det, E, ehat, iters, want_shots=False):
     if want_shots:
         return out, (cls, _pack_words(F), r)
     return out
+
+
+# ---------------------------------------------------------------------------
+# Sliding-window decoding: the decoder works on a window of W
+# rounds, commits its first F rounds into the full estimate, corrects the next
+# window's first detector round by the committed measurement estimate, and
+# moves on. The last window is the closed space-time matrix of the rounds
+# left and commits all of them.
+# ---------------------------------------------------------------------------
+def _window(window, commit=None):
+    """(W, F) of window= / commit= (commit None: 1), checked."""
+    if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or window < 1:
+        raise ValueError("window must be an integer >= 1")
+    F = 1 if commit is None else commit
+    if isinstance(F, bool) or not isinstance(F, (int, np.integer)) or not (1 <= F <= window):
+        raise ValueError("commit must be an integer in [1, window]")
+    return int(window), int(F)
+
+
+def window_shape(n, m, R, closed):
+    """(rows, columns) of a window of R rounds: the closed one is the
+    space-time matrix's, the open one has measurement columns in every round."""
+    R = _rounds(R)
+    return (R * m, R * n + (R - 1) * m) if closed else (R * m, R * (n + m))
+
+
+def window_matrix(H, W):
+    """The open window of W rounds, int8 [W m, W (n+m)]: the first W rounds of
+    spacetime_matrix(H, W + 1), so every round has its measurement columns and
+    the last round's have degree 1."""
+    W = _rounds(W)
+    H = np.asarray(H)
+    if H.ndim != 2:
+        raise ValueError("H must be a 2-D matrix")
+    m, n = H.shape
+    return np.ascontiguousarray(spacetime_matrix(H, W + 1)[:W * m, :W * (n + m)])
+
+
+def window_prior(n, m, W, p_data, q):
+    """The prior float64 [W (n+m)] of window_matrix: p_data on data columns, q
+    on measurement columns (spacetime_prior's layout)."""
+    W = _rounds(W)
+    return np.ascontiguousarray(spacetime_prior(n, m, W + 1, p_data, q)[:W * (n + m)])
+
+
+def window_schedule(rounds, window, commit=1):
+    """The windows of T rounds decoded W at a time, F committed per window:
+    a list of (start round a, rounds R, closed, commit rounds C). Window k
+    starts at a = k F; if a + W >= T it is the last one: closed (the matrix
+    spacetime_matrix(H, R) of the R = T - a rounds left) and commits all of
+    them; else it is open (window_matrix(H, W)) and commits C = F. T <= W is
+    one closed window of T rounds."""
+    T = _rounds(rounds)
+    W, F = _window(window, commit)
+    out, a = [], 0
+    while a + W < T:
+        out.append((a, W, False, F))
+        a += F
+    out.append((a, T - a, True, T - a))
+    return out
+
+
+def window_advance(n, m, rounds, det, ehat, iters_total, done=None, west=None, witers=None, nxt=None):
+    """NumPy twin of qldpc_phenom_window, the step between two windows.
+    `done` = (a, R, closed, C) is the window just decoded, `west` uint8
+    [B, N_w] its estimate and `witers` [B] its iteration counts: the committed
+    columns west[:, :C (n+m)] (closed: all R n + (R-1) m) are copied to
+    ehat[:, a (n+m) + .] (uint8 [B, N], in place; every other column stays) and
+    witers is added to iters_total (int32 [B], in place). `nxt` = (a', R', ..)
+    is the next window: returns its syndrome uint8 [B, R' m], det[:, a' m :
+    (a' + R') m] with the first m entries XORed by the committed measurement
+    estimate of window round C - 1 (d_a' ^ u_{a'-1}). done None: the plain cut
+    (the first window); nxt None: returns None."""
+    T = _rounds(rounds)
+    nm = n + m
+    det = np.asarray(det)
+    C = None
+    if done is not None:
+        a, R, closed, C = (int(v) for v in done)
+        if not (0 <= a and 1 <= R and a + R <= T and 1 <= C <= R) or (a + R == T) != bool(closed) or \
+                (closed and C != R):
+            raise ValueError(f"window {done} does not lie in [0, {T})")
+        west = np.asarray(west).astype(np.uint8) & 1
+        if west.shape != (ehat.shape[0], window_shape(n, m, R, closed)[1]):
+            raise ValueError("west does not match the window")
+        k = west.shape[1] if closed else C * nm
+        ehat[:, a * nm:a * nm + k] = west[:, :k]
+        iters_total += np.asarray(witers).astype(iters_total.dtype)
+    if nxt is None:
+        return None
+    a2, R2 = int(nxt[0]), int(nxt[1])
+    if not (0 <= a2 and 1 <= R2 and a2 + R2 <= T) or (done is not None and (closed or a2 != a + C)):
+        raise ValueError(f"next window {nxt} does not follow {done} in [0, {T})")
+    syn = (det[:, a2 * m:(a2 + R2) * m].astype(np.uint8) & 1).copy()
+    if done is not None:
+        o = (C - 1) * nm + n
+        syn[:, :m] ^= west[:, o:o + m]
+    return syn
