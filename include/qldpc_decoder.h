@@ -442,6 +442,40 @@ int qldpc_osd_device_ordered_ex(const qldpc_code *code, int64_t count, const uin
                                 double *d_spill_post, int32_t *d_spill_idx, int32_t *d_spill_count,
                                 int64_t spill_cap, void *stream);
 
+/* OSD-CS: combination-sweep OSD, the higher-order search the
+ * reference's OSDdec does not have (its order 1 flips one bit, orders >= 2
+ * equal order 0). No reference counterpart. With perm, J (the greedy set of
+ * decoders.py:329-342, in perm positions) and T (the other positions,
+ * ascending) as in qldpc_osd_decode, the candidates are, in this order:
+ *   the order-0 result e0;
+ *   for k = 0 .. |T|-1: e0 with position T[k] flipped and e_J solved again;
+ *   for a < b < min(lambda, |T|), lexicographic: the same with T[a] and T[b].
+ * The result is the first candidate of strictly smallest Hamming weight (all n
+ * bits). The order-0 result is returned as it is where the syndrome lies
+ * outside H's column space, and (host) where column perm[0] of H is all-zero.
+ * 0 <= lambda <= QLDPC_OSD_CS_MAX_LAMBDA, else QLDPC_EINVAL. Errors and
+ * status values otherwise as the entry point each one is named after.
+ * The host form takes any code. The device forms run osd_block_kernel's range
+ * only: m <= 512, n <= 1087 and no all-zero column in H; any other code, and
+ * options osd_column / osd_hbm, give QLDPC_EUNSUP before any launch. Shots
+ * that qldpc_osd_device_ordered(_ex)_cs leaves to NumPy's order (status 2)
+ * are finished with qldpc_osd_device_cs. */
+#define QLDPC_OSD_CS_MAX_LAMBDA 64
+int qldpc_osd_decode_batch_cs(const qldpc_code *code, int64_t count, const uint8_t *h_syn,
+                              const int32_t *h_perm, int lambda, uint8_t *h_ehat, int nthreads);
+int qldpc_osd_device_cs(const qldpc_code *code, int64_t count, const uint8_t *d_syn, const int32_t *d_perm,
+                        int lambda, uint8_t *d_ehat, int32_t *d_status, void *stream);
+int qldpc_osd_device_ordered_cs(const qldpc_code *code, int64_t count, const uint8_t *d_syn, const double *d_post,
+                                int lambda, uint8_t *d_ehat, int32_t *d_status, int32_t *d_perm,
+                                int32_t *d_tiepos, void *stream);
+int qldpc_osd_device_ordered_ex_cs(const qldpc_code *code, int64_t count, const uint8_t *d_syn,
+                                   const double *d_post, int lambda, uint8_t *d_ehat, int32_t *d_status,
+                                   int32_t *d_perm, int32_t *d_tiepos, double *d_spill_post,
+                                   int32_t *d_spill_idx, int32_t *d_spill_count, int64_t spill_cap, void *stream);
+/* The name of the kernel qldpc_osd_device(_cs) launches for this code
+ * ("osd_block_kernel<17, 8, 2>", "osd_block_cs_kernel<17, 8, 2>", ...), into buf. Measurement and tests. */
+int qldpc_osd_kernel_name(const qldpc_code *code, int cs, char *buf, int len);
+
 /* First element of CPython's `set(range(n)) - set(J)` iteration order
  * (the reference's infoSet[0], decoders.py:344); -1 if empty. */
 int qldpc_cpython_setdiff_first(int n, const int32_t *J, int nJ);

@@ -35,6 +35,8 @@ EXPORTS = (
     "qldpc_hard_decode_device", "qldpc_hard_decode_host", "qldpc_hard_kernel_name", "qldpc_hard_launch_info",
     "qldpc_osd_decode", "qldpc_osd_decode_batch", "qldpc_osd_device", "qldpc_osd_order_device",
     "qldpc_osd_device_ordered", "qldpc_osd_device_ordered_ex", "qldpc_cpython_setdiff_first",
+    "qldpc_osd_decode_batch_cs", "qldpc_osd_device_cs", "qldpc_osd_device_ordered_cs",
+    "qldpc_osd_device_ordered_ex_cs", "qldpc_osd_kernel_name",
     "qldpc_osd_order_host", "qldpc_np_argsort_host", "qldpc_osd_keys_host", "qldpc_libm_eval_host",
     "qldpc_channel_thresholds", "qldpc_channel_sample", "qldpc_channel_sample_ex", "qldpc_count_outcomes",
     "qldpc_count_outcomes_ex",
@@ -108,6 +110,11 @@ def _load():
         "qldpc_osd_order_device": ([P, I64, P, P, P, P], I),
         "qldpc_osd_device_ordered": ([P, I64, P, P, I, P, P, P, P, P], I),
         "qldpc_osd_device_ordered_ex": ([P, I64, P, P, I, P, P, P, P, P, P, P, I64, P], I),
+        "qldpc_osd_decode_batch_cs": ([P, I64, P, P, I, P, I], I),
+        "qldpc_osd_device_cs": ([P, I64, P, P, I, P, P, P], I),
+        "qldpc_osd_device_ordered_cs": ([P, I64, P, P, I, P, P, P, P, P], I),
+        "qldpc_osd_device_ordered_ex_cs": ([P, I64, P, P, I, P, P, P, P, P, P, P, I64, P], I),
+        "qldpc_osd_kernel_name": ([P, I, ctypes.c_char_p, I], I),
         "qldpc_cpython_setdiff_first": ([I, P, I], I),
         "qldpc_osd_order_host": ([P, I64, I, P, P, I], I),
         "qldpc_np_argsort_host": ([P, I, P], I),

@@ -133,10 +133,27 @@ static int osd_hbm_impl(const qldpc_code* code, qldpc::OsdArgs a, int64_t count,
   return QLDPC_OK;
 }
 
+// The reason OSD-CS cannot run this code on the device (it is osd_block_kernel's
+// epilogue: that kernel's range, and no other kernel), or null
+static const char* osd_cs_refusal(const qldpc_code* code) {
+  if (code->m > 512 || code->n > 1087) return "m <= 512 and n <= 1087 (the block kernel's range)";
+  if (code->zero_col) return "an H without all-zero columns";
+  if (opt(&Options::osd_column) != 0 || opt(&Options::osd_hbm) != 0) return "options osd_column and osd_hbm off";
+  return nullptr;
+}
+
+// cs_lambda < 0: the reference's OSD of `order`; else OSD-CS (order unused)
 static int osd_device_impl(const qldpc_code* code, int64_t count, const uint8_t* d_syn, const int32_t* d_perm,
-                           const int32_t* d_tiepos, const double* d_post, int order, uint8_t* d_ehat,
-                           int32_t* d_status, void* stream, const SpillCfg& spill = {}) {
+                           const int32_t* d_tiepos, const double* d_post, int order, int cs_lambda,
+                           uint8_t* d_ehat, int32_t* d_status, void* stream, const SpillCfg& spill = {}) {
   if (!code) return fail(QLDPC_EINVAL, "code is null");
+  const bool cs = cs_lambda >= 0;
+  if (cs_lambda > QLDPC_OSD_CS_MAX_LAMBDA)
+    return fail(QLDPC_EINVAL, "OSD-CS lambda must lie in 0..%d (got %d)", QLDPC_OSD_CS_MAX_LAMBDA, cs_lambda);
+  if (cs) {
+    order = 0;                                       // the base estimate, and the redo pass's semantics
+    if (const char* why = osd_cs_refusal(code)) return fail(QLDPC_EUNSUP, "OSD-CS on the device needs %s", why);
+  }
   if (count < 0) return fail(QLDPC_EINVAL, "negative count");
   if (count == 0) return QLDPC_OK;
   if (code->device < 0) return fail(QLDPC_EHIP, "no HIP device was visible when the code was created");
@@ -144,6 +161,7 @@ static int osd_device_impl(const qldpc_code* code, int64_t count, const uint8_t*
   const int m = code->m, n = code->n;
   hipStream_t st = (hipStream_t)stream;
   qldpc::OsdArgs a = osd_args(code, d_syn, d_perm, d_tiepos, d_post, order, d_ehat, d_status, spill);
+  a.cs_lambda = cs ? cs_lambda : 0;
   int dev = 0, max_lds = 0;
   HIP_TRY(hipGetDevice(&dev));
   HIP_TRY(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
@@ -160,7 +178,7 @@ static int osd_device_impl(const qldpc_code* code, int64_t count, const uint8_t*
   // option osd_column: the column kernel alone (A/B reference, tests).
   const bool column = opt(&Options::osd_column) != 0 || code->zero_col;
   int rt = 1;                                        // block kernel: rows per thread
-  const void* kblk = column ? nullptr : qldpc::select_osd_block_kernel(nw, m, &rt);
+  const void* kblk = column ? nullptr : qldpc::select_osd_block_kernel(nw, m, &rt, cs);
   const int block = std::max(64, (m + 63) / 64 * 64);
   const int bblk = std::max(64, ((m + rt - 1) / rt + 63) / 64 * 64);   // block kernel threads
   const int mr = rt * bblk;                          // its row slots
@@ -171,6 +189,10 @@ static int osd_device_impl(const qldpc_code* code, int64_t count, const uint8_t*
   if (lds_col > max_lds) return fail(QLDPC_EUNSUP, "GPU OSD needs %d B LDS", lds_col);
   HIP_TRY(hipFuncSetAttribute(kcol, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
   if (kblk && lds_blk > max_lds) kblk = nullptr;
+  // OSD-CS has the block kernel alone, and works in its block-loop LDS (Wd .. CT)
+  const size_t cs_room = (size_t)(16 * mr + 8 * nw * (64 + (QLDPC_OSD_PAIRS ? 32 : 0)) + 512);
+  if (cs && (!kblk || qldpc::osd_cs_lds(nw, mr) > cs_room))
+    return fail(QLDPC_EUNSUP, "OSD-CS on the device needs the block kernel (m = %d, n = %d)", m, n);
   if (kblk) HIP_TRY(hipFuncSetAttribute(kblk, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
   // rank(H) and the column bit-vectors: built on first use, after every
   // cheap refusal above (a large HBM-path code is refused without them)
@@ -216,7 +238,20 @@ static int osd_device_impl(const qldpc_code* code, int64_t count, const uint8_t*
 extern "C" int qldpc_osd_device(const qldpc_code* code, int64_t count, const uint8_t* d_syn,
                                 const int32_t* d_perm, int order, uint8_t* d_ehat, int32_t* d_status,
                                 void* stream) {
-  return osd_device_impl(code, count, d_syn, d_perm, nullptr, nullptr, order, d_ehat, d_status, stream);
+  return osd_device_impl(code, count, d_syn, d_perm, nullptr, nullptr, order, -1, d_ehat, d_status, stream);
+}
+
+static int cs_lambda_checked(int lambda) {
+  if (lambda < 0 || lambda > QLDPC_OSD_CS_MAX_LAMBDA)
+    return fail(QLDPC_EINVAL, "OSD-CS lambda must lie in 0..%d (got %d)", QLDPC_OSD_CS_MAX_LAMBDA, lambda);
+  return QLDPC_OK;
+}
+
+extern "C" int qldpc_osd_device_cs(const qldpc_code* code, int64_t count, const uint8_t* d_syn,
+                                   const int32_t* d_perm, int lambda, uint8_t* d_ehat, int32_t* d_status,
+                                   void* stream) {
+  if (const int rc = cs_lambda_checked(lambda)) return rc;
+  return osd_device_impl(code, count, d_syn, d_perm, nullptr, nullptr, 0, lambda, d_ehat, d_status, stream);
 }
 
 extern "C" int qldpc_osd_order_device(const qldpc_code* code, int64_t count, const double* d_post,
@@ -244,16 +279,58 @@ extern "C" int qldpc_osd_device_ordered(const qldpc_code* code, int64_t count, c
                                      nullptr, nullptr, nullptr, 0, stream);
 }
 
+static int osd_ordered_impl(const qldpc_code* code, int64_t count, const uint8_t* d_syn, const double* d_post,
+                            int order, int cs_lambda, uint8_t* d_ehat, int32_t* d_status, int32_t* d_perm,
+                            int32_t* d_tiepos, double* d_spill_post, int32_t* d_spill_idx, int32_t* d_spill_count,
+                            int64_t spill_cap, void* stream) {
+  if (d_spill_count && (!d_spill_post || !d_spill_idx || spill_cap < 0))
+    return fail(QLDPC_EINVAL, "spill buffers incomplete");
+  if (d_spill_count && count > INT32_MAX) return fail(QLDPC_EINVAL, "spill indices are int32");
+  if (cs_lambda >= 0 && code)                        // (refused before the order kernel's launch too)
+    if (const char* why = osd_cs_refusal(code)) return fail(QLDPC_EUNSUP, "OSD-CS on the device needs %s", why);
+  const int rc = qldpc_osd_order_device(code, count, d_post, d_perm, d_tiepos, stream);
+  if (rc != QLDPC_OK) return rc;
+  return osd_device_impl(code, count, d_syn, d_perm, d_tiepos, d_post, order, cs_lambda, d_ehat, d_status, stream,
+                         SpillCfg{d_spill_post, d_spill_idx, d_spill_count, spill_cap});
+}
+
 extern "C" int qldpc_osd_device_ordered_ex(const qldpc_code* code, int64_t count, const uint8_t* d_syn,
                                            const double* d_post, int order, uint8_t* d_ehat, int32_t* d_status,
                                            int32_t* d_perm, int32_t* d_tiepos, double* d_spill_post,
                                            int32_t* d_spill_idx, int32_t* d_spill_count, int64_t spill_cap,
                                            void* stream) {
-  if (d_spill_count && (!d_spill_post || !d_spill_idx || spill_cap < 0))
-    return fail(QLDPC_EINVAL, "spill buffers incomplete");
-  if (d_spill_count && count > INT32_MAX) return fail(QLDPC_EINVAL, "spill indices are int32");
-  const int rc = qldpc_osd_order_device(code, count, d_post, d_perm, d_tiepos, stream);
-  if (rc != QLDPC_OK) return rc;
-  return osd_device_impl(code, count, d_syn, d_perm, d_tiepos, d_post, order, d_ehat, d_status, stream,
-                         SpillCfg{d_spill_post, d_spill_idx, d_spill_count, spill_cap});
+  return osd_ordered_impl(code, count, d_syn, d_post, order, -1, d_ehat, d_status, d_perm, d_tiepos, d_spill_post,
+                          d_spill_idx, d_spill_count, spill_cap, stream);
+}
+
+extern "C" int qldpc_osd_device_ordered_cs(const qldpc_code* code, int64_t count, const uint8_t* d_syn,
+                                           const double* d_post, int lambda, uint8_t* d_ehat, int32_t* d_status,
+                                           int32_t* d_perm, int32_t* d_tiepos, void* stream) {
+  return qldpc_osd_device_ordered_ex_cs(code, count, d_syn, d_post, lambda, d_ehat, d_status, d_perm, d_tiepos,
+                                        nullptr, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int qldpc_osd_device_ordered_ex_cs(const qldpc_code* code, int64_t count, const uint8_t* d_syn,
+                                              const double* d_post, int lambda, uint8_t* d_ehat, int32_t* d_status,
+                                              int32_t* d_perm, int32_t* d_tiepos, double* d_spill_post,
+                                              int32_t* d_spill_idx, int32_t* d_spill_count, int64_t spill_cap,
+                                              void* stream) {
+  if (const int rc = cs_lambda_checked(lambda)) return rc;
+  return osd_ordered_impl(code, count, d_syn, d_post, 0, lambda, d_ehat, d_status, d_perm, d_tiepos, d_spill_post,
+                          d_spill_idx, d_spill_count, spill_cap, stream);
+}
+
+// The block kernel's instance as select_osd_block_kernel picks it (NW row
+// words, SL engine slots, RT rows per thread), or the kernel that runs instead
+extern "C" int qldpc_osd_kernel_name(const qldpc_code* code, int cs, char* buf, int len) {
+  if (!code || !buf || len <= 0) return fail(QLDPC_EINVAL, "null argument");
+  const int m = code->m, n = code->n, nw = qldpc::osd_nw_of((n + 1 + 63) / 64);
+  int rt = 1;
+  const bool hbm = m > 1024 || !nw || opt(&Options::osd_hbm) != 0;
+  const bool column = opt(&Options::osd_column) != 0 || code->zero_col;
+  if (cs && osd_cs_refusal(code)) return fail(QLDPC_EUNSUP, "OSD-CS on the device needs %s", osd_cs_refusal(code));
+  if (hbm) snprintf(buf, len, "osd_hbm_kernel");
+  else if (column || !qldpc::select_osd_block_kernel(nw, m, &rt, cs != 0)) snprintf(buf, len, "osd_kernel<%d>", nw);
+  else snprintf(buf, len, "osd_block%s_kernel<%d, %d, %d>", cs ? "_cs" : "", nw, rt == 1 ? 4 : 8, rt);
+  return QLDPC_OK;
 }

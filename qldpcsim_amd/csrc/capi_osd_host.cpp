@@ -198,21 +198,136 @@ static int osd_one(const qldpc_code* c, const uint8_t* syn, const int32_t* perm,
   return QLDPC_OK;
 }
 
+static int osd_check_perm(const qldpc_code* code, const int32_t* h_perm) {
+  std::vector<char> seen(code->n, 0);
+  for (int i = 0; i < code->n; ++i) {
+    if (h_perm[i] < 0 || h_perm[i] >= code->n || seen[h_perm[i]])
+      return fail(QLDPC_EINVAL, "perm is not a permutation");
+    seen[h_perm[i]] = 1;
+  }
+  return QLDPC_OK;
+}
+
 extern "C" int qldpc_osd_decode(const qldpc_code* code, const uint8_t* h_syn, const int32_t* h_perm, int order,
                                 uint8_t* h_ehat, int32_t* h_J, int32_t* h_J_size, int first_info_index) {
   if (!code || !h_perm || !h_ehat || (!h_syn && code->m)) return fail(QLDPC_EINVAL, "null argument");
-  std::vector<char> seen(code->n, 0);
-  for (int i = 0; i < code->n; ++i) {
-    if (h_perm[i] < 0 || h_perm[i] >= code->n || seen[h_perm[i]]) return fail(QLDPC_EINVAL, "perm is not a permutation");
-    seen[h_perm[i]] = 1;
-  }
+  if (const int rc = osd_check_perm(code, h_perm)) return rc;
   return osd_one(code, h_syn, h_perm, order, h_ehat, h_J, h_J_size, first_info_index);
+}
+
+// ---------------------------------------------------------------------------
+// OSD-CS (combination sweep), the device epilogue's host
+// twin. One elimination of [H[:, perm] | s] with REF's pivot rule gives J (the
+// pivot columns, the greedy set of decoders.py:329-342), T (the rest,
+// ascending) and, in pivot row k, column k of B^-1 H_T and of B^-1 s. The base
+// estimate e0 is the order-0 result; candidates, in order: e0, every single
+// flip of T[k], every pair T[a], T[b] with a < b < min(lambda, |T|); the first
+// of strictly smallest Hamming weight wins. Three cases have no B^-1 and
+// return the order-0 result of osd_one: an all-zero column perm[0] (J's
+// unconditional first entry is no pivot), a syndrome outside H's column space,
+// and rank(H) <= 1 (the reference's IndexError case, QLDPC_ERANGE).
+// ---------------------------------------------------------------------------
+static int osd_cs_one(const qldpc_code* c, const uint8_t* syn, const int32_t* perm, int lambda, uint8_t* ehat) {
+  const int m = c->m, n = c->n, mw = c->mw;
+  if (n == 0) return QLDPC_OK;
+  code_osd_prep(c);
+  const int nw = (n + 1 + 63) / 64;                   // row words, syndrome bit at column n
+  std::vector<uint64_t> R((size_t)std::max(m, 1) * nw, 0);
+  bool col0 = false;
+  for (int i = 0; i < n; ++i) {
+    const uint64_t* cb = &c->col_bits[(size_t)perm[i] * mw];
+    for (int w = 0; w < mw; ++w) {
+      uint64_t bits = cb[w];
+      if (i == 0 && bits) col0 = true;
+      while (bits) {
+        const int r = w * 64 + __builtin_ctzll(bits);
+        bits &= bits - 1;
+        R[(size_t)r * nw + (i >> 6)] |= 1ull << (i & 63);
+      }
+    }
+  }
+  for (int r = 0; r < m; ++r)
+    if (syn[r] & 1) R[(size_t)r * nw + (n >> 6)] |= 1ull << (n & 63);
+  auto order0 = [&]() { return osd_one(c, syn, perm, 0, ehat, nullptr, nullptr, -1); };
+  if (!col0 || c->rank <= 1) return order0();
+  std::vector<int> J;
+  std::vector<char> inJ(n, 0);
+  int xr = 0;
+  for (int i = 0; i < n && xr < c->rank; ++i) {
+    int r = xr;
+    while (r < m && !((R[(size_t)r * nw + (i >> 6)] >> (i & 63)) & 1)) ++r;
+    if (r == m) continue;
+    for (int w = 0; w < nw; ++w) std::swap(R[(size_t)xr * nw + w], R[(size_t)r * nw + w]);
+    const uint64_t* pr = &R[(size_t)xr * nw];
+    for (int t = 0; t < m; ++t)
+      if (t != xr && ((R[(size_t)t * nw + (i >> 6)] >> (i & 63)) & 1))
+        for (int w = i >> 6; w < nw; ++w) R[(size_t)t * nw + w] ^= pr[w];
+    J.push_back(i);
+    inJ[i] = 1;
+    ++xr;
+  }
+  const int nJ = xr;
+  for (int r = nJ; r < m; ++r)
+    if ((R[(size_t)r * nw + (n >> 6)] >> (n & 63)) & 1) return order0();   // s outside H's column space
+  // e_T as a row mask; e0_J[k] = (B^-1 s)[k] + (B^-1 H_T e_T)[k]
+  std::vector<uint64_t> eT(nw, 0);
+  std::vector<int> T;
+  for (int i = 0; i < n; ++i)
+    if (!inJ[i]) {
+      T.push_back(i);
+      if (ehat[perm[i]] & 1) eT[i >> 6] |= 1ull << (i & 63);
+    }
+  const int kw = (nJ + 63) / 64, nT = (int)T.size();
+  std::vector<uint64_t> eJ(kw, 0);
+  for (int k = 0; k < nJ; ++k) {
+    const uint64_t* row = &R[(size_t)k * nw];
+    uint64_t acc = (row[n >> 6] >> (n & 63)) & 1;
+    for (int w = 0; w < nw; ++w) acc ^= (uint64_t)(__builtin_popcountll(row[w] & eT[w]) & 1);
+    if (acc) eJ[k >> 6] |= 1ull << (k & 63);
+  }
+  // column T[k] of B^-1 H_T over the pivot rows, bit-packed
+  auto column = [&](int i, uint64_t* out) {
+    for (int w = 0; w < kw; ++w) out[w] = 0;
+    for (int k = 0; k < nJ; ++k)
+      if ((R[(size_t)k * nw + (i >> 6)] >> (i & 63)) & 1) out[k >> 6] |= 1ull << (k & 63);
+  };
+  // cost change of XOR-ing `col` into e_J: +1 per 0 it sets, -1 per 1 it clears
+  auto delta = [&](const uint64_t* col) {
+    int d = 0;
+    for (int w = 0; w < kw; ++w) d += __builtin_popcountll(col[w]) - 2 * __builtin_popcountll(col[w] & eJ[w]);
+    return d;
+  };
+  auto flip_cost = [&](int i) { return ((eT[i >> 6] >> (i & 63)) & 1) ? -1 : 1; };
+  const int L = std::min(lambda, nT);
+  std::vector<uint64_t> first((size_t)std::max(L, 1) * std::max(kw, 1)), col(std::max(kw, 1));
+  int best = 0, ba = -1, bb = -1;                     // strictly below the base's 0, first such
+  for (int k = 0; k < nT; ++k) {
+    uint64_t* dst = k < L ? &first[(size_t)k * kw] : col.data();
+    column(T[k], dst);
+    const int d = flip_cost(T[k]) + delta(dst);
+    if (d < best) best = d, ba = k, bb = -1;
+  }
+  for (int a = 0; a < L; ++a)
+    for (int b = a + 1; b < L; ++b) {
+      for (int w = 0; w < kw; ++w) col[w] = first[(size_t)a * kw + w] ^ first[(size_t)b * kw + w];
+      const int d = flip_cost(T[a]) + flip_cost(T[b]) + delta(col.data());
+      if (d < best) best = d, ba = a, bb = b;
+    }
+  for (int f : {ba, bb})
+    if (f >= 0) {
+      column(T[f], col.data());
+      for (int w = 0; w < kw; ++w) eJ[w] ^= col[w];
+      ehat[perm[T[f]]] ^= 1;
+    }
+  for (int k = 0; k < nJ; ++k) ehat[perm[J[k]]] = (uint8_t)((eJ[k >> 6] >> (k & 63)) & 1);
+  return QLDPC_OK;
 }
 
 int qldpc_host_thread_budget();                         // np_order.cpp
 
-extern "C" int qldpc_osd_decode_batch(const qldpc_code* code, int64_t count, const uint8_t* h_syn,
-                                      const int32_t* h_perm, int order, uint8_t* h_ehat, int nthreads) {
+// lambda < 0: the reference's OSD of `order`; else OSD-CS with that lambda
+static int osd_batch(const qldpc_code* code, int64_t count, const uint8_t* h_syn, const int32_t* h_perm, int order,
+                     int lambda, uint8_t* h_ehat, int nthreads) {
   if (!code) return fail(QLDPC_EINVAL, "code is null");
   if (count <= 0) return QLDPC_OK;
   if (nthreads <= 0) nthreads = qldpc_host_thread_budget();
@@ -226,8 +341,13 @@ extern "C" int qldpc_osd_decode_batch(const qldpc_code* code, int64_t count, con
     while (true) {
       const int64_t b = next.fetch_add(1);
       if (b >= count || rc.load() != QLDPC_OK) return;
-      const int r = qldpc_osd_decode(code, h_syn + b * m, h_perm + b * n, order, h_ehat + b * n,
-                                     nullptr, nullptr, -1);
+      int r;
+      if (lambda < 0) {
+        r = qldpc_osd_decode(code, h_syn + b * m, h_perm + b * n, order, h_ehat + b * n, nullptr, nullptr, -1);
+      } else {
+        r = osd_check_perm(code, h_perm + b * n);
+        if (r == QLDPC_OK) r = osd_cs_one(code, h_syn + b * m, h_perm + b * n, lambda, h_ehat + b * n);
+      }
       if (r != QLDPC_OK) {
         std::lock_guard<std::mutex> lk(emu);
         if (rc.load() == QLDPC_OK) err = g_err;
@@ -241,4 +361,17 @@ extern "C" int qldpc_osd_decode_batch(const qldpc_code* code, int64_t count, con
   for (auto& t : th) t.join();
   if (rc.load() != QLDPC_OK) g_err = err;
   return rc.load();
+}
+
+extern "C" int qldpc_osd_decode_batch(const qldpc_code* code, int64_t count, const uint8_t* h_syn,
+                                      const int32_t* h_perm, int order, uint8_t* h_ehat, int nthreads) {
+  return osd_batch(code, count, h_syn, h_perm, order, -1, h_ehat, nthreads);
+}
+
+extern "C" int qldpc_osd_decode_batch_cs(const qldpc_code* code, int64_t count, const uint8_t* h_syn,
+                                         const int32_t* h_perm, int lambda, uint8_t* h_ehat, int nthreads) {
+  if (lambda < 0 || lambda > QLDPC_OSD_CS_MAX_LAMBDA)
+    return fail(QLDPC_EINVAL, "OSD-CS lambda must lie in 0..%d (got %d)", QLDPC_OSD_CS_MAX_LAMBDA, lambda);
+  if (count > 0 && (!h_perm || !h_ehat || (!h_syn && code && code->m))) return fail(QLDPC_EINVAL, "null argument");
+  return osd_batch(code, count, h_syn, h_perm, 0, lambda, h_ehat, nthreads);
 }

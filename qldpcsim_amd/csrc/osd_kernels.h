@@ -29,6 +29,8 @@ struct OsdArgs {
   uint32_t* cu_tickets;    // [kOsdCuSlots] per-CU workgroup tickets (engine SIMD choice), or null
   int redo;                // osd_kernel only: process just the shots whose status is 3
                            // (left by osd_block_kernel: syndrome outside H's column space)
+  int cs_lambda;           // osd_block_kernel's OSD-CS instances only: pairs among the first
+                           // min(cs_lambda, |T|) information positions (0 .. 64); `order` is 0
 };
 
 // Reliability order on the device (decoders.py:320-325): NumPy's exact order
@@ -59,7 +61,10 @@ const void* osd_hbm_kernel_ptr();        // __global__ osd_hbm_kernel(OsdArgs, O
 inline size_t osd_hbm_lds(int m, int nwr) { return 8 * (size_t)((m + 63) / 64 * 64) + 24 * (size_t)nwr + 160; }
 
 const void* select_osd_kernel(int nw);  // nw = 64-bit words per row incl. the syndrome column
-const void* select_osd_block_kernel(int nw, int m, int* rows_per_thread);  // block elimination (default), same arguments
+const void* select_osd_block_kernel(int nw, int m, int* rows_per_thread, bool cs = false);  // block elimination (default)
+// bytes of osd_block_kernel's dead block-loop LDS (Wd | Cm | PW | PX | CT) the
+// OSD-CS epilogue needs, for nw row words and mr row slots
+inline size_t osd_cs_lds(int nw, int mr) { return 8 * (size_t)mr + (size_t)mr / 8 + 264 * (size_t)nw + 272; }
 int osd_nw_of(int nw);
 
 }  // namespace qldpc

@@ -448,343 +448,178 @@ __device__ __forceinline__ void osd_apply_rows(uint64_t (&R)[NW], uint64_t cm, c
   }
 }
 
+// ---------------------------------------------------------------------------
+// OSD-CS epilogue of osd_block_kernel: the combination sweep
+// over the fully reduced [Hp | s] the block loop leaves in registers. With J
+// the pivot columns and T the others (ascending), pivot row r holds row r of
+// B^-1 H_T on T's columns and of B^-1 s in the syndrome column. Candidates in
+// order: the order-0 estimate e0; one flip of T[k], every k; two flips T[a],
+// T[b], a < b < L = min(lambda, |T|). Flipping a set F of T columns XORs those
+// columns of B^-1 H_T into e0_J, so its cost change is
+//   sum over F of (1 - 2 e_T) + sum over pivot rows r of x[r] (1 - 2 e0_J[r]),
+// x = the XOR of F's columns. The first candidate of strictly smallest cost
+// wins: the minimum of (cost change + 2048) << 13 | candidate index, index 0 =
+// e0, 1 + c = the flip of perm position c, 2048 + 64 a + b = the pair (a, b).
+//
+// A column over the pivot rows is the ballots of "my row holds a 1" (word q =
+// h * waves + wave covers rows 64 wave + lane + h * blockDim); two scalar
+// popcounts against the same ballots of e0_J give the wave's share of the
+// column's sum, added to an LDS counter per column. The first L columns'
+// ballots stay in LDS; a pair costs one XOR and two popcounts per word.
+//
+// LDS: the block loop's Wd | Cm | PW | PX | CT, dead by now, as
+//   colv [64][Q] u64 | ejm [Q] u64 | tmask [NW] u64 | cnt [64 NW] i32 | tl [64] i32 | red [4] i32
+// with Q = MR / 64 words per column: 8 MR + MR / 8 + 264 NW + 272 bytes of the
+// region's 16 MR + 512 NW + 512 at least (osd_cs_lds, checked by the launcher).
+// ---------------------------------------------------------------------------
+constexpr int kCsIdxBits = 13, kCsBias = 2048, kCsPair = 2048;
+
+template <int NW, int RT>
+__device__ __forceinline__ void osd_cs_epilogue(const OsdArgs& a, const uint64_t (&R)[RT][NW], const bool (&own)[RT],
+                                                const int (&mypos)[RT], int nJ, const int* Jl,
+                                                const unsigned char* inJ, const uint64_t* emask, uint64_t* region,
+                                                const int32_t* perm, uint8_t* ehat) {
+  const int n = a.n, t = threadIdx.x, B = blockDim.x, lane = t & 63;
+  const int nwaves = B >> 6, wave = __builtin_amdgcn_readfirstlane(t >> 6), Q = RT * nwaves;
+  const int L = min(a.cs_lambda, n - nJ);
+  uint64_t* colv = region;
+  uint64_t* ejm = colv + 64 * Q;
+  uint64_t* tmask = ejm + Q;
+  int* cnt = (int*)(tmask + NW);
+  int* tl = cnt + 64 * NW;
+  int* red = tl + 64;
+
+  // e0_J: the k-th pivot row gives entry k, as the order-0 epilogue
+  bool piv[RT];
+  uint32_t ej[RT];
+  uint64_t ejb[RT];
+#pragma unroll
+  for (int h = 0; h < RT; ++h) {
+    piv[h] = own[h] && mypos[h] < nJ;
+    uint64_t acc = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      if (w == (n >> 6)) acc ^= (R[h][w] >> (n & 63)) & 1ull;
+      acc ^= (uint64_t)(__builtin_popcountll(R[h][w] & emask[w]) & 1);
+    }
+    ej[h] = piv[h] ? (uint32_t)(acc & 1ull) : 0u;
+    ejb[h] = __ballot(ej[h] != 0);
+    if (lane == 0) ejm[h * nwaves + wave] = ejb[h];
+  }
+  for (int i0w = 64 * wave; i0w < 64 * NW; i0w += B) {
+    const int i = i0w + lane;
+    const uint64_t bits = __ballot(i < n && !inJ[i]);
+    if (lane == 0) tmask[i0w >> 6] = bits;
+  }
+  for (int i = t; i < 64 * NW; i += B) cnt[i] = 0;
+  if (t == 0) red[0] = kCsBias << kCsIdxBits;         // e0: cost change 0, index 0
+  __syncthreads();
+
+  // every T column's sum into cnt, the first L columns' ballots into colv
+  int k = 0;
+  for (int w = 0; w < NW && 64 * w < n; ++w) {
+    uint64_t rw[RT];
+#pragma unroll
+    for (int h = 0; h < RT; ++h) {
+      uint64_t v = 0;
+#pragma unroll
+      for (int x = 0; x < NW; ++x)
+        if (x == w) v = R[h][x];
+      rw[h] = piv[h] ? v : 0ull;
+    }
+    const uint64_t tm = tmask[w];
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      uint32_t bits = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(tm >> (32 * half)));
+      uint32_t r32[RT];
+#pragma unroll
+      for (int h = 0; h < RT; ++h) r32[h] = (uint32_t)(rw[h] >> (32 * half));
+      while (bits) {
+        bits = (uint32_t)__builtin_amdgcn_readfirstlane((int)bits);
+        k = __builtin_amdgcn_readfirstlane(k);
+        const int b = (int)__builtin_ctz(bits);
+        bits &= bits - 1;
+        const int c = 64 * w + 32 * half + b;
+        int d = 0;
+#pragma unroll
+        for (int h = 0; h < RT; ++h) {
+          const uint64_t bal = __ballot(((r32[h] >> b) & 1u) != 0);
+          d += __builtin_popcountll(bal) - 2 * __builtin_popcountll(bal & ejb[h]);
+          if (k < L && lane == 0) colv[k * Q + h * nwaves + wave] = bal;
+        }
+        if (lane == 0 && d != 0) atomicAdd(&cnt[c], d);
+        if (k < L && t == 0) tl[k] = c;
+        ++k;
+      }
+    }
+  }
+  __syncthreads();
+
+  auto flip_cost = [&](int c) { return ((emask[c >> 6] >> (c & 63)) & 1ull) ? -1 : 1; };
+  int best = 0x7fffffff;
+  for (int c = t; c < n; c += B)
+    if (!inJ[c]) best = min(best, ((cnt[c] + flip_cost(c) + kCsBias) << kCsIdxBits) | (1 + c));
+  for (int idx = t; idx < 64 * L; idx += B) {
+    const int pa = idx >> 6, pb = idx & 63;
+    if (pa < pb && pb < L) {
+      int d = flip_cost(tl[pa]) + flip_cost(tl[pb]);
+      for (int q = 0; q < Q; ++q) {
+        const uint64_t x = colv[pa * Q + q] ^ colv[pb * Q + q];
+        d += __builtin_popcountll(x) - 2 * __builtin_popcountll(x & ejm[q]);
+      }
+      best = min(best, ((d + kCsBias) << kCsIdxBits) | (kCsPair + idx));
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) best = min(best, __shfl_xor(best, off, 64));
+  if (lane == 0) atomicMin(&red[0], best);
+  __syncthreads();
+
+  // the winner's columns into e0_J (pivot rows), its T flips into e_hat
+  const int idx = red[0] & ((1 << kCsIdxBits) - 1);
+  int c1 = -1, c2 = -1;
+  if (idx >= kCsPair) {
+    c1 = tl[(idx - kCsPair) >> 6];
+    c2 = tl[(idx - kCsPair) & 63];
+  } else if (idx > 0) {
+    c1 = idx - 1;
+  }
+#pragma unroll
+  for (int h = 0; h < RT; ++h)
+    if (piv[h]) {
+      uint64_t v1 = 0, v2 = 0;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) {
+        if (c1 >= 0 && w == (c1 >> 6)) v1 = R[h][w];
+        if (c2 >= 0 && w == (c2 >> 6)) v2 = R[h][w];
+      }
+      const uint32_t e = ej[h] ^ (c1 >= 0 ? (uint32_t)(v1 >> (c1 & 63)) & 1u : 0u) ^
+                         (c2 >= 0 ? (uint32_t)(v2 >> (c2 & 63)) & 1u : 0u);
+      ehat[perm[Jl[mypos[h]]]] = (uint8_t)e;
+    }
+  if (t == 0) {
+    if (c1 >= 0) ehat[perm[c1]] ^= 1;
+    if (c2 >= 0) ehat[perm[c2]] ^= 1;
+  }
+}
+
 // SL = rows per wave-0 lane (m <= 64 SL), sized to the code so the state stays
 // in VGPRs; RT = rows per thread (thread t holds rows t, t + blockDim, ..):
 // with 2, a 450-row shot takes 4 waves and a CU holds 4 shots (4 engines, one
 // per SIMD) instead of 2
 template <int NW, int SL, int RT>
 __global__ void __launch_bounds__(64 * SL / RT) __attribute__((amdgpu_waves_per_eu(RT == 2 ? QLDPC_OSD_WPE : 1))) osd_block_kernel(OsdArgs a) {
-  // LDS: inv_perm[n] | J list [m+2] | inJ bytes [n] | emask [NW] | Wd [MR] | Cm [MR] |
-  //      PW [64][NW] | PX [32][NW] (QLDPC_OSD_PAIRS) | CT [64] | pkof [MR] | pidx [MR] | crow [MR] | pk [64] | misc [16] | set table
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  const int m = a.m, n = a.n;
-  const int B = blockDim.x, MR = RT * B;
-  int* inv = (int*)lds;
-  int* Jl = inv + n;
-  unsigned char* inJ = (unsigned char*)(Jl + m + 2);
-  uint64_t* emask = (uint64_t*)(lds + ((4 * (n + m + 2) + n + 15) & ~15));
-  uint64_t* Wd = emask + NW;
-  uint64_t* Cm = Wd + MR;
-  uint64_t* PW = Cm + MR;                            // [64][NW]
-  uint64_t* PX = PW + 64 * NW;                       // [32][NW] pivot pairs (QLDPC_OSD_PAIRS)
-  uint64_t* CT = PX + (QLDPC_OSD_PAIRS ? 32 * NW : 0);   // C of this block's pivot by its column bit
-  int* pkof = (int*)(CT + 64);                       // pivot tag per row: 64 w + k, -1 none
-  int* pidx = pkof + MR;                             // pivot index of each row (m: none)
-  int* crow = pidx + MR;                             // compact position -> row (free rows)
-  int* pk = crow + MR;                               // pivot k: compact position << 6 | column bit
-  int* misc = pk + 64;                               // [0] nJ [1] rank [2] i0 [3] flag [4] done [5] K
-                                                     // [6..7] this block's pivot-column mask
-                                                     // [8..11] SIMD of each wave [12] engine SIMD
-  int* table = misc + 16;
+#define QLDPC_OSD_BLOCK_CS 0
+#include "osd_block_body.inc"
+#undef QLDPC_OSD_BLOCK_CS
+}
 
-  const int t = threadIdx.x;
-  // readfirstlane: `wave` is then known to be wave-uniform, so the engine's
-  // branch is scalar and the counters it updates stay in SGPRs
-  const int lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  const long long shot = blockIdx.x;
-  if (osd_host_shot(a, shot, n, misc + 7)) return;
-  const int32_t* perm = a.perm + shot * (long long)n;
-  const uint8_t* syn = a.syn + shot * (long long)m;
-  uint8_t* ehat = a.ehat + shot * (long long)n;
-
-  for (int i = t; i < n; i += blockDim.x) {
-    inv[perm[i]] = i;
-    inJ[i] = 0;
-  }
-#pragma unroll
-  for (int h = 0; h < RT; ++h) {
-    pkof[t + h * B] = -1;
-    pidx[t + h * B] = m;
-  }
-  // Phase B runs on one "engine" wave while the workgroup's other waves wait
-  // at the barrier, and a CU runs 4 shots (workgroups) whose 4 waves sit on
-  // its 4 SIMDs, wave 0 on a SIMD that rotates between workgroups: engines of
-  // co-resident shots often shared a SIMD. Each workgroup takes a per-CU
-  // ticket and runs its engine on the wave placed on SIMD (ticket mod 4), so
-  // the engines of 4 consecutive workgroups of a CU use 4 SIMDs.
-  if (lane == 0 && wave < 4) misc[8 + wave] = (int)((__builtin_amdgcn_s_getreg(kHwRegHwId) >> 4) & 3u);
-  if (t == 0) {
-    misc[3] = 0;
-    uint32_t tk = 0;
-    if (a.cu_tickets) {
-      const uint32_t hw = __builtin_amdgcn_s_getreg(kHwRegHwId), xcc = __builtin_amdgcn_s_getreg(kHwRegXccId);
-      tk = atomicAdd(a.cu_tickets + (((xcc & 15u) << 8) | ((hw >> 8) & 0xffu)), 1u);
-    }
-    misc[12] = (int)(tk & 3u);
-  }
-  __syncthreads();
-  int engine = 0;
-  {
-    const int target = misc[12], nwv = (int)(blockDim.x >> 6);
-    for (int w = 0; w < 4 && w < nwv; ++w)
-      if (misc[8 + w] == target) engine = w;
-    engine = __builtin_amdgcn_readfirstlane(engine);
-  }
-
-  // my rows of Hp (+ syndrome bit at column n)
-  uint64_t R[RT][NW];
-  bool own[RT];
-#pragma unroll
-  for (int h = 0; h < RT; ++h) {
-    const int r = t + h * B;
-    own[h] = r < m;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) R[h][w] = 0;
-    if (own[h]) {
-      for (int e = a.row_ptr[r]; e < a.row_ptr[r + 1]; ++e) {
-        const int i = inv[a.col_idx[e]];
-#pragma unroll
-        for (int w = 0; w < NW; ++w)
-          if ((i >> 6) == w) R[h][w] |= 1ull << (i & 63);
-      }
-      if (syn[r] & 1) {
-#pragma unroll
-        for (int w = 0; w < NW; ++w)
-          if ((n >> 6) == w) R[h][w] |= 1ull << (n & 63);
-      }
-    }
-  }
-
-  int rank = 0, nJ = 1;
-  bool done = a.rank == 0;                            // rank(H) = 0: IndexError below
-  if (t == 0) {
-    Jl[0] = 0;                                        // column 0 always (decoders.py:329)
-    inJ[0] = 1;
-  }
-
-  // runtime block loop (one copy of phase B); R is only ever indexed by the
-  // compile-time x of the unrolled word loops, so it stays in VGPRs
-  unsigned long long tp[6] = {0, 0, 0, 0, 0, 0};
-  unsigned long long tc = QLDPC_OSD_TIMING ? clock64() : 0;
-#define QLDPC_TICK(k)                            \
-  if constexpr (QLDPC_OSD_TIMING != 0) {         \
-    const unsigned long long now = clock64();    \
-    tp[k] += now - tc;                           \
-    tc = now;                                    \
-  }
-  QLDPC_TICK(0);                                      // setup
-  for (int w = 0; w < NW && 64 * w < n && !done; ++w) {   // done: uniform, re-read per block
-#pragma unroll
-    for (int h = 0; h < RT; ++h)                      // A
-      if (own[h]) {
-        uint64_t v = 0;
-#pragma unroll
-        for (int x = 0; x < NW; ++x)
-          if (x == w) v = R[h][x];
-        Wd[t + h * B] = v;
-      }
-    __syncthreads();
-    QLDPC_TICK(1);
-    if (wave == engine) {                             // B
-      // The engine is its shot's critical path while the SIMD also runs
-      // other shots' phase-D waves: raised priority lets it issue first.
-      if constexpr (QLDPC_OSD_PRIO != 0) __builtin_amdgcn_s_setprio(QLDPC_OSD_PRIO);
-      // the engine works on the rows still free (no pivot yet), compacted:
-      // crow[c] = the c-th free row; earlier pivots are reduced in phase D
-      const int rank0 = rank;
-      int F = 0;
-      // every read of a slot loop issued before the first use (left alone,
-      // each slot's read sat in its own exec-masked block with its own wait:
-      // 8 dependent LDS round trips on the engine's chain, twice per block)
-      int pv[SL];
-#pragma unroll
-      for (int s = 0; s < SL; ++s) pv[s] = pidx[64 * s + lane];     // (64 SL = MR row slots)
-#pragma unroll
-      for (int s = 0; s < SL; ++s) asm volatile("" : "+v"(pv[s]));
-#pragma unroll
-      for (int s = 0; s < SL; ++s) {
-        const int row = 64 * s + lane;
-        const bool fr = row < m && pv[s] == m;
-        const uint64_t bf = __ballot(fr);
-        if (fr) crow[F + __builtin_amdgcn_mbcnt_hi((uint32_t)(bf >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bf, 0))] = row;
-        F += __builtin_popcountll(bf);
-      }
-      uint32_t lo[SL], hi[SL], cl[SL], ch[SL];
-      uint64_t fm[SL];                                // slot s: lanes whose compact row is not yet a pivot
-      uint32_t alo = 0, ahi = 0;                      // columns some free row holds
-      int cr[SL];
-#pragma unroll
-      for (int s = 0; s < SL; ++s) cr[s] = crow[64 * s + lane];     // (this wave's writes above: in order)
-#pragma unroll
-      for (int s = 0; s < SL; ++s) asm volatile("" : "+v"(cr[s]));
-      uint64_t wv[SL];
-#pragma unroll
-      for (int s = 0; s < SL; ++s) wv[s] = Wd[64 * s + lane < F ? cr[s] : 0];
-#pragma unroll
-      for (int s = 0; s < SL; ++s) asm volatile("" : "+v"(wv[s]));
-#pragma unroll
-      for (int s = 0; s < SL; ++s) {
-        const int cp = 64 * s + lane;
-        const uint64_t v = cp < F ? wv[s] : 0ull;
-        lo[s] = (uint32_t)v;
-        hi[s] = (uint32_t)(v >> 32);
-        cl[s] = ch[s] = 0;
-        fm[s] = __ballot(cp < F);
-        alo |= lo[s];
-        ahi |= hi[s];
-      }
-      uint64_t cols = ((uint64_t)wave_or32(ahi) << 32) | wave_or32(alo);
-      if (n - 64 * w < 64) cols &= (1ull << (n - 64 * w)) - 1;
-      if constexpr ((QLDPC_ABLATE_OSD & 2) != 0) cols = 0;
-      const int SF = (F + 63) >> 6;
-      uint64_t pivm = 0;
-      // low half-word columns, then high (each loop's column order ascends)
-      const int nJ0 = nJ;
-      int pkv = 0;
-      int K = block_half_n<SL, SL, false>(SF, lo, hi, cl, ch, fm, (uint32_t)cols, 0, w, lane, rank, nJ, done,
-                                          pivm, a.rank, m, pkv);
-      K = block_half_n<SL, SL, true>(SF, lo, hi, cl, ch, fm, (uint32_t)(cols >> 32), K, w, lane, rank, nJ, done,
-                                     pivm, a.rank, m, pkv);
-#pragma unroll
-      for (int s = 0; s < SL; ++s) {
-        const int cp = 64 * s + lane;
-        if (cp < F) Cm[crow[cp]] = ((uint64_t)ch[s] << 32) | cl[s];
-      }
-      // (one wave: its LDS accesses complete in order, so the reads below see
-      // the writes above)
-      {
-        // the block's J entries (column 0 is J's first entry from the start)
-        const int ivv = 64 * w + (pkv & 63);
-        const int z = (K > 0 && __builtin_amdgcn_readlane(ivv, 0) == 0) ? 1 : 0;
-        if (lane < K) {
-          pk[lane] = pkv;
-          if (ivv != 0) {
-            Jl[nJ0 + lane - z] = ivv;
-            inJ[ivv] = 1;
-          }
-          const int e = pkv;
-          const int row = crow[e >> 6];
-          CT[e & 63] = Cm[row] ^ (1ull << lane);      // reduced pivot k = its own row + C
-          pkof[row] = 64 * w + lane;
-          pidx[row] = rank0 + lane;                   // REF moves the k-th pivot row to row k
-        }
-        if (lane == 0) {
-          misc[0] = nJ;
-          misc[1] = rank;
-          misc[4] = done;
-          misc[5] = K;
-          misc[6] = (int)(uint32_t)pivm;
-          misc[7] = (int)(uint32_t)(pivm >> 32);
-        }
-      }
-      if constexpr (QLDPC_OSD_PRIO != 0) __builtin_amdgcn_s_setprio(0);
-    }
-    QLDPC_TICK(2);
-    __syncthreads();
-    QLDPC_TICK(3);
-    nJ = __builtin_amdgcn_readfirstlane(misc[0]);    // (LDS loads count as per-lane values)
-    rank = __builtin_amdgcn_readfirstlane(misc[1]);
-    done = __builtin_amdgcn_readfirstlane(misc[4]) != 0;
-    const int K = __builtin_amdgcn_readfirstlane(misc[5]);
-    const uint64_t pivm = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(misc[7]) << 32) |
-                          (uint32_t)__builtin_amdgcn_readfirstlane(misc[6]);
-    // C: pivot rows publish their words w.. as they were at the block start
-    int tag[RT];
-#pragma unroll
-    for (int h = 0; h < RT; ++h) {
-      tag[h] = own[h] ? pkof[t + h * B] : -1;
-      if (tag[h] >= 0 && (tag[h] >> 6) == w) {
-        uint64_t* dst = PW + (tag[h] & 63) * NW;
-#pragma unroll
-        for (int x = 0; x < NW; ++x)
-          if (x >= w) dst[x] = R[h][x];
-      }
-    }
-    __syncthreads();
-    if constexpr (QLDPC_OSD_PAIRS != 0) {
-      // pair rows PX[j] = PW[2j] ^ PW[2j + 1], words w.. (pairs of this block's pivots)
-      if (K > 1) {                                    // (uniform)
-        const int np = K >> 1, nx = NW - w;
-        for (int i = t; i < np * nx; i += B) {
-          const int j = i / nx, x = w + i - j * nx;
-          PX[j * NW + x] = PW[2 * j * NW + x] ^ PW[(2 * j + 1) * NW + x];
-        }
-        __syncthreads();
-      }
-    }
-    QLDPC_TICK(4);
-    // D: every row applies its combination of this block's pivot rows
-#pragma unroll
-    for (int h = 0; h < RT; ++h)
-    if (own[h] && K > 0 && (QLDPC_ABLATE_OSD & 1) == 0) {
-      uint64_t cm;
-      if (tag[h] >= 0 && (tag[h] >> 6) < w) {
-        // a pivot row of an earlier block: clear this block's pivot columns
-        // from it. Its result is unique (word w + the reduced block pivots it
-        // holds a 1 for), so C = XOR of those pivots' C (no engine pass).
-        uint64_t v = 0;
-#pragma unroll
-        for (int x = 0; x < NW; ++x)
-          if (x == w) v = R[h][x];
-        cm = osd_gather_xor4(CT, v & pivm);
-      } else {
-        cm = Cm[t + h * B];
-      }
-      // (per-lane gathers of the pivot rows: a uniform loop over all K with
-      // broadcast reads measured 2x slower, VALU-bound). The word range is a
-      // compile-time one per block (switch on w), so a pivot row's words are
-      // all read before any XOR — one LDS round trip per pivot row instead
-      // of one per word behind a uniform branch.
-      osd_apply_rows<NW>(R[h], cm, PW, PX, w);
-    }
-    QLDPC_TICK(5);
-  }
-  if constexpr (QLDPC_OSD_TIMING != 0) {
-    if (lane == 0 && (wave == engine || wave == (engine ^ 1)))   // [0]: the engine wave, [1]: another
-      for (int k = 0; k < 6; ++k) atomicAdd(a.prof + 8 * (wave == engine ? 0 : 1) + k, tp[k]);
-  }
-#undef QLDPC_TICK
-  if (rank < a.rank) {                              // greedy loop runs past column n-1
-    if (t == 0) a.status[shot] = 1;                 // (the reference raises IndexError)
-    return;
-  }
-  // a row left without pivot is zero on every column of H; a 1 in its
-  // syndrome column means s is outside H's column space (status 3)
-  int mypos[RT];
-#pragma unroll
-  for (int h = 0; h < RT; ++h) {
-    mypos[h] = own[h] ? pidx[t + h * B] : m;
-    uint64_t sbit = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w)
-      if (w == (n >> 6)) sbit = (R[h][w] >> (n & 63)) & 1ull;   // (compile-time R index)
-    if (own[h] && mypos[h] >= nJ && sbit) misc[3] = 1;
-  }
-  if (t == 0) {
-    int i0 = -1;
-    if (a.order == 1 && nJ < n) i0 = first_setdiff(n, inJ, nJ, table);   // (decoders.py:344)
-    misc[2] = i0;
-  }
-  __syncthreads();
-  const int i0 = misc[2];
-  if (misc[3]) {
-    if (t == 0) a.status[shot] = 3;
-    return;
-  }
-  // information-set values e_I (e_perm = e_hat[perm], decoders.py:345)
-  for (int i0w = 64 * wave; i0w < 64 * NW; i0w += blockDim.x) {
-    const int i = i0w + lane;
-    const bool bit = i < n && !inJ[i] && (ehat[perm[i]] & 1);
-    const uint64_t bits = __ballot(bit);
-    if (lane == 0) emask[i0w >> 6] = bits;
-  }
-  __syncthreads();
-  if (t == 0 && i0 >= 0) emask[i0 >> 6] ^= 1ull << (i0 & 63);   // order-1 flip (:349-350)
-  __syncthreads();
-  // e_J = (T sJ)[:|J|]: the k-th pivot row gives entry k   (decoders.py:352-358)
-#pragma unroll
-  for (int h = 0; h < RT; ++h)
-    if (own[h] && mypos[h] < nJ) {
-      uint64_t acc = 0;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        if (w == (n >> 6)) acc ^= (R[h][w] >> (n & 63)) & 1ull;   // T s (augmented column)
-        acc ^= (uint64_t)(__builtin_popcountll(R[h][w] & emask[w]) & 1);
-      }
-      ehat[perm[Jl[mypos[h]]]] = (uint8_t)(acc & 1ull);         // e_hat[perm] = ... (:368)
-    }
-  if (t == 0 && i0 >= 0) ehat[perm[i0]] ^= 1;
-  if (t == 0) a.status[shot] = 0;
+// the same elimination, finished by the OSD-CS epilogue (osd_cs_epilogue)
+template <int NW, int SL, int RT>
+__global__ void __launch_bounds__(64 * SL / RT) __attribute__((amdgpu_waves_per_eu(RT == 2 ? QLDPC_OSD_WPE : 1))) osd_block_cs_kernel(OsdArgs a) {
+#define QLDPC_OSD_BLOCK_CS 1
+#include "osd_block_body.inc"
+#undef QLDPC_OSD_BLOCK_CS
 }
 
 // ---------------------------------------------------------------------------
@@ -1352,22 +1187,28 @@ __global__ void __launch_bounds__(1024) osd_hbm_kernel(OsdArgs a, OsdHbmArgs h) 
 
 const void* osd_hbm_kernel_ptr() { return (const void*)&osd_hbm_kernel; }
 
-template <int NW>
+template <int NW, bool CS>
 static const void* osd_block_by_rows(int m, int* rt) {
   *rt = m <= 256 ? 1 : 2;
-  if (m <= 256) return (const void*)&osd_block_kernel<NW, 4, 1>;
-  if (m <= 512) return (const void*)&osd_block_kernel<NW, 8, 2>;
+  if (m <= 256) return CS ? (const void*)&osd_block_cs_kernel<NW, 4, 1> : (const void*)&osd_block_kernel<NW, 4, 1>;
+  if (m <= 512) return CS ? (const void*)&osd_block_cs_kernel<NW, 8, 2> : (const void*)&osd_block_kernel<NW, 8, 2>;
   return nullptr;                                   // (the engine state would spill: column kernel)
 }
 
-// block kernel configurations whose state fits the VGPR budget without
-// spills (m <= 512 rows, n <= 1087 columns); null -> osd_kernel
-const void* select_osd_block_kernel(int nw, int m, int* rows_per_thread) {
+template <bool CS>
+static const void* osd_block_by_words(int nw, int m, int* rows_per_thread) {
   if (nw <= 0) return nullptr;
-  if (nw <= 4) return osd_block_by_rows<4>(m, rows_per_thread);
-  if (nw <= 9) return osd_block_by_rows<9>(m, rows_per_thread);
-  if (nw <= 17) return osd_block_by_rows<17>(m, rows_per_thread);
+  if (nw <= 4) return osd_block_by_rows<4, CS>(m, rows_per_thread);
+  if (nw <= 9) return osd_block_by_rows<9, CS>(m, rows_per_thread);
+  if (nw <= 17) return osd_block_by_rows<17, CS>(m, rows_per_thread);
   return nullptr;
+}
+
+// block kernel configurations whose state fits the VGPR budget without
+// spills (m <= 512 rows, n <= 1087 columns); null -> osd_kernel. cs: the
+// OSD-CS instance of the same configuration
+const void* select_osd_block_kernel(int nw, int m, int* rows_per_thread, bool cs) {
+  return cs ? osd_block_by_words<true>(nw, m, rows_per_thread) : osd_block_by_words<false>(nw, m, rows_per_thread);
 }
 
 int osd_nw_of(int nw) { return nw <= 4 ? 4 : nw <= 9 ? 9 : nw <= 17 ? 17 : nw <= 33 ? 33 : 0; }

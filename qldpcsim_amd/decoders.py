@@ -53,7 +53,7 @@ __all__ = ["MS_decoder", "BP_decoder", "NG_decoder", "BF_decoder", "OSDdec", "de
            "Relay_decoder", "RelayConfig", "relay_gammas",
            "osd_perm", "pack_bits", "unpack_bits",
            "osd_perms", "apply_osd", "apply_osd_device", "apply_osd_device_many", "osd_device_stage",
-           "osd_device_finish", "osd_host_orders", "osd_status_check", "numpy_order_pinned",
+           "osd_device_finish", "osd_host_orders", "osd_status_check", "osd_method_checked", "numpy_order_pinned",
            "numpy_libm_pinned", "parity_pins"]
 
 
@@ -125,7 +125,7 @@ def unpack_bits(words, k):
 
 def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, eps=1e-9,
                  want_post=False, osd_order=-1, layer_ptr=None, layer_rows=None, stream=None,
-                 out=None, ehat_bits=False, prior_mask=None, p_masked=None, relay=None, prior=None):
+                 out=None, ehat_bits=False, prior_mask=None, p_masked=None, relay=None, prior=None, osd_method="ref"):
     """Decode a batch of syndromes of one matrix on the GPU.
 
     syndromes: uint8 [B, m] NumPy array (host; staged, synchronous) or a
@@ -155,6 +155,12 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
     decode_vprior_kernel on both paths, with the limits of
     the prior_mask kernel; not combinable with prior_mask, relay= or NG / BF.
     A uniform vector gives the scalar decode's result bit for bit.
+    `osd_method` (with osd_order >= 0): "ref" is the reference's OSDdec of that
+    order (order 1 flips one bit, orders >= 2 equal order 0); "cs" is OSD-CS,
+    the combination sweep with lambda = osd_order in 0..64:
+    every single flip of an information position and every pair among the
+    first lambda, lowest Hamming weight wins. MS / BP only: "cs" with
+    osd_order < 0, with RELAY, NG or BF, or an unknown method raises ValueError.
     `algo="RELAY"` with `relay=RelayConfig(...)`: relay min-sum (DESIGN.md
     §3.11), flooding only. `max_iter` is ignored: the legs carry their own
     counts (relay.leg_iters). layers other than flooding, prior_mask and
@@ -162,6 +168,7 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
     caller can run OSDdec on the failures). The result's `info` (`found`,
     `best_leg`) says how many solutions each shot met and which leg's was kept.
     """
+    osd_method_checked(osd_method, osd_order, algo)
     if prior is not None:
         if p is not None:
             raise ValueError("give either p (one scalar prior) or prior (one per column), not both")
@@ -213,7 +220,7 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
             *head, *ins, float(p), int(max_iter), float(beta), float(eps), *outs))
     if host and osd_order >= 0:
         syn, post = held[:2]
-        apply_osd(H, syn, res.ehat, post, res.flags, osd_order)
+        apply_osd(H, syn, res.ehat, post, res.flags, osd_order, **_method_kw("method", osd_method))
     return res
 
 
@@ -373,6 +380,31 @@ def _device_batch(H, syndromes, make, made_from, want_post, osd=False, prior_mas
     outs = (res.ehat.data_ptr(), _lib.FMT_BITS if ehat_bits else _lib.FMT_BYTES, res.iters.data_ptr(), *post_p,
             res.flags.data_ptr(), *info_p, st)
     return code, handle, res, (syn.data_ptr(), syn_fmt, B), mask, outs, (syn, res.post, prior_mask)
+
+
+OSD_METHODS = ("ref", "cs")
+OSD_CS_MAX_LAMBDA = 64       # QLDPC_OSD_CS_MAX_LAMBDA
+
+
+def osd_method_checked(method, order, algo="MS"):
+    """The OSD method of a call, checked: "ref" (the reference's OSDdec) or "cs"
+    (OSD-CS, `order` = lambda). ValueError for an unknown method, and for "cs"
+    without an order in 0..64 or with a decoder that has no OSD step."""
+    if method not in OSD_METHODS:
+        raise ValueError(f"osd_method must be one of {OSD_METHODS}, got {method!r}")
+    if method == "cs":
+        if algo not in ("MS", "BP"):
+            raise ValueError(f'osd_method="cs" needs a decoder with posteriors (MS or BP), not {algo}')
+        if not 0 <= int(order) <= OSD_CS_MAX_LAMBDA:
+            raise ValueError(f'osd_method="cs" takes its lambda from the OSD order: 0..{OSD_CS_MAX_LAMBDA}, '
+                             f"got {order}")
+    return method
+
+
+def _method_kw(name, method):
+    """The OSD method as a keyword of that name, given only when it is not the
+    default: a "ref" call is the call earlier releases made."""
+    return {} if method == "ref" else {name: method}
 
 
 def osd_perm(posteriorLLRs):
@@ -579,21 +611,22 @@ def _pinned(key, shape, dtype):
     return buf[:need].view(*shape)
 
 
-def apply_osd_device(H, syn, res, order, stream=None):
+def apply_osd_device(H, syn, res, order, stream=None, method="ref"):
     """GPU OSD for the non-converged shots of a device decode `res`
     (DecodeResult of torch tensors, with posteriors). The reliability order is
     NumPy's, computed on the device (qldpc_osd_device_ordered); only the shots
     it leaves to NumPy (NaN posteriors, x86-simd-sort's std::sort fallback)
     have their posteriors copied to the host. Updates res.ehat in place. See
-    apply_osd_device_many for several decodes at once."""
-    return apply_osd_device_many([(H, syn, res)], order, stream)[0]
+    apply_osd_device_many for several decodes at once. `method`: "ref", or "cs"
+    for OSD-CS with lambda = `order` (decode_batch's osd_method)."""
+    return apply_osd_device_many([(H, syn, res)], order, stream, method)[0]
 
 
-def apply_osd_device_many(items, order, stream=None):
+def apply_osd_device_many(items, order, stream=None, method="ref"):
     """apply_osd_device for several (H, syn, res) decodes (the X and Z halves
     of a batch): every device order and elimination is queued first."""
-    staged = osd_device_stage(items, stream, order=order)
-    osd_device_finish(items, staged, order, stream)
+    staged = osd_device_stage(items, stream, order=order, method=method)
+    osd_device_finish(items, staged, order, stream, method=method)
     with _on_stream(stream):                      # the status check reads on the same stream
         osd_status_check(items)
     return [r.ehat for _, _, r in items]
@@ -661,7 +694,7 @@ def release_workspaces():
     _lib.release_hbm_workspaces()
 
 
-def osd_device_stage(items, stream=None, slot0=0, order=0):
+def osd_device_stage(items, stream=None, slot0=0, order=0, method="ref"):
     """First half of the device OSD: find each decode's non-converged shots
     (one device sync), then queue asynchronously on the device: the
     reliability order (decoders.py:320-325) and the elimination of every shot
@@ -669,11 +702,13 @@ def osd_device_stage(items, stream=None, slot0=0, order=0):
     pinned host buffer. Shots that need NumPy's order (status 2) are finished
     by osd_device_finish. `slot0` selects the pinned buffer set (pipelined
     callers alternate). OSD_POLICY["host_order"] (A/B, or an unpinned NumPy)
-    or n > 2048 sends every shot through the host order (osd_perms)."""
+    or n > 2048 sends every shot through the host order (osd_perms).
+    `method` as apply_osd_device's; osd_device_finish takes the same one."""
+    osd_method_checked(method, order)
     staged = []
     with _on_stream(stream):
         for slot, (H, syn, res) in enumerate(items):
-            staged.append(_osd_stage_one(H, syn, res, slot0 + slot, order))
+            staged.append(_osd_stage_one(H, syn, res, slot0 + slot, order, method))
     return staged
 
 
@@ -699,7 +734,7 @@ class _Staged:
     cap: int = 0
 
 
-def _osd_stage_one(H, syn, res, slot, order):
+def _osd_stage_one(H, syn, res, slot, order, method="ref"):
     import torch
     if res.post is None:
         raise ValueError("apply_osd_device needs the decode's posteriors (want_post=True)")
@@ -740,7 +775,8 @@ def _osd_stage_one(H, syn, res, slot, order):
         sp_idx = _device_buf(("spill_idx", slot), (cap,), torch.int32, dev)
         sp_cnt = _device_buf(("spill_cnt", slot), (1,), torch.int32, dev)
         sp_cnt.zero_()
-        _lib.check(_lib.lib.qldpc_osd_device_ordered_ex(
+        ordered = _lib.lib.qldpc_osd_device_ordered_ex_cs if method == "cs" else _lib.lib.qldpc_osd_device_ordered_ex
+        _lib.check(ordered(
             code.handle, k, syn_b.data_ptr(), post_b.data_ptr(), int(order), e_b.data_ptr(),
             status.data_ptr(), perm.data_ptr(), tie.data_ptr(), sp_post.data_ptr(), sp_idx.data_ptr(),
             sp_cnt.data_ptr(), cap, st))
@@ -775,7 +811,7 @@ def _device_buf(key, shape, dtype, dev):
     return buf[:need].view(shape)
 
 
-def osd_device_finish(items, staged, order, stream=None, host=None):
+def osd_device_finish(items, staged, order, stream=None, host=None, method="ref"):
     """Second half: for each staged decode, the shots the device order could
     not decide (status 2) get NumPy's reliability order on the host (their
     posteriors only, pinned copies) and the GPU elimination; then the
@@ -789,7 +825,7 @@ def osd_device_finish(items, staged, order, stream=None, host=None):
     with _on_stream(stream):
         for (H, syn, res), sg, hr in zip(items, staged, host):
             if sg is not None:
-                _osd_finish_device(H, syn, res, sg, hr, order)
+                _osd_finish_device(H, syn, res, sg, hr, order, method)
     return staged
 
 
@@ -851,7 +887,7 @@ def osd_host_orders(staged):
     return out
 
 
-def _osd_finish_device(H, syn, res, sg, hr, order):
+def _osd_finish_device(H, syn, res, sg, hr, order, method="ref"):
     import torch
     e_b, status = sg.e_b, sg.status
     dev = res.ehat.device
@@ -867,8 +903,9 @@ def _osd_finish_device(H, syn, res, sg, hr, order):
         e_r = e_b.index_select(0, idx)
         st2 = torch.empty(k2, dtype=torch.int32, device=dev)
         st = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(_lib.lib.qldpc_osd_device(code.handle, k2, syn_r.data_ptr(), perms.data_ptr(), int(order),
-                                             e_r.data_ptr(), st2.data_ptr(), st))
+        device = _lib.lib.qldpc_osd_device_cs if method == "cs" else _lib.lib.qldpc_osd_device
+        _lib.check(device(code.handle, k2, syn_r.data_ptr(), perms.data_ptr(), int(order), e_r.data_ptr(),
+                          st2.data_ptr(), st))
         e_b.index_copy_(0, idx, e_r)
         status.index_copy_(0, idx, st2)
     res.ehat.index_copy_(0, sg.bad, e_b)
@@ -897,11 +934,13 @@ def osd_status_raise(flags):
         raise IndexError("OSD: column basis search ran past the last column")
 
 
-def apply_osd(H, syn, ehat, post, flags, order, nthreads=None):
+def apply_osd(H, syn, ehat, post, flags, order, nthreads=None, method="ref"):
     """OSD post-step for every non-converged row (decoders.py:179-180, :287-288).
 
-    ehat (uint8 [B, n]) is updated in place.
+    ehat (uint8 [B, n]) is updated in place. `method`: "ref", or "cs" for
+    OSD-CS with lambda = `order` (decode_batch's osd_method).
     """
+    osd_method_checked(method, order)
     idx = np.flatnonzero((np.asarray(flags) & _lib.FLAG_CONVERGED) == 0)
     if idx.size == 0:
         return ehat
@@ -911,9 +950,9 @@ def apply_osd(H, syn, ehat, post, flags, order, nthreads=None):
     perms = np.ascontiguousarray(osd_perms(post[idx]), dtype=np.int32)
     sub_syn = np.ascontiguousarray(syn[idx], dtype=np.uint8)
     sub_e = np.ascontiguousarray(ehat[idx], dtype=np.uint8)
-    _lib.check(_lib.lib.qldpc_osd_decode_batch(code.handle, idx.size, _lib.ptr(sub_syn),
-                                               _lib.ptr(perms), int(order), _lib.ptr(sub_e),
-                                               int(nthreads or hostcores.rank_cores())))
+    batch = _lib.lib.qldpc_osd_decode_batch_cs if method == "cs" else _lib.lib.qldpc_osd_decode_batch
+    _lib.check(batch(code.handle, idx.size, _lib.ptr(sub_syn), _lib.ptr(perms), int(order), _lib.ptr(sub_e),
+                     int(nthreads or hostcores.rank_cores())))
     ehat[idx] = sub_e
     return ehat
 
@@ -935,9 +974,11 @@ def _row(H, syndrome):
     return syndrome.reshape(1, m)
 
 
-def _soft(H, syndrome, p, max_iter, layers, algo, beta, eps, OSDorder, dtype):
+def _soft(H, syndrome, p, max_iter, layers, algo, beta, eps, OSDorder, dtype, osd_method="ref"):
     """MS_decoder / BP_decoder of a non-empty shot: (e_hat of `dtype`, n_iter)."""
     row = _row(H, syndrome)
+    if osd_method != "ref" or OSDorder >= 0:
+        osd_method_checked(osd_method, OSDorder, algo)
     if int(max_iter) < 1:
         # the reference's iteration loop never binds e_hat (decoders.py:153/:182)
         raise UnboundLocalError("local variable 'e_hat' referenced before assignment")
@@ -949,27 +990,31 @@ def _soft(H, syndrome, p, max_iter, layers, algo, beta, eps, OSDorder, dtype):
                      want_post=True, layer_ptr=lp, layer_rows=lr, prior=p if vec else None)
     e_hat = r.ehat[0].astype(dtype)
     if OSDorder >= 0 and not r.converged[0]:       # (:179-180, :287-288)
-        e_hat = OSDdec(H, e_hat, syndrome, r.post[0], OSDorder)
+        e_hat = OSDdec(H, e_hat, syndrome, r.post[0], OSDorder, **_method_kw("osd_method", osd_method))
     return e_hat, int(r.iters[0])
 
 
 def MS_decoder(H: np.ndarray, syndrome: np.ndarray, p: float, max_iter: int = 99,
                layers: Optional[list] = None, beta: float = 0.75, OSDorder: int = -1,
-               eps: float = 1e-9):
-    """Normalized min-sum (reference decoders.py:110-182) on the GPU."""
+               eps: float = 1e-9, osd_method: str = "ref"):
+    """Normalized min-sum (reference decoders.py:110-182) on the GPU.
+    osd_method="cs": OSD-CS with lambda = OSDorder (decode_batch)."""
     H, syndrome, bare = _shot(H, syndrome)
     if bare is not None:
         return bare
-    return _soft(H, syndrome, p, max_iter, layers, "MS", beta, eps, OSDorder, np.int8)
+    return _soft(H, syndrome, p, max_iter, layers, "MS", beta, eps, OSDorder, np.int8, osd_method)
 
 
 def BP_decoder(H: np.ndarray, syndrome: np.ndarray, p: float, max_iter: int = 99,
-               layers: Optional[list] = None, OSDorder: int = -1, eps: float = 1e-9):
-    """Sum-product BP (reference decoders.py:189-290) on the GPU."""
+               layers: Optional[list] = None, OSDorder: int = -1, eps: float = 1e-9,
+               osd_method: str = "ref"):
+    """Sum-product BP (reference decoders.py:189-290) on the GPU.
+    osd_method="cs": OSD-CS with lambda = OSDorder (decode_batch)."""
     H, syndrome, bare = _shot(H, syndrome)
     if bare is not None:
         return bare
-    return _soft(H, syndrome, p, max_iter, layers, "BP", 0.75, eps, OSDorder, int)   # (L_post < 0).astype(int) (:280)
+    # dtype int: (L_post < 0).astype(int) (:280)
+    return _soft(H, syndrome, p, max_iter, layers, "BP", 0.75, eps, OSDorder, int, osd_method)
 
 
 def Relay_decoder(H: np.ndarray, syndrome: np.ndarray, p: float, leg_iters, gammas, sols: int = 1,
@@ -1006,18 +1051,24 @@ def BF_decoder(H: np.ndarray, syndrome: np.ndarray, max_iter: int = 50):
 
 
 def OSDdec(H: np.ndarray, e_hat: np.ndarray, syndrome: np.ndarray, posteriorLLRs: np.ndarray,
-           order: int = 0) -> np.ndarray:
+           order: int = 0, osd_method: str = "ref") -> np.ndarray:
     """OSD post-decoder (reference decoders.py:299-370), host C++ GF(2).
 
     Mutates and returns `e_hat`, like the reference's `e_hat[perm] = ...`.
+    osd_method="cs": OSD-CS with lambda = `order`.
     """
+    osd_method_checked(osd_method, order)
     H = np.asarray(H)
     m, n = H.shape
     perm = np.ascontiguousarray(osd_perm(posteriorLLRs), dtype=np.int32)
     syn = np.ascontiguousarray(np.asarray(syndrome) % 2, dtype=np.uint8)
     e = np.ascontiguousarray(np.asarray(e_hat) & 1, dtype=np.uint8)
     code = _lib.code_for(H)
-    _lib.check(_lib.lib.qldpc_osd_decode(code.handle, _lib.ptr(syn), _lib.ptr(perm), int(order),
-                                         _lib.ptr(e), None, None, -1))
+    if osd_method == "cs":
+        _lib.check(_lib.lib.qldpc_osd_decode_batch_cs(code.handle, 1, _lib.ptr(syn), _lib.ptr(perm), int(order),
+                                                      _lib.ptr(e), 1))
+    else:
+        _lib.check(_lib.lib.qldpc_osd_decode(code.handle, _lib.ptr(syn), _lib.ptr(perm), int(order),
+                                             _lib.ptr(e), None, None, -1))
     e_hat[...] = e.astype(e_hat.dtype)
     return e_hat

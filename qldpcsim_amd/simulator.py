@@ -497,15 +497,27 @@ class _Decode(NamedTuple):
     packed: bool                 # device path without OSD: bit-packed syndromes and estimates
     kw: dict                     # the path's keywords (_path_kw)
     masked: tuple = None         # correlated: (p, p_masked) of the second half
+    osd_method: str = "ref"      # "cs": OSD-CS with lambda = osd (decoders.decode_batch)
 
 
-def _path_kw(use_dev, osd):
+def _path_kw(use_dev, osd, osd_method="ref"):
     """decode_batch's keywords of a shot path -> (packed, keywords). Device:
     bit-packed syndromes and estimates (one bit per check / qubit in HBM)
     unless OSD needs posteriors and byte rows of the failing shots, and OSD
     is the caller's step; host: decode_batch applies OSD itself."""
     packed = use_dev and osd < 0
-    return packed, ({"want_post": osd >= 0, "ehat_bits": packed} if use_dev else {"osd_order": osd})
+    host = {"osd_order": osd, **decoders._method_kw("osd_method", osd_method)}
+    return packed, ({"want_post": osd >= 0, "ehat_bits": packed} if use_dev else host)
+
+
+def _osd_method(osd_method, OSDorder, decType):
+    """simulate_p's and simulate_phenomenological's osd_method, checked: "cs"
+    needs decType MS (the only decoder whose shots get OSD here) and an
+    OSDorder in 0..64."""
+    if osd_method != "ref" and decType != "MS":
+        decoders.osd_method_checked(osd_method, OSDorder)
+        raise ValueError(f'osd_method="{osd_method}" needs decType MS: {decType} shots get no OSD step')
+    return decoders.osd_method_checked(osd_method, OSDorder)
 
 
 def _decode_half(half, syn, dec, mask=None):
@@ -542,12 +554,13 @@ class _Plan(NamedTuple):
 
 
 def _plan(Hx, Hz, p, decType, decIterations, decSchedule, OSDorder, rngSeed, samples, sampler, logical, correlated,
-          correlated_q1, relay, channel_weights):
+          correlated_q1, relay, channel_weights, osd_method="ref"):
     """simulate_p's argument checks, in the order they have always been made
     (all before a shot is drawn or the device is touched), and what they
     establish. `relay`: the six relay_* arguments by name."""
     n = Hx.shape[1]
     hard = decType in _lib.HARD_ALGOS
+    _osd_method(osd_method, OSDorder, decType)
     probs = None
     priors = [(p / 3, {}), (p / 3, {})]           # decode_batch's p and prior= of the X and the Z half
     if channel_weights is not None:
@@ -615,7 +628,8 @@ def _plan(Hx, Hz, p, decType, decIterations, decSchedule, OSDorder, rngSeed, sam
                          "with sampler='device' (which draws its own Philox shots)")
     use_dev = sampler == "device" or (sampler is None and samples is None and _device_ok()
                                       and _channel_ok(Hx, Hz))
-    dec = _Decode(decType, 50 if hard else decIterations, osd, *_path_kw(use_dev, osd), masked)
+    dec = _Decode(decType, 50 if hard else decIterations, osd, *_path_kw(use_dev, osd, osd_method), masked,
+                  osd_method)
     return _Plan(halves, (1, 0) if correlated == "ZX" else (0, 1), dec, probs, pair_logicals, use_dev)
 
 
@@ -686,7 +700,7 @@ def _pipelined_loop(ch, count, acc, plan, p, my_shots, batch_size, osd_flags, sh
     (one sync per batch, in the OSD staging; none without OSD until the end).
     `osd_flags` collects the IndexError flags, checked once at the end."""
     Hz, Hx = plan.halves[0].H, plan.halves[1].H
-    osd = plan.dec.osd
+    osd, method = plan.dec.osd, plan.dec.osd_method
     done = 0
     pending = None
     phase = 0
@@ -698,7 +712,8 @@ def _pipelined_loop(ch, count, acc, plan, p, my_shots, batch_size, osd_flags, sh
         """Queue b's device OSD (it waits for b's decode) and hand its NumPy
         orders to the worker thread."""
         nonlocal phase
-        b.staged = decoders.osd_device_stage([(Hz, b.sy_z, b.rX), (Hx, b.sy_x, b.rZ)], slot0=2 * phase, order=osd)
+        b.staged = decoders.osd_device_stage([(Hz, b.sy_z, b.rX), (Hx, b.sy_x, b.rZ)], slot0=2 * phase, order=osd,
+                                              method=method)
         b.orders = _host_worker().submit(_host_orders_on, ch.dev, b.staged)
         phase ^= 1
 
@@ -730,7 +745,7 @@ def _pipelined_loop(ch, count, acc, plan, p, my_shots, batch_size, osd_flags, sh
             if osd >= 0:                               # (decoders.py:179-180), on the GPU
                 # the status-2 shots' NumPy orders were computed on the
                 # worker thread while the GPU decoded this batch
-                decoders.osd_device_finish(items, b.staged, osd, host=b.orders.result())
+                decoders.osd_device_finish(items, b.staged, osd, host=b.orders.result(), method=method)
                 decoders.osd_status_check(items, defer=osd_flags)
             count(b.sy_z, b.sy_x, b.errX, b.errZ, b.rX.ehat, b.rZ.ehat, b.rX.iters, b.rZ.iters, acc)
         if cur is not None and osd >= 0 and cur.staged is None:
@@ -750,7 +765,8 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
                verbose: bool = True, samples=None, sampler: Optional[str] = None,
                logical: bool = False, correlated: Optional[str] = None, correlated_q1: float = 0.49,
                relay_legs: int = 11, relay_leg_iters: int = 60, relay_sols: int = 1, relay_gamma0: float = 0.125,
-               relay_gamma_range=(-0.24, 0.66), relay_seed: int = 0, channel_weights=None) -> dict:
+               relay_gamma_range=(-0.24, 0.66), relay_seed: int = 0, channel_weights=None,
+               osd_method: str = "ref") -> dict:
     """One depolarizing probability: sample, decode both halves, count.
 
     Returns the reference's dict (simulator.py:308-315). `samples`, if given,
@@ -758,6 +774,12 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
     the parity tests). `sampler`: "device" (HIP sampler + counters on the GPU,
     the default when a device is present), or "host" (NumPy). Extra keyword
     arguments default to reference behaviour.
+
+    `osd_method` (extension; decType MS): "ref" is the reference's OSDdec of
+    order OSDorder; "cs" is OSD-CS, the combination sweep with lambda =
+    OSDorder in 0..64, on the device and on the host path.
+    "cs" with OSDorder < 0, with another decType, or an unknown method raises
+    ValueError.
 
     `logical` (extension): also test every residual against the pair's logical
     operators (count_logical_outcomes; on the device one counter kernel forms
@@ -805,7 +827,7 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
     plan = _plan(Hx, Hz, p, decType, decIterations, decSchedule, OSDorder, rngSeed, samples, sampler, logical,
                  correlated, correlated_q1,
                  dict(legs=relay_legs, leg_iters=relay_leg_iters, sols=relay_sols, gamma0=relay_gamma0,
-                      gamma_range=relay_gamma_range, seed=relay_seed), channel_weights)
+                      gamma_range=relay_gamma_range, seed=relay_seed), channel_weights, osd_method)
     osd = plan.dec.osd
     rank, my_shots, my_start, seed = _shard(shots, rngSeed)
     keys = COUNTER_KEYS + LOGICAL_KEYS if logical else COUNTER_KEYS
@@ -834,7 +856,8 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
             # bit-packed estimate tensor itself: no kernel, copy or sync between.
             def osd_now(H, syn, r):
                 items = [(H, syn, r)]
-                decoders.osd_device_finish(items, decoders.osd_device_stage(items, order=osd), osd)
+                decoders.osd_device_finish(items, decoders.osd_device_stage(items, order=osd, method=osd_method),
+                                           osd, method=osd_method)
                 decoders.osd_status_check(items, defer=osd_flags)
             _batch_loop(ch, count, acc, plan, p, my_shots, batch_size, show, osd_now if osd >= 0 else None)
         decoders.osd_status_raise(osd_flags)
@@ -1035,7 +1058,7 @@ def _decode_windows(recs, s, wins, det, dec, use_dev):
         h = recs[w[1], w[2]]
         r = _decode_half(h, syn, dec)
         if use_dev and dec.osd >= 0:
-            decoders.apply_osd_device(h.H, syn, r, dec.osd)
+            decoders.apply_osd_device(h.H, syn, r, dec.osd, method=dec.osd_method)
         last = w
     s.advance(det, ehat, iters, last, r.ehat, r.iters, None)
     return ehat, iters
@@ -1046,7 +1069,7 @@ def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float
                               OSDorder: int = -1, rngSeed: Optional[int] = None, *,
                               batch_size: Optional[int] = None, sampler: Optional[str] = None,
                               verbose: bool = True, window: Optional[int] = None, commit: Optional[int] = None,
-                              **unsupported) -> dict:
+                              osd_method: str = "ref", **unsupported) -> dict:
     """Phenomenological noise (extension; no reference counterpart): `rounds`
     = T rounds of syndrome extraction with measurement error probability `q`,
     the last round measured perfectly, decoded over each half's space-time
@@ -1066,7 +1089,10 @@ def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float
     decType "MS" or "BP"; decSchedule "F", or "L" / "S" with layers from
     schedule.layerize of the half's own space-time matrix (none of the
     reference's cross-wiring). OSDorder >= 0 (MS only, as in simulate_p) runs
-    decoders.apply_osd_device per half after its decode, unpipelined.
+    decoders.apply_osd_device per half after its decode, unpipelined;
+    `osd_method` as in simulate_p ("cs": OSD-CS with lambda = OSDorder, on every
+    window's decode too; on the device its limits are the block kernel's,
+    m <= 512 and n <= 1087 of the matrix decoded, else NotImplementedError).
     `sampler`: "device" (phenom_kernels.hip, the default with a device) or
     "host" (the NumPy twins in spacetime.py, drawn from
     np.random.default_rng([rngSeed, rank]), the X half first in every batch).
@@ -1114,6 +1140,7 @@ def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float
         raise ValueError("Unrecognized decoder type.")
     if decSchedule not in ("F", "L", "S"):
         raise ValueError("Unrecognized decoder scheduling option.")
+    _osd_method(osd_method, OSDorder, decType)
     T = int(rounds)
     if T < 1 or T != rounds:
         raise ValueError("rounds must be an integer >= 1")
@@ -1135,7 +1162,7 @@ def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float
     if batch_size is None:
         # posteriors (OSD) and byte rows cost 9 N bytes per half-shot
         batch_size = ((1 << 18) if osd < 0 else (1 << 14)) if use_dev else (1 << 14)
-    dec = _Decode(decType, decIterations, osd, *_path_kw(use_dev, osd))
+    dec = _Decode(decType, decIterations, osd, *_path_kw(use_dev, osd, osd_method), osd_method=osd_method)
     # the matrices decoded: (rounds, closed) -> a _Half per CSS half. Without
     # window= (and with T <= W) that is the closed matrix of all T rounds
     kinds = sorted({(R, closed) for _, R, closed, _ in (wins or [(0, T, True, T)])})
@@ -1182,7 +1209,7 @@ def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float
                 h = recs[kinds[0]]
                 r = _decode_half(h, det, dec)
                 if use_dev and osd >= 0:
-                    decoders.apply_osd_device(h.H, det, r, osd)
+                    decoders.apply_osd_device(h.H, det, r, osd, method=osd_method)
                 ehat, iters = r.ehat, r.iters
             cls.append(s.count_device(det, E, ehat, iters, acc, want_class=True)[1])
         both += ((cls[0] | cls[1]) == 0).sum()
@@ -1303,7 +1330,7 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
              relay_legs: int = 11, relay_leg_iters: int = 60, relay_sols: int = 1, relay_gamma0: float = 0.125,
              relay_gamma_range=(-0.24, 0.66), relay_seed: int = 0, bias: Optional[float] = None,
              channel_weights=None, rounds: Optional[int] = None, meas_error: Optional[float] = None,
-             window: Optional[int] = None, commit: Optional[int] = None):
+             window: Optional[int] = None, commit: Optional[int] = None, osd_method: str = "ref"):
     """p-sweep + results table (simulator.py:319-347). Returns None like the
     reference unless return_results=True.
 
@@ -1335,6 +1362,12 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
     W/F. window without rounds, commit without window, window < 1, commit
     outside [1, window] and non-integers raise ValueError.
 
+    osd_method (extension; decType MS): simulate_p's / simulate_phenomenological's
+    OSD method for every point, "ref" or "cs" (OSD-CS, lambda = OSDorder). A
+    method other than "ref" enters the results file's meta as "osd_method" (a
+    file without the key is a "ref" sweep), so a sweep is never resumed across
+    methods.
+
     resultsFile (extension): a JSON file the sweep writes after every
     p-point; a rerun with the same arguments skips the points already there
     (resumable long sweeps). Only rank 0 writes it.
@@ -1344,6 +1377,7 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
     Hz = load_matrix(HzFile)
     assert max(p) <= 1. and min(p) >= 0.
     _, rank, world = _dist()
+    method = {} if _osd_method(osd_method, OSDorder, decType) == "ref" else {"osd_method": osd_method}
     if rounds is None and meas_error is not None:
         raise ValueError("meas_error needs rounds (the phenomenological model)")
     if rounds is None and (window is not None or commit is not None):
@@ -1361,10 +1395,11 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
         if _window_schedule(rounds, window, commit) is not None:
             win = {"window": int(window), "commit": 1 if commit is None else int(commit)}
             meta.update(win)
+        meta.update(method)
         results = _sweep(p, meta, resultsFile, on_point, rank, lambda pT: simulate_phenomenological(
             Hx, Hz, pT, 2 * pT / 3 if meas_error is None else meas_error, rounds, shots=shots, decType=decType,
             decIterations=decIterations, decSchedule=decSchedule, OSDorder=OSDorder, rngSeed=rngSeed,
-            batch_size=batch_size, sampler=sampler, verbose=verbose, **win))
+            batch_size=batch_size, sampler=sampler, verbose=verbose, **win, **method))
         if rank == 0:
             print(format_phenomenological_results(p, results, shots))
         return results if return_results else None
@@ -1372,8 +1407,8 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
         sampler = "device" if (_device_ok() and _channel_ok(Hx, Hz)) else "host"
     meta = {"Hx": HxFile, "Hz": HzFile, "shots": shots, "decType": decType,
             "decIterations": decIterations, "decSchedule": decSchedule, "OSDorder": OSDorder,
-            "rngSeed": rngSeed, "world": world, "sampler": sampler}
-    extra = {}
+            "rngSeed": rngSeed, "world": world, "sampler": sampler, **method}
+    extra = dict(method)
     if logical:
         meta["logical"] = True
         extra["logical"] = True
@@ -1469,6 +1504,9 @@ def main(argv=None):
     parser.add_argument("--decSchedule", choices=["F", "L", "S"], default="F",
                         help="Decoder scheduling method: [F] flooding; [L] layered; [S] serial.")
     parser.add_argument("--OSDorder", type=int, default=-1, help="Ordered Statistics Decoding order.")
+    parser.add_argument("--osd-method", dest="osd_method", choices=["ref", "cs"], default="ref",
+                        help="OSD method (decType MS): ref = the reference's OSDdec of order --OSDorder; cs = OSD-CS, "
+                             "the combination sweep with lambda = --OSDorder (0..64).")
     parser.add_argument("--batch", type=int, default=None,
                         help="Shots per batch (default on the GPU: 2^20 without OSD, 2^18 with OSD; "
                              "2^16 on the host path).")
@@ -1542,6 +1580,7 @@ def main(argv=None):
                  **({"channel_weights": np.load(args.channel_weights)} if args.channel_weights else {}),
                  **({"rounds": rounds, "meas_error": meas_error} if rounds is not None else {}),
                  **({"window": window, "commit": commit} if window is not None else {}),
+                 **({"osd_method": args.osd_method} if args.osd_method != "ref" else {}),
                  **({k: getattr(args, k) for k in ("relay_legs", "relay_leg_iters", "relay_sols", "relay_gamma0",
                                                    "relay_gamma_range", "relay_seed")}
                     if args.decType == "RELAY" else {}))
