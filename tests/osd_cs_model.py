@@ -32,28 +32,21 @@ def gf2_rank(A):
         if rows.size == 0:
             continue
         A[[r, rows[0]]] = A[[rows[0], r]]
-        for i in np.flatnonzero(A[:, j]):
-            if i != r:
-                A[i] ^= A[r]
+        rows = np.flatnonzero(A[:, j])
+        A[rows[rows != r]] ^= A[r]
         r += 1
         if r == A.shape[0]:
             break
     return r
 
 
-def osd_cs_one(H, syn, perm, e_in, lam, rank=None):
-    """-> (e_hat uint8 [n], winner kind, consistent). Raises IndexError where
-    the reference's OSDdec does."""
+def reduce_shot(H, syn, perm, rank):
+    """-> (A, J): the full reduction of [Hp | s] with REF's pivot rule, stopping
+    at rank(H), and the pivot positions. It does not depend on lambda."""
     H = np.asarray(H, dtype=np.uint8) & 1
     m, n = H.shape
-    perm = np.asarray(perm)
-    rank = gf2_rank(H) if rank is None else rank
-    Hp = H[:, perm]
+    Hp = H[:, np.asarray(perm)]
     assert Hp[:, 0].any(), "the model does not cover an all-zero first column"
-    if rank <= 1:
-        raise IndexError("index %d is out of bounds for axis 1 with size %d" % (n, n))
-    ep = (np.asarray(e_in, dtype=np.uint8) & 1)[perm]
-    # full reduction of [Hp | s] with REF's pivot rule, stopping at rank(H)
     A = np.concatenate([Hp, (np.asarray(syn, dtype=np.uint8) & 1).reshape(m, 1)], axis=1)
     J, r = [], 0
     for j in range(n):
@@ -63,11 +56,26 @@ def osd_cs_one(H, syn, perm, e_in, lam, rank=None):
         if rows.size == 0:
             continue
         A[[r, rows[0]]] = A[[rows[0], r]]
-        for i in np.flatnonzero(A[:, j]):
-            if i != r:
-                A[i] ^= A[r]
+        rows = np.flatnonzero(A[:, j])
+        A[rows[rows != r]] ^= A[r]                      # (one vectorised update per pivot)
         J.append(j)
         r += 1
+    return A, J
+
+
+def osd_cs_one(H, syn, perm, e_in, lam, rank=None, reduced=None):
+    """-> (e_hat uint8 [n], winner kind, consistent). Raises IndexError where
+    the reference's OSDdec does. `reduced`: this shot's reduce_shot result,
+    where a caller runs several lambdas on the same shot."""
+    H = np.asarray(H, dtype=np.uint8) & 1
+    m, n = H.shape
+    perm = np.asarray(perm)
+    rank = gf2_rank(H) if rank is None else rank
+    assert H[:, perm[0]].any(), "the model does not cover an all-zero first column"
+    if rank <= 1:
+        raise IndexError("index %d is out of bounds for axis 1 with size %d" % (n, n))
+    ep = (np.asarray(e_in, dtype=np.uint8) & 1)[perm]
+    A, J = reduce_shot(H, syn, perm, rank) if reduced is None else reduced
     nJ = len(J)
     inJ = np.zeros(n, bool)
     inJ[J] = True
