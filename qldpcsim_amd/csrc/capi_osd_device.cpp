@@ -5,7 +5,6 @@
 
 #include "capi_internal.h"
 #include "osd_kernels.h"
-#include "tuning.h"
 
 using namespace capi;
 
@@ -42,32 +41,6 @@ static struct OsdDeviceState {
   uint32_t* tickets[64] = {};
 } g_osd;
 
-// The OsdArgs fields both launchers fill alike, buffers at the first shot
-// (rank follows code_osd_prep, after the launcher's cheap refusals)
-static qldpc::OsdArgs osd_args(const qldpc_code* code, const uint8_t* d_syn, const int32_t* d_perm,
-                               const int32_t* d_tiepos, const double* d_post, int order, uint8_t* d_ehat,
-                               int32_t* d_status, const SpillCfg& spill) {
-  qldpc::OsdArgs a{};
-  a.row_ptr = code->d_row_ptr;
-  a.col_idx = code->d_col_idx;
-  a.perm = d_perm;
-  a.syn = d_syn;
-  a.ehat = d_ehat;
-  a.status = d_status;
-  a.m = code->m;
-  a.n = code->n;
-  a.order = order;
-  a.tiepos = d_tiepos;
-  a.post = d_tiepos ? d_post : nullptr;
-  if (d_tiepos && spill.count) {
-    a.spill_post = spill.post;
-    a.spill_idx = spill.idx;
-    a.spill_count = spill.count;
-    a.spill_cap = spill.cap;
-  }
-  return a;
-}
-
 // launch(args of the chunk, its shots) for `count` shots in chunks of at most
 // `chunk` (grid.x limit, scratch size); stops at the first error
 template <typename Launch>
@@ -87,17 +60,57 @@ static hipError_t osd_chunks(const qldpc::OsdArgs& a, int64_t count, int64_t chu
   return e;
 }
 
+// Which OSD kernel runs a code: all that (m, n, zero_col, the options, cs)
+// decide, without a HIP call; the launchers and qldpc_osd_kernel_name read it
+struct OsdChoice {
+  const void *kernel = nullptr, *kblk = nullptr;   // osd_hbm_kernel or osd_kernel<nw>; the block kernel in front of it, or null
+  const char* name = "";              // of the kernel that does the work: kblk's, else kernel's
+  bool hbm = false;
+  int nw = 0, rt = 1;                 // row words of the instance (0 past 33); block kernel: rows per thread
+  int block = 0, bblk = 0, mr = 0;    // threads of kernel and of kblk; kblk's rt * bblk row slots
+};
+static int osd_threads(int rows) { return std::max(64, (rows + 63) / 64 * 64); }   // one per row, whole waves
+
+// QLDPC_EUNSUP where cs asks for OSD-CS and the code cannot have it on the device:
+// it is osd_block_kernel's epilogue (that kernel's range, and no other kernel)
+static int choose_osd_kernel(const qldpc_code* code, bool cs, OsdChoice* c) {
+  const int m = code->m, n = code->n;
+  const bool column = opt(&Options::osd_column) != 0, hbm = opt(&Options::osd_hbm) != 0;
+  const char* why = !cs                     ? nullptr
+                    : m > 512 || n > 1087   ? "m <= 512 and n <= 1087 (the block kernel's range)"
+                    : code->zero_col        ? "an H without all-zero columns"
+                    : column || hbm         ? "options osd_column and osd_hbm off"
+                                            : nullptr;
+  if (why) return fail(QLDPC_EUNSUP, "OSD-CS on the device needs %s", why);
+  *c = OsdChoice{};
+  c->nw = qldpc::osd_nw_of((n + 1 + 63) / 64);
+  // past the register / LDS kernels (m > 1024 rows, n > 2111 columns) or option osd_hbm: osd_hbm_kernel
+  c->hbm = m > 1024 || !c->nw || hbm;
+  c->block = c->hbm ? std::min(1024, osd_threads(m)) : osd_threads(m);
+  c->kernel = c->hbm ? qldpc::osd_hbm_kernel_ptr(&c->name) : qldpc::select_osd_kernel(c->nw, &c->name);
+  // The block kernel leaves two cases to REF's own row order (osd_block.h): an
+  // H with an all-zero column (the column kernel for the whole code) and a
+  // syndrome outside H's column space (those shots to the column kernel's redo
+  // pass behind it). Option osd_column: the column kernel alone (A/B, tests)
+  if (c->hbm || column || code->zero_col) return QLDPC_OK;
+  c->kblk = qldpc::select_osd_block_kernel(c->nw, m, cs, &c->rt, &c->name);
+  c->bblk = osd_threads((m + c->rt - 1) / c->rt);
+  c->mr = c->rt * c->bblk;
+  return QLDPC_OK;
+}
+
 // osd_hbm_kernel: one workgroup per shot, the shot's working matrix in a
 // per-shot slice of a stream-ordered scratch allocation (chunks of at most
 // 1 GiB of slices), LDS = one 64-bit word per row + small
-static int osd_hbm_impl(const qldpc_code* code, qldpc::OsdArgs a, int64_t count, int max_lds, hipStream_t st) {
+static int osd_hbm_impl(const qldpc_code* code, const OsdChoice& c, qldpc::OsdArgs a, int64_t count, int max_lds,
+                        hipStream_t st) {
   const int m = code->m, n = code->n;
   const int nwr = (n + 1 + 63) / 64, mp = (m + 63) / 64 * 64;
   const size_t lds = qldpc::osd_hbm_lds(m, nwr);
   if (lds > (size_t)max_lds)
     return fail(QLDPC_EUNSUP, "GPU OSD keeps one word per row in LDS: m = %d needs %zu B (at most %d)", m, lds,
                 max_lds);
-  const void* k = qldpc::osd_hbm_kernel_ptr();
+  const void* k = c.kernel;
   // the device's limit, not this code's size: concurrent calls set one value
   HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
   code_osd_prep(code);
@@ -122,10 +135,9 @@ static int osd_hbm_impl(const qldpc_code* code, qldpc::OsdArgs a, int64_t count,
   void* scr = nullptr;
   HIP_TRY(hipMallocAsync(&scr, (size_t)chunk * off, st));
   h.scratch = (unsigned char*)scr;
-  const int block = std::min(1024, std::max(64, mp));
   const hipError_t e = osd_chunks(a, count, chunk, [&](qldpc::OsdArgs& ai, unsigned g) {
     void* params[] = {(void*)&ai, (void*)&h};
-    return hipLaunchKernel(k, dim3(g), dim3(block), params, lds, st);
+    return hipLaunchKernel(k, dim3(g), dim3(c.block), params, lds, st);
   });
   const hipError_t ef = hipFreeAsync(scr, st);
   HIP_TRY(e);
@@ -133,65 +145,55 @@ static int osd_hbm_impl(const qldpc_code* code, qldpc::OsdArgs a, int64_t count,
   return QLDPC_OK;
 }
 
-// The reason OSD-CS cannot run this code on the device (it is osd_block_kernel's
-// epilogue: that kernel's range, and no other kernel), or null
-static const char* osd_cs_refusal(const qldpc_code* code) {
-  if (code->m > 512 || code->n > 1087) return "m <= 512 and n <= 1087 (the block kernel's range)";
-  if (code->zero_col) return "an H without all-zero columns";
-  if (opt(&Options::osd_column) != 0 || opt(&Options::osd_hbm) != 0) return "options osd_column and osd_hbm off";
-  return nullptr;
-}
-
-// cs_lambda < 0: the reference's OSD of `order`; else OSD-CS (order unused)
+// cs_lambda < 0: the reference's OSD of `order`; else OSD-CS (order unused;
+// the _cs entry points have checked lambda's range)
 static int osd_device_impl(const qldpc_code* code, int64_t count, const uint8_t* d_syn, const int32_t* d_perm,
                            const int32_t* d_tiepos, const double* d_post, int order, int cs_lambda,
                            uint8_t* d_ehat, int32_t* d_status, void* stream, const SpillCfg& spill = {}) {
   if (!code) return fail(QLDPC_EINVAL, "code is null");
   const bool cs = cs_lambda >= 0;
-  if (cs_lambda > QLDPC_OSD_CS_MAX_LAMBDA)
-    return fail(QLDPC_EINVAL, "OSD-CS lambda must lie in 0..%d (got %d)", QLDPC_OSD_CS_MAX_LAMBDA, cs_lambda);
-  if (cs) {
-    order = 0;                                       // the base estimate, and the redo pass's semantics
-    if (const char* why = osd_cs_refusal(code)) return fail(QLDPC_EUNSUP, "OSD-CS on the device needs %s", why);
-  }
+  OsdChoice c;
+  if (const int rc = choose_osd_kernel(code, cs, &c)) return rc;
+  if (cs) order = 0;                                // the base estimate, and the redo pass's semantics
   if (count < 0) return fail(QLDPC_EINVAL, "negative count");
   if (count == 0) return QLDPC_OK;
   if (code->device < 0) return fail(QLDPC_EHIP, "no HIP device was visible when the code was created");
   if (!d_syn || !d_perm || !d_ehat || !d_status) return fail(QLDPC_EINVAL, "null device buffer");
   const int m = code->m, n = code->n;
   hipStream_t st = (hipStream_t)stream;
-  qldpc::OsdArgs a = osd_args(code, d_syn, d_perm, d_tiepos, d_post, order, d_ehat, d_status, spill);
+  qldpc::OsdArgs a{};                                // buffers at the first shot; rank follows code_osd_prep
+  a.row_ptr = code->d_row_ptr;
+  a.col_idx = code->d_col_idx;
+  a.perm = d_perm;
+  a.syn = d_syn;
+  a.ehat = d_ehat;
+  a.status = d_status;
+  a.m = m;
+  a.n = n;
+  a.order = order;
+  a.tiepos = d_tiepos;
+  a.post = d_tiepos ? d_post : nullptr;
+  if (d_tiepos && spill.count) {
+    a.spill_post = spill.post;
+    a.spill_idx = spill.idx;
+    a.spill_count = spill.count;
+    a.spill_cap = spill.cap;
+  }
   a.cs_lambda = cs ? cs_lambda : 0;
   int dev = 0, max_lds = 0;
   HIP_TRY(hipGetDevice(&dev));
   HIP_TRY(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-  const int nw = qldpc::osd_nw_of((n + 1 + 63) / 64);
-  const void* kcol = qldpc::select_osd_kernel(nw);
-  // past the register / LDS kernels (m > 1024 rows, n > 2111 columns), or
-  // option osd_hbm: the working matrix in global memory (osd_hbm_kernel)
-  if (m > 1024 || !kcol || opt(&Options::osd_hbm) != 0) return osd_hbm_impl(code, a, count, max_lds, st);
-  // The block kernel picks pivot rows by row index instead of REF's row
-  // order: same J, same e_J (the unique solution), except when column 0 of
-  // H[:, perm] has no pivot (an all-zero column of H: column kernel for the
-  // whole code) or the syndrome lies outside H's column space (the block
-  // kernel marks those shots, a second column-kernel pass redoes them).
-  // option osd_column: the column kernel alone (A/B reference, tests).
-  const bool column = opt(&Options::osd_column) != 0 || code->zero_col;
-  int rt = 1;                                        // block kernel: rows per thread
-  const void* kblk = column ? nullptr : qldpc::select_osd_block_kernel(nw, m, &rt, cs);
-  const int block = std::max(64, (m + 63) / 64 * 64);
-  const int bblk = std::max(64, ((m + rt - 1) / rt + 63) / 64 * 64);   // block kernel threads
-  const int mr = rt * bblk;                          // its row slots
-  const int base = align16(4 * n + 4 * (m + 2) + n) + (order == 1 ? 4 * setdiff_table_ints(n) : 0);
-  const int lds_col = base + 8 * nw * (1 + 2 * 16 + 2) + 4 * 32 + 16;         // emask, candidate / xrow rows, slots, misc
-  const int lds_blk = base + 8 * nw * (1 + 64 + (QLDPC_OSD_PAIRS ? 32 : 0)) + 8 * 64 + 8 * 2 * mr + 4 * 3 * mr + 4 * 64 + 64;
-                      // emask, PW, PX, CT, Wd / Cm, pkof / pidx / crow, pk, misc
-  if (lds_col > max_lds) return fail(QLDPC_EUNSUP, "GPU OSD needs %d B LDS", lds_col);
+  if (c.hbm) return osd_hbm_impl(code, c, a, count, max_lds, st);
+  // the device's LDS limit is the one thing the choice does not know: past it
+  // the column kernel refuses and the block kernel steps aside
+  const int tab = order == 1 ? setdiff_table_ints(n) : 0;
+  const size_t lds_col = qldpc::osd_column_lds(m, n, c.nw, tab), lds_blk = qldpc::osd_block_lds(m, n, c.nw, c.mr, tab);
+  const void *kcol = c.kernel, *kblk = c.kblk;
+  if (lds_col > (size_t)max_lds) return fail(QLDPC_EUNSUP, "GPU OSD needs %zu B LDS", lds_col);
   HIP_TRY(hipFuncSetAttribute(kcol, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-  if (kblk && lds_blk > max_lds) kblk = nullptr;
+  if (kblk && lds_blk > (size_t)max_lds) kblk = nullptr;
   // OSD-CS has the block kernel alone, and works in its block-loop LDS (Wd .. CT)
-  const size_t cs_room = (size_t)(16 * mr + 8 * nw * (64 + (QLDPC_OSD_PAIRS ? 32 : 0)) + 512);
-  if (cs && (!kblk || qldpc::osd_cs_lds(nw, mr) > cs_room))
+  if (cs && (!kblk || qldpc::osd_cs_lds(c.nw, c.mr) > qldpc::osd_block_cs_room(c.nw, c.mr)))
     return fail(QLDPC_EUNSUP, "OSD-CS on the device needs the block kernel (m = %d, n = %d)", m, n);
   if (kblk) HIP_TRY(hipFuncSetAttribute(kblk, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
   // rank(H) and the column bit-vectors: built on first use, after every
@@ -216,10 +218,10 @@ static int osd_device_impl(const qldpc_code* code, int64_t count, const uint8_t*
     void* params[] = {(void*)&ai};
     hipError_t e = hipSuccess;
     if (kblk) {
-      e = hipLaunchKernel(kblk, dim3(g), dim3(bblk), params, (size_t)lds_blk, st);
+      e = hipLaunchKernel(kblk, dim3(g), dim3(c.bblk), params, lds_blk, st);
       ai.redo = 1;                                    // same stream: runs after the block pass
     }
-    if (e == hipSuccess) e = hipLaunchKernel(kcol, dim3(g), dim3(block), params, (size_t)lds_col, st);
+    if (e == hipSuccess) e = hipLaunchKernel(kcol, dim3(g), dim3(c.block), params, lds_col, st);
     return e;
   });
   HIP_TRY(launched);
@@ -286,8 +288,9 @@ static int osd_ordered_impl(const qldpc_code* code, int64_t count, const uint8_t
   if (d_spill_count && (!d_spill_post || !d_spill_idx || spill_cap < 0))
     return fail(QLDPC_EINVAL, "spill buffers incomplete");
   if (d_spill_count && count > INT32_MAX) return fail(QLDPC_EINVAL, "spill indices are int32");
-  if (cs_lambda >= 0 && code)                        // (refused before the order kernel's launch too)
-    if (const char* why = osd_cs_refusal(code)) return fail(QLDPC_EUNSUP, "OSD-CS on the device needs %s", why);
+  OsdChoice c;                                       // (OSD-CS is refused before the order kernel's launch too)
+  if (cs_lambda >= 0 && code)
+    if (const int rc = choose_osd_kernel(code, true, &c)) return rc;
   const int rc = qldpc_osd_order_device(code, count, d_post, d_perm, d_tiepos, stream);
   if (rc != QLDPC_OK) return rc;
   return osd_device_impl(code, count, d_syn, d_perm, d_tiepos, d_post, order, cs_lambda, d_ehat, d_status, stream,
@@ -320,17 +323,12 @@ extern "C" int qldpc_osd_device_ordered_ex_cs(const qldpc_code* code, int64_t co
                           d_spill_idx, d_spill_count, spill_cap, stream);
 }
 
-// The block kernel's instance as select_osd_block_kernel picks it (NW row
+// The kernel choose_osd_kernel picks: the block kernel's instance (NW row
 // words, SL engine slots, RT rows per thread), or the kernel that runs instead
 extern "C" int qldpc_osd_kernel_name(const qldpc_code* code, int cs, char* buf, int len) {
   if (!code || !buf || len <= 0) return fail(QLDPC_EINVAL, "null argument");
-  const int m = code->m, n = code->n, nw = qldpc::osd_nw_of((n + 1 + 63) / 64);
-  int rt = 1;
-  const bool hbm = m > 1024 || !nw || opt(&Options::osd_hbm) != 0;
-  const bool column = opt(&Options::osd_column) != 0 || code->zero_col;
-  if (cs && osd_cs_refusal(code)) return fail(QLDPC_EUNSUP, "OSD-CS on the device needs %s", osd_cs_refusal(code));
-  if (hbm) snprintf(buf, len, "osd_hbm_kernel");
-  else if (column || !qldpc::select_osd_block_kernel(nw, m, &rt, cs != 0)) snprintf(buf, len, "osd_kernel<%d>", nw);
-  else snprintf(buf, len, "osd_block%s_kernel<%d, %d, %d>", cs ? "_cs" : "", nw, rt == 1 ? 4 : 8, rt);
+  OsdChoice c;
+  if (const int rc = choose_osd_kernel(code, cs != 0, &c)) return rc;
+  snprintf(buf, len, "%s", c.name);
   return QLDPC_OK;
 }

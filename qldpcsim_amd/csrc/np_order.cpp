@@ -32,7 +32,7 @@
 //     compress-stores its < pivot lanes (lane order) at l_store and its
 //     >= pivot lanes (lane order) just below r_store + 8, then l_store +=
 //     #lt, r_store -= #ge; returns l_store.
-// The device kernel (osd_kernels.hip, osd_order_kernel) runs the same
+// The device kernel (osd_order.h, osd_order_kernel) runs the same
 // algorithm with a workgroup per shot.
 
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // osd_block_body.inc — the body of osd_block_kernel and osd_block_cs_kernel
-// (osd_kernels.hip; template parameters NW, SL, RT, argument `a`), included
-// once per kernel. QLDPC_OSD_BLOCK_CS = 1 ends it with the OSD-CS epilogue
+// (osd_block.h; template parameters NW, SL, RT, argument `a`; LDS bytes: osd_block_lds, osd_kernels.h),
+// included once per kernel. QLDPC_OSD_BLOCK_CS = 1 ends it with the OSD-CS epilogue
 // (osd_cs_epilogue) instead of the order-0 one; with 0 the text is the
 // order-0 kernel's alone, so that kernel's machine code does not depend on
 // the other's.

@@ -1,7 +1,10 @@
-// osd_kernels.h — batched GPU OSD (decoders.py:299-370), shared with capi_osd_device.cpp.
+// osd_kernels.h — batched GPU OSD (decoders.py:299-370): what osd_kernels.hip
+// shares with capi_osd_device.cpp — argument structs, selectors, LDS sizes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "tuning.h"
 
 namespace qldpc {
 
@@ -57,14 +60,38 @@ struct OsdHbmArgs {
   long long stride;
   int nwr, mp, off_inv, off_jl, off_inj, off_table;
 };
-const void* osd_hbm_kernel_ptr();        // __global__ osd_hbm_kernel(OsdArgs, OsdHbmArgs)
 inline size_t osd_hbm_lds(int m, int nwr) { return 8 * (size_t)((m + 63) / 64 * 64) + 24 * (size_t)nwr + 160; }
 
-const void* select_osd_kernel(int nw);  // nw = 64-bit words per row incl. the syndrome column
-const void* select_osd_block_kernel(int nw, int m, int* rows_per_thread, bool cs = false);  // block elimination (default)
-// bytes of osd_block_kernel's dead block-loop LDS (Wd | Cm | PW | PX | CT) the
-// OSD-CS epilogue needs, for nw row words and mr row slots
+// Selectors: the kernel, and through `name` (may be null) its name as
+// rocprofv3 prints it. nw = the NW instance for a row of `words` 64-bit words
+// incl. the syndrome column (osd_nw_of; 0 past 33 words).
+int osd_nw_of(int words);
+const void* osd_hbm_kernel_ptr(const char** name);   // __global__ osd_hbm_kernel(OsdArgs, OsdHbmArgs)
+const void* select_osd_kernel(int nw, const char** name);
+// block elimination (the default), or null: osd_kernel runs alone. cs: the OSD-CS instance
+const void* select_osd_block_kernel(int nw, int m, bool cs, int* rows_per_thread, const char** name);
+
+// Dynamic LDS bytes of osd_kernel<nw> and osd_block_kernel<nw, ..>: one term per array, in the order the
+// kernels carve them (osd_column.h, osd_block_body.inc). mr = the block kernel's row slots, table_ints =
+// CPython's set table (order 1, else 0). Both start with inv_perm [n] i32 | J list [m + 2] i32 | inJ [n] bytes:
+inline size_t osd_head_lds(size_t m, size_t n) { return (4 * n + 4 * (m + 2) + n + 15) & ~(size_t)15; }
+inline size_t osd_column_lds(int m, int n, size_t nw, size_t table_ints) {
+  return osd_head_lds(m, n) + 8 * nw               // emask [NW] u64
+         + 8 * 2 * 16 * nw + 8 * 2 * nw            // candidate rows [2][16][NW], xrow rows [2][NW] u64
+         + 4 * 32 + 4 * 4                          // candidate ids [2][16], misc [4] i32
+         + 4 * table_ints;                         // set table
+}
+// the block loop's arrays, which the OSD-CS epilogue reuses (osd_cs_lds bytes of them: osd_cs_epilogue's carve)
+inline size_t osd_block_cs_room(size_t nw, size_t mr) {
+  return 8 * mr + 8 * mr                           // Wd [MR], Cm [MR] u64
+         + 8 * 64 * nw + (QLDPC_OSD_PAIRS ? 8 * 32 * nw : 0) + 8 * 64;   // PW [64][NW], PX [32][NW], CT [64] u64
+}
 inline size_t osd_cs_lds(int nw, int mr) { return 8 * (size_t)mr + (size_t)mr / 8 + 264 * (size_t)nw + 272; }
-int osd_nw_of(int nw);
+inline size_t osd_block_lds(int m, int n, size_t nw, size_t mr, size_t table_ints) {
+  return osd_head_lds(m, n) + 8 * nw               // emask [NW] u64
+         + osd_block_cs_room(nw, mr)               // Wd | Cm | PW | PX | CT
+         + 4 * 3 * mr + 4 * 64 + 4 * 16            // pkof, pidx, crow [MR], pk [64], misc [16] i32
+         + 4 * table_ints;                         // set table
+}
 
 }  // namespace qldpc
