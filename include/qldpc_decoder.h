@@ -603,6 +603,21 @@ int qldpc_count_logical_ex(const qldpc_code *hx, const qldpc_code *hz, const qld
                            int64_t *d_counters, uint8_t *d_class_x, uint8_t *d_class_z, uint64_t *d_flip_x,
                            uint64_t *d_flip_z, void *stream);
 
+/* The name of the kernel instance a launch for this pair uses
+ * ("channel_sample_kernel<8>", "channel_sample_vec_kernel<0>",
+ * "count_outcomes_kernel<7, true>", "count_logical_kernel<6, true, false>"),
+ * into buf. kind: QLDPC_CHANNEL_*. est_aligned: both byte-estimate bases are
+ * 4-byte aligned (the counters; word estimates always are); tabs_lds: the
+ * residency qldpc_count_logical_ex picks (option "logical_tabs", the device's
+ * LDS). The samplers ignore both, qldpc_count_outcomes_ex ignores tabs_lds.
+ * Needs no device; n > 4096: QLDPC_EUNSUP. Measurement and tests. */
+#define QLDPC_CHANNEL_SAMPLE 0
+#define QLDPC_CHANNEL_SAMPLE_VEC 1
+#define QLDPC_CHANNEL_COUNT 2
+#define QLDPC_CHANNEL_COUNT_LOGICAL 3
+int qldpc_channel_kernel_name(const qldpc_code *hx, const qldpc_code *hz, int kind, int est_aligned, int tabs_lds,
+                              char *buf, int len);
+
 /* ---- Phenomenological noise: multi-round space-time decoding -------------
  * T = rounds rounds of syndrome extraction of one CSS half: `code` is the
  * half's H [m][n] (the X half: Hz), L [k][n] its logical table (Lz). Round t
@@ -655,6 +670,14 @@ int qldpc_phenom_count(const qldpc_code *code, const qldpc_phenom *ph, int round
                        int det_format, const uint64_t *d_E, const void *d_ehat, int ehat_format,
                        const int32_t *d_iters, int64_t *d_counters, uint8_t *d_class, uint64_t *d_flips,
                        uint64_t *d_resid, void *stream);
+
+/* The name of the sampler's or the counter's instance for this half
+ * ("phenom_sample_kernel<8>", "phenom_count_kernel<0>"), into buf. kind:
+ * QLDPC_PHENOM_*. phenom_window_kernel has one instance. Needs no device;
+ * the code's limits as above. Measurement and tests. */
+#define QLDPC_PHENOM_SAMPLE 0
+#define QLDPC_PHENOM_COUNT 1
+int qldpc_phenom_kernel_name(const qldpc_code *code, int kind, char *buf, int len);
 
 /* qldpc_phenom_window: the step between two windows of sliding-window
  * decoding, one launch of phenom_window_kernel. A window (start a, rounds R)

@@ -41,8 +41,9 @@ EXPORTS = (
     "qldpc_channel_thresholds", "qldpc_channel_sample", "qldpc_channel_sample_ex", "qldpc_count_outcomes",
     "qldpc_count_outcomes_ex",
     "qldpc_channel_table", "qldpc_channel_create", "qldpc_channel_destroy", "qldpc_channel_sample_vec",
+    "qldpc_channel_kernel_name",
     "qldpc_logicals_create", "qldpc_logicals_destroy", "qldpc_count_logical_ex",
-    "qldpc_phenom_create", "qldpc_phenom_destroy", "qldpc_phenom_sample", "qldpc_phenom_count",
+    "qldpc_phenom_kernel_name", "qldpc_phenom_create", "qldpc_phenom_destroy", "qldpc_phenom_sample", "qldpc_phenom_count",
     "qldpc_phenom_window",
     "qldpc_timing_enable", "qldpc_timing_reset", "qldpc_timing_read",
     "qldpc_set_option", "qldpc_get_option",
@@ -129,9 +130,11 @@ def _load():
         "qldpc_channel_create": ([P, P, P, P, P, PP], I),
         "qldpc_channel_destroy": ([P], I),
         "qldpc_channel_sample_vec": ([P, ctypes.c_uint64, ctypes.c_uint64, I64, P, P, P, P, I, P], I),
+        "qldpc_channel_kernel_name": ([P, P, I, I, I, ctypes.c_char_p, I], I),
         "qldpc_logicals_create": ([P, P, P, P, I, PP], I),
         "qldpc_logicals_destroy": ([P], I),
         "qldpc_count_logical_ex": ([P, P, P, I64, P, P, P, P, I, P, P, I, P, P, P, P, P, P, P, P], I),
+        "qldpc_phenom_kernel_name": ([P, I, ctypes.c_char_p, I], I),
         "qldpc_phenom_create": ([P, P, I, PP], I),
         "qldpc_phenom_destroy": ([P], I),
         "qldpc_phenom_sample": ([P, I, D, D, ctypes.c_uint64, ctypes.c_uint64, I64, P, I, P, P, P], I),
@@ -526,6 +529,31 @@ def vprior_kernel_name(H, layer_ptr, layer_rows, algo, device_index=None):
     sched = code.schedule(layer_ptr, layer_rows)
     buf = ctypes.create_string_buffer(128)
     check(lib.qldpc_decode_vprior_kernel_name(code.handle, sched.handle, ALGO[algo], buf, 128))
+    return buf.value.decode()
+
+
+CHANNEL_KERNELS = {"sample": 0, "sample_vec": 1, "count": 2, "count_logical": 3}     # QLDPC_CHANNEL_*
+PHENOM_KERNELS = {"sample": 0, "count": 1}                                            # QLDPC_PHENOM_*
+
+
+def channel_kernel_name(Hx, Hz, kind, est_aligned=True, tabs_lds=False, device_index=None):
+    """Name of the kernel instance the device sampler ("sample", with
+    per-qubit thresholds "sample_vec") or an outcome counter ("count",
+    "count_logical") launches for the pair. est_aligned: both byte-estimate
+    bases are 4-byte aligned; tabs_lds: the logical tables' residency. Needs
+    no device."""
+    cx, cz = code_for(Hx, device_index), code_for(Hz, device_index)
+    buf = ctypes.create_string_buffer(128)
+    check(lib.qldpc_channel_kernel_name(cx.handle, cz.handle, CHANNEL_KERNELS[kind], int(bool(est_aligned)),
+                                        int(bool(tabs_lds)), buf, 128))
+    return buf.value.decode()
+
+
+def phenom_kernel_name(H, kind, device_index=None):
+    """Name of the phenomenological sampler's ("sample") or counter's
+    ("count") instance for the half H. Needs no device."""
+    buf = ctypes.create_string_buffer(128)
+    check(lib.qldpc_phenom_kernel_name(code_for(H, device_index).handle, PHENOM_KERNELS[kind], buf, 128))
     return buf.value.decode()
 
 

@@ -15,26 +15,37 @@ using namespace capi;
 // 
 static constexpr long long kLogicalLdsTabBytes = 64 * 1024;
 
-static int pair_tabs(const qldpc_code* hx, const qldpc_code* hz, qldpc::PairTabs* t) {
+// The pair's shape as the kernels and channel_choice read it: every check
+// and field that needs no device
+static int pair_shape(const qldpc_code* hx, const qldpc_code* hz, qldpc::PairTabs* t) {
   if (!hx || !hz) return fail(QLDPC_EINVAL, "code is null");
   if (hx->n != hz->n)
     return fail(QLDPC_EINVAL, "Hx and Hz must have the same number of columns (physical qubits).");
-  if (hx->device < 0 || hz->device < 0)
-    return fail(QLDPC_EHIP, "no HIP device was visible when the code was created");
-  if (hx->device != hz->device) return fail(QLDPC_EINVAL, "Hx and Hz live on different devices");
-  const int W = (hx->n + 63) / 64;
-  if (W > 64) return fail(QLDPC_EUNSUP, "the channel kernels support n <= 4096 qubits (got %d)", hx->n);
-  t->rp_x = hx->d_row_ptr;
-  t->ci_x = hx->d_col_idx;
-  t->rp_z = hz->d_row_ptr;
-  t->ci_z = hz->d_col_idx;
   t->mx = hx->m;
   t->mz = hz->m;
   t->ex = hx->E;
   t->ez = hz->E;
   t->n = hx->n;
-  t->W = W;
+  t->W = (hx->n + 63) / 64;
   t->udeg = (hx->uniform_deg == hz->uniform_deg && hx->m > 0 && hz->m > 0) ? hx->uniform_deg : 0;
+  return QLDPC_OK;
+}
+
+static int pair_limit(const qldpc::PairTabs& t) {
+  if (t.W > 64) return fail(QLDPC_EUNSUP, "the channel kernels support n <= 4096 qubits (got %d)", t.n);
+  return QLDPC_OK;
+}
+
+static int pair_tabs(const qldpc_code* hx, const qldpc_code* hz, qldpc::PairTabs* t) {
+  if (int rc = pair_shape(hx, hz, t)) return rc;
+  if (hx->device < 0 || hz->device < 0)
+    return fail(QLDPC_EHIP, "no HIP device was visible when the code was created");
+  if (hx->device != hz->device) return fail(QLDPC_EINVAL, "Hx and Hz live on different devices");
+  if (int rc = pair_limit(*t)) return rc;
+  t->rp_x = hx->d_row_ptr;
+  t->ci_x = hx->d_col_idx;
+  t->rp_z = hz->d_row_ptr;
+  t->ci_z = hz->d_col_idx;
   int dev = 0, max_lds = 0;
   HIP_TRY(hipGetDevice(&dev));
   HIP_TRY(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
@@ -354,5 +365,21 @@ extern "C" int qldpc_count_logical_ex(const qldpc_code* hx, const qldpc_code* hz
   la.flip_x = d_flip_x;
   la.flip_z = d_flip_z;
   HIP_TRY(qldpc::launch_count_logical(la, channel_grid(batch), (hipStream_t)stream));
+  return QLDPC_OK;
+}
+
+static_assert(QLDPC_CHANNEL_SAMPLE == qldpc::kChannelSample && QLDPC_CHANNEL_SAMPLE_VEC == qldpc::kChannelSampleVec &&
+              QLDPC_CHANNEL_COUNT == qldpc::kChannelCount && QLDPC_CHANNEL_COUNT_LOGICAL == qldpc::kChannelCountLogical,
+              "qldpc_decoder.h names the kernels as channel_kernels.h does");
+
+// The instance channel_choice picks, as the launchers do. Needs no device.
+extern "C" int qldpc_channel_kernel_name(const qldpc_code* hx, const qldpc_code* hz, int kind, int est_aligned,
+                                         int tabs_lds, char* buf, int len) {
+  if (!buf || len <= 0) return fail(QLDPC_EINVAL, "null argument");
+  qldpc::PairTabs t{};
+  if (int rc = pair_shape(hx, hz, &t)) return rc;
+  if (int rc = pair_limit(t)) return rc;
+  if (!qldpc::channel_kernel_name(kind, qldpc::channel_choice(t, est_aligned != 0, tabs_lds != 0), buf, len))
+    return fail(QLDPC_EINVAL, "unknown channel kernel kind %d", kind);
   return QLDPC_OK;
 }

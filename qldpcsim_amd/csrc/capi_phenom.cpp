@@ -39,8 +39,7 @@ static int phenom_tabs(const qldpc_code* code, int rounds, qldpc::PhenomTabs* t)
   t->m = code->m;
   t->n = code->n;
   t->e = code->E;
-  t->udeg = (code->m > 0 && (code->uniform_deg == 6 || code->uniform_deg == 7 || code->uniform_deg == 8))
-                ? code->uniform_deg : 0;
+  t->udeg = code->m > 0 ? code->uniform_deg : 0;
   t->W = (code->n + 63) / 64;
   t->rounds = rounds;
   t->N = (int)N;
@@ -250,5 +249,18 @@ extern "C" int qldpc_phenom_window(const qldpc_code* code, int rounds, int64_t b
   a.syn_bits = syn_format == QLDPC_FMT_BITS;
   a.batch = batch;
   HIP_TRY(qldpc::launch_phenom_window(a, phenom_grid(batch), (hipStream_t)stream));
+  return QLDPC_OK;
+}
+
+static_assert(QLDPC_PHENOM_SAMPLE == qldpc::kPhenomSample && QLDPC_PHENOM_COUNT == qldpc::kPhenomCount,
+              "qldpc_decoder.h names the kernels as phenom_kernels.h does");
+
+// The instance phenom_choice picks, as the launchers do. Needs no device.
+extern "C" int qldpc_phenom_kernel_name(const qldpc_code* code, int kind, char* buf, int len) {
+  if (!buf || len <= 0) return fail(QLDPC_EINVAL, "null argument");
+  qldpc::PhenomTabs t{};
+  if (int rc = phenom_tabs(code, 1, &t)) return rc;      // (the instance does not depend on the rounds)
+  if (!qldpc::phenom_kernel_name(kind, qldpc::phenom_choice(t), buf, len))
+    return fail(QLDPC_EINVAL, "unknown phenomenological kernel kind %d", kind);
   return QLDPC_OK;
 }

@@ -68,6 +68,24 @@ struct LogicalArgs {
 constexpr int kChannelWaves = 4;  // waves per workgroup (one shot per wave at a time)
 constexpr int kLogicalCounters = 9;
 
+// Which instantiation runs a pair: all that the row degrees, n, the estimates'
+// alignment and the table residency decide, without a HIP call; the launchers
+// and qldpc_channel_kernel_name read it.
+//   deg   the row degree shared by every row of Hx and Hz if it is 6, 7 or 8
+//         (unrolled row reads), else 0 (generic CSR loop)
+//   vec   counters: byte estimates read by 32-bit loads, which need every row
+//         4-byte aligned (n % 4 == 0) and both bases 4-byte aligned
+//   tlds  count_logical_kernel: both logical tables staged into LDS
+struct ChannelChoice {
+  int deg;
+  bool vec, tlds;
+};
+ChannelChoice channel_choice(const PairTabs& t, bool est_aligned, bool tabs_lds);
+enum ChannelKernel { kChannelSample = 0, kChannelSampleVec = 1, kChannelCount = 2, kChannelCountLogical = 3 };
+// kind: a ChannelKernel (QLDPC_CHANNEL_* of qldpc_decoder.h). The name of that kernel's instance,
+// "count_logical_kernel<6, true, false>"; false for an unknown kind.
+bool channel_kernel_name(int kind, const ChannelChoice& c, char* buf, int len);
+
 // LDS bytes the two kernels need for these tables
 int channel_lds_bytes(const PairTabs& t, bool counters);
 // LDS bytes of count_logical_kernel, with both logical tables staged or not

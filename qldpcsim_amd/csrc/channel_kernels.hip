@@ -35,6 +35,8 @@
 // HBM-bound byte work, no MFMA: per shot the sampler writes 2·8·W + m_x + m_z
 // bytes, the counter reads them back with the 2n estimate bytes.
 
+#include <cstdio>
+
 #include "channel_kernels.h"
 #include "channel_common.h"
 #include "wave_common.h"
@@ -465,13 +467,31 @@ __global__ void __launch_bounds__(64 * kChannelWaves) count_logical_kernel(Logic
   }
 }
 
-// common row degree of Hx and Hz if both are uniform with a specialised
-// instantiation, else 0 (generic CSR loop)
-int uniform_degree(const PairTabs& t) {
-  return (t.udeg == 6 || t.udeg == 7 || t.udeg == 8) ? t.udeg : 0;
+}  // namespace
+
+ChannelChoice channel_choice(const PairTabs& t, bool est_aligned, bool tabs_lds) {
+  ChannelChoice c;
+  c.deg = (t.udeg == 6 || t.udeg == 7 || t.udeg == 8) ? t.udeg : 0;
+  c.vec = t.n % 4 == 0 && est_aligned;
+  c.tlds = tabs_lds;
+  return c;
 }
 
-}  // namespace
+bool channel_kernel_name(int kind, const ChannelChoice& c, char* buf, int len) {
+  const char *v = c.vec ? "true" : "false", *l = c.tlds ? "true" : "false";
+  switch (kind) {
+    case kChannelSample: snprintf(buf, len, "channel_sample_kernel<%d>", c.deg); return true;
+    case kChannelSampleVec: snprintf(buf, len, "channel_sample_vec_kernel<%d>", c.deg); return true;
+    case kChannelCount: snprintf(buf, len, "count_outcomes_kernel<%d, %s>", c.deg, v); return true;
+    case kChannelCountLogical: snprintf(buf, len, "count_logical_kernel<%d, %s, %s>", c.deg, v, l); return true;
+    default: return false;
+  }
+}
+
+// both estimate bases 4-byte aligned (ChannelChoice::vec)
+static bool estimates_aligned(const CountArgs& a) {
+  return (uintptr_t)a.ehx % 4 == 0 && (uintptr_t)a.ehz % 4 == 0;
+}
 
 int channel_lds_bytes(const PairTabs& t, bool counters) {
   int b = (4 * (t.mz + 1 + t.mx + 1) + 2 * (t.ez + t.ex) + 7) & ~7;
@@ -491,7 +511,7 @@ static hipError_t launch(K kernel, const void* args, size_t size, int grid, int 
 
 hipError_t launch_channel_sample(const SampleArgs& a, int grid, hipStream_t stream) {
   const int lds = channel_lds_bytes(a.t, false);
-  switch (uniform_degree(a.t)) {
+  switch (channel_choice(a.t, true, false).deg) {
     case 6: return launch(channel_sample_kernel<6>, &a, sizeof a, grid, lds, stream);
     case 7: return launch(channel_sample_kernel<7>, &a, sizeof a, grid, lds, stream);
     case 8: return launch(channel_sample_kernel<8>, &a, sizeof a, grid, lds, stream);
@@ -501,7 +521,7 @@ hipError_t launch_channel_sample(const SampleArgs& a, int grid, hipStream_t stre
 
 hipError_t launch_channel_sample_vec(const SampleVecArgs& a, int grid, hipStream_t stream) {
   const int lds = channel_lds_bytes(a.s.t, false);
-  switch (uniform_degree(a.s.t)) {
+  switch (channel_choice(a.s.t, true, false).deg) {
     case 6: return launch(channel_sample_vec_kernel<6>, &a, sizeof a, grid, lds, stream);
     case 7: return launch(channel_sample_vec_kernel<7>, &a, sizeof a, grid, lds, stream);
     case 8: return launch(channel_sample_vec_kernel<8>, &a, sizeof a, grid, lds, stream);
@@ -511,10 +531,8 @@ hipError_t launch_channel_sample_vec(const SampleVecArgs& a, int grid, hipStream
 
 hipError_t launch_count_outcomes(const CountArgs& a, int grid, hipStream_t stream) {
   const int lds = channel_lds_bytes(a.t, true);
-  // 32-bit estimate loads need every row 4-byte aligned (n % 4 == 0) and a
-  // 4-byte aligned base
-  const bool vec = (a.t.n % 4 == 0) && ((uintptr_t)a.ehx % 4 == 0) && ((uintptr_t)a.ehz % 4 == 0);
-  switch (uniform_degree(a.t) * 2 + (vec ? 1 : 0)) {
+  const ChannelChoice c = channel_choice(a.t, estimates_aligned(a), false);
+  switch (c.deg * 2 + (c.vec ? 1 : 0)) {
     case 13: return launch(count_outcomes_kernel<6, true>, &a, sizeof a, grid, lds, stream);
     case 12: return launch(count_outcomes_kernel<6, false>, &a, sizeof a, grid, lds, stream);
     case 15: return launch(count_outcomes_kernel<7, true>, &a, sizeof a, grid, lds, stream);
@@ -535,23 +553,23 @@ int logical_lds_bytes(const PairTabs& t, int kp, bool tabs_lds) {
 }
 
 template <int DC, bool VEC>
-static hipError_t launch_logical(const LogicalArgs& a, int grid, int lds, hipStream_t stream) {
-  return a.tabs_lds ? launch(count_logical_kernel<DC, VEC, true>, &a, sizeof a, grid, lds, stream)
+static hipError_t launch_logical(const LogicalArgs& a, bool tlds, int grid, int lds, hipStream_t stream) {
+  return tlds ? launch(count_logical_kernel<DC, VEC, true>, &a, sizeof a, grid, lds, stream)
                     : launch(count_logical_kernel<DC, VEC, false>, &a, sizeof a, grid, lds, stream);
 }
 
 hipError_t launch_count_logical(const LogicalArgs& a, int grid, hipStream_t stream) {
-  const int lds = logical_lds_bytes(a.c.t, a.kp, a.tabs_lds != 0);
-  const bool vec = (a.c.t.n % 4 == 0) && ((uintptr_t)a.c.ehx % 4 == 0) && ((uintptr_t)a.c.ehz % 4 == 0);
-  switch (uniform_degree(a.c.t) * 2 + (vec ? 1 : 0)) {
-    case 13: return launch_logical<6, true>(a, grid, lds, stream);
-    case 12: return launch_logical<6, false>(a, grid, lds, stream);
-    case 15: return launch_logical<7, true>(a, grid, lds, stream);
-    case 14: return launch_logical<7, false>(a, grid, lds, stream);
-    case 17: return launch_logical<8, true>(a, grid, lds, stream);
-    case 16: return launch_logical<8, false>(a, grid, lds, stream);
-    case 1: return launch_logical<0, true>(a, grid, lds, stream);
-    default: return launch_logical<0, false>(a, grid, lds, stream);
+  const ChannelChoice c = channel_choice(a.c.t, estimates_aligned(a.c), a.tabs_lds != 0);
+  const int lds = logical_lds_bytes(a.c.t, a.kp, c.tlds);
+  switch (c.deg * 2 + (c.vec ? 1 : 0)) {
+    case 13: return launch_logical<6, true>(a, c.tlds, grid, lds, stream);
+    case 12: return launch_logical<6, false>(a, c.tlds, grid, lds, stream);
+    case 15: return launch_logical<7, true>(a, c.tlds, grid, lds, stream);
+    case 14: return launch_logical<7, false>(a, c.tlds, grid, lds, stream);
+    case 17: return launch_logical<8, true>(a, c.tlds, grid, lds, stream);
+    case 16: return launch_logical<8, false>(a, c.tlds, grid, lds, stream);
+    case 1: return launch_logical<0, true>(a, c.tlds, grid, lds, stream);
+    default: return launch_logical<0, false>(a, c.tlds, grid, lds, stream);
   }
 }
 

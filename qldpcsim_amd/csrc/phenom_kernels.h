@@ -13,7 +13,7 @@ struct PhenomTabs {
   const int32_t* rp;
   const int32_t* ci;
   int m, n, e;   // rows, columns, edges of H
-  int udeg;      // row degree shared by every row of H (6, 7, 8), else 0
+  int udeg;      // row degree shared by every row of H, else 0
   int W;         // 64-bit words of an n-bit vector
   int rounds;    // T
   int N, M;      // T n + (T-1) m columns, T m detector rows
@@ -83,6 +83,16 @@ struct PhenomWindowArgs {
 
 constexpr int kPhenomWaves = 4;  // waves per workgroup (one shot per wave at a time)
 constexpr int kPhenomCounters = 4;
+
+// Which instantiation of the sampler and the counter runs a half: H's row
+// degree if every row has it and it is 6, 7 or 8 (unrolled row reads), else 0
+// (generic CSR loop). No HIP call; the launchers and qldpc_phenom_kernel_name
+// read it.
+int phenom_choice(const PhenomTabs& t);
+enum PhenomKernel { kPhenomSample = 0, kPhenomCount = 1 };
+// kind: a PhenomKernel (QLDPC_PHENOM_* of qldpc_decoder.h). The name of that
+// kernel's instance, "phenom_count_kernel<8>"; false for an unknown kind.
+bool phenom_kernel_name(int kind, int deg, char* buf, int len);
 
 // LDS bytes of a workgroup of each kernel
 long long phenom_sample_lds_bytes(const PhenomTabs& t);

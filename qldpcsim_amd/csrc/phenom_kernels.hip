@@ -33,13 +33,17 @@
 // iteration count, and cuts the next window's syndrome from bit offset a' m of
 // the detector row, its first m entries XORed with the committed measurement
 // estimate. Each of the four rows is bytes or words on its own; in words
-// neither offset is a multiple of 64, so reads are funnel shifts and the
-// first and last destination word of a commit are merged with the row's.
+// either offset may or may not be a multiple of 64 (it is one at every step
+// when n + m is), so reads are funnel shifts that fall back to the plain word
+// at shift 0, and the first and last destination word of a commit are merged
+// with the row's unless the commit starts or ends on a word boundary.
 //
 // Sampler and counter: one wavefront per shot (grid-stride), H's CSR staged once per
 // workgroup into LDS as 16-bit column indices (and, for the counter, L's
 // word-major table) — neither depends on T; lane l owns bit l of every 64-bit
 // word (ballots assemble the words); detectors are lane-parallel over checks.
+
+#include <cstdio>
 
 #include "phenom_kernels.h"
 #include "channel_common.h"
@@ -365,6 +369,14 @@ hipError_t launch(K kernel, const void* args, int grid, long long lds, hipStream
 
 }  // namespace
 
+int phenom_choice(const PhenomTabs& t) { return (t.udeg == 6 || t.udeg == 7 || t.udeg == 8) ? t.udeg : 0; }
+
+bool phenom_kernel_name(int kind, int deg, char* buf, int len) {
+  if (kind != kPhenomSample && kind != kPhenomCount) return false;
+  snprintf(buf, len, "%s<%d>", kind == kPhenomSample ? "phenom_sample_kernel" : "phenom_count_kernel", deg);
+  return true;
+}
+
 long long phenom_sample_lds_bytes(const PhenomTabs& t) {
   return csr_bytes(t.m, t.e) + (long long)kPhenomWaves * 8 * (t.NW + 1);
 }
@@ -377,7 +389,7 @@ long long phenom_count_lds_bytes(const PhenomTabs& t, int kp, bool tab_lds) {
 
 hipError_t launch_phenom_sample(const PhenomSampleArgs& a, int grid, hipStream_t stream) {
   const long long lds = phenom_sample_lds_bytes(a.t);
-  switch (a.t.udeg) {
+  switch (phenom_choice(a.t)) {
     case 6: return launch(phenom_sample_kernel<6>, &a, grid, lds, stream);
     case 7: return launch(phenom_sample_kernel<7>, &a, grid, lds, stream);
     case 8: return launch(phenom_sample_kernel<8>, &a, grid, lds, stream);
@@ -387,7 +399,7 @@ hipError_t launch_phenom_sample(const PhenomSampleArgs& a, int grid, hipStream_t
 
 hipError_t launch_phenom_count(const PhenomCountArgs& a, int grid, hipStream_t stream) {
   const long long lds = phenom_count_lds_bytes(a.t, a.kp, a.tab_lds != 0);
-  switch (a.t.udeg) {
+  switch (phenom_choice(a.t)) {
     case 6: return launch(phenom_count_kernel<6>, &a, grid, lds, stream);
     case 7: return launch(phenom_count_kernel<7>, &a, grid, lds, stream);
     case 8: return launch(phenom_count_kernel<8>, &a, grid, lds, stream);

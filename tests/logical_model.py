@@ -14,31 +14,36 @@ import numpy as np
 
 def nullspace(H):
     """uint8 [n - rank, n]: a basis of {v : H·v = 0 mod 2} (Gauss-Jordan on
-    dense 0/1 rows, one row XOR per pivot)."""
+    0/1 rows held as 64-bit words, one row XOR per pivot)."""
     A = (np.asarray(H) % 2).astype(np.uint8)
     m, n = A.shape
+    P = np.zeros((m, 8 * ((n + 63) // 64)), np.uint8)
+    P[:, :(n + 7) // 8] = np.packbits(A, axis=1, bitorder="little")
+    P = P.view("<u8")                       # bit j % 64 of word j / 64
     piv = []
     r = 0
     for j in range(n):
         if r == m:
             break
-        rows = np.flatnonzero(A[r:, j]) + r
+        w, sh = j >> 6, np.uint64(j & 63)
+        rows = np.flatnonzero((P[r:, w] >> sh) & np.uint64(1)) + r
         if rows.size == 0:
             continue
         if rows[0] != r:
-            A[[r, rows[0]]] = A[[rows[0], r]]
-        hit = np.flatnonzero(A[:, j])
+            P[[r, rows[0]]] = P[[rows[0], r]]
+        hit = np.flatnonzero((P[:, w] >> sh) & np.uint64(1))
         hit = hit[hit != r]
-        A[hit] ^= A[r]
+        P[hit] ^= P[r]
         piv.append(j)
         r += 1
+    A = np.unpackbits(P.view(np.uint8), axis=1, bitorder="little")[:, :n]
     pivset = set(piv)
     free = [j for j in range(n) if j not in pivset]
     N = np.zeros((len(free), n), dtype=np.uint8)
     for i, f in enumerate(free):            # v[f] = 1, v[pivot q] = A[q, f]
         N[i, f] = 1
         N[i, piv] = A[:r, f]
-    assert not ((A[:r].astype(np.int64) @ N.T.astype(np.int64)) % 2).any()
+    assert not _mod2(A[:r], N).any()        # (float32 products of 0/1 rows: exact below 2^24 columns)
     return N
 
 

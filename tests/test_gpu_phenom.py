@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import phenom_model as pm
-from test_phenom_model import SHAPES, half
+from test_phenom_model import KERNEL_DEGREE, SHAPES, half
 
 pytestmark = pytest.mark.gpu
 
@@ -51,8 +51,10 @@ def test_sampler_equals_the_model(name, T):
     2^32 - 100, bit for bit; one call equals calls of 100 + 157; p_data = 0
     gives E = 0 and q = 0 fires no measurement column."""
     import torch
+    from qldpcsim_amd import _lib
     H = half(name)[0]
     m, n = H.shape
+    assert _lib.phenom_kernel_name(H, "sample", 0) == f"phenom_sample_kernel<{KERNEL_DEGREE[name]}>"
     det, E, fired = _model(name, T)
     assert fired.any() and E.any() and (T == 1 or fired[:, ~pm.is_data(n, m, T)].any())
     for bits in (False, True):
@@ -120,7 +122,8 @@ def test_counter_equals_the_model(name, T):
     detector formats; the four counters equal the sums and accumulate over
     two calls. Every crafted case occurs with its class in the model."""
     import torch
-    from qldpcsim_amd import decoders
+    from qldpcsim_amd import _lib, decoders
+    assert _lib.phenom_kernel_name(half(name)[0], "count", 0) == f"phenom_count_kernel<{KERNEL_DEGREE[name]}>"
     det, E, ehat, rec, iters, cls, F, r = _crafted(name, T)
     for i, want in enumerate((0, 0, 0, 1, 2, 2)):
         hit = cls[rec == i]

@@ -17,9 +17,12 @@ from test_phenom_model import half
 pytestmark = pytest.mark.gpu
 
 # shape, T, (W, F): many windows inside one 64-bit word (steane, n + m = 10);
-# commits and cuts that straddle words at odd offsets (LP04_0, n + m = 259)
+# commits and cuts that straddle words at odd offsets (LP04_0, n + m = 259); every commit and cut on a word
+# boundary (q8a-Hz of tests/channel_shape_codes.py, n + m = 192: shift 0, whole first and last words); m = 63
+# beside n = 126 (q6b-Hz, n + m = 189)
 KERNEL_CASES = [("steane", 9, (3, 1)), ("steane", 9, (3, 3)), ("steane", 9, (4, 2)),
-                ("LP04_0", 6, (3, 1)), ("LP04_0", 6, (2, 2)), ("shor_x", 5, (2, 1))]
+                ("LP04_0", 6, (3, 1)), ("LP04_0", 6, (2, 2)), ("shor_x", 5, (2, 1)),
+                ("q8a_hz", 5, (3, 1)), ("q8a_hz", 5, (2, 2)), ("q6b_hz", 4, (2, 1))]
 FORMATS = list(itertools.product((False, True), repeat=3))      # (detectors, estimate, syndrome) packed?
 
 

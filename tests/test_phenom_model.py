@@ -10,7 +10,12 @@ import pytest
 
 import phenom_model as pm
 
-SHAPES = ("steane", "shor_x", "shor_z", "LP04_0")
+# the bundled halves, then four of tests/channel_shape_codes.py ("<case>_hz": Hz detects): the sampler's
+# and the counter's <8>, <6>, <8> and <0> instances; q8a: m % 64 == 0 and (n + m) % 64 == 0, no padding bits
+SHAPES = ("steane", "shor_x", "shor_z", "LP04_0", "q8a_hz", "q6v_hz", "q8b_hz", "g0v_hx")
+# the row degree phenom_sample_kernel / phenom_count_kernel are instantiated on for each (0: the generic loop)
+KERNEL_DEGREE = {"steane": 0, "shor_x": 0, "shor_z": 6, "LP04_0": 7, "q8a_hz": 8, "q6v_hz": 6, "q8b_hz": 8,
+                 "g0v_hx": 0}
 
 
 @functools.lru_cache(maxsize=None)
@@ -19,6 +24,9 @@ def half(name):
     counter tests with, Hstab / Lop the stabilisers / logical operators of the
     errors' own type."""
     from qldpcsim_amd import codes, logicals
+    import channel_shape_codes as csc
+    if name.partition("_")[0] in csc.CASES:
+        return csc.half(name)
     code, _, which = name.partition("_") if name.startswith("shor") else (name, "", "x")
     Hx, Hz = codes.load_code(code)
     Lx, Lz = logicals.css_logicals(Hx, Hz)
