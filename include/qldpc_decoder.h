@@ -87,6 +87,7 @@ typedef struct qldpc_relay qldpc_relay;       /* relay min-sum: legs and memory 
 typedef struct qldpc_prior qldpc_prior;       /* one prior probability per variable of one code */
 typedef struct qldpc_channel qldpc_channel;   /* per-qubit Pauli probabilities of a CSS pair */
 typedef struct qldpc_phenom qldpc_phenom;     /* logical table of one CSS half (phenomenological noise) */
+typedef struct qldpc_dem qldpc_dem;           /* detector error model: thresholds and [H; L] by column */
 
 const char *qldpc_last_error(void);
 const char *qldpc_version(void);
@@ -718,6 +719,73 @@ int qldpc_phenom_window(const qldpc_code *code, int rounds, int64_t batch, int d
                         const int32_t *d_witers, void *d_ehat, int ehat_format, int32_t *d_iters, int next_start,
                         int next_rounds, const void *d_det, int det_format, void *d_syn, int syn_format,
                         void *stream);
+
+/* ---- Detector error models ------------------------------------------------
+ * A detector error model is N independent error mechanisms: mechanism J
+ * fires with probability p_J and flips the detectors of column J of H [M][N]
+ * and the logical observables of column J of L [K][N]. It is what a
+ * circuit-level noise simulation yields (Stim's .dem files; the package reads
+ * them in qldpcsim_amd/dem.py), and the phenomenological model above is the
+ * special case (space-time matrix, folded logical table, prior row). The
+ * decoders take H and the priors as any other matrix (qldpc_decode_device,
+ * qldpc_decode_device_vprior); these entry points are the shot source and the
+ * outcome counter around them. No reference counterpart.
+ *
+ * qldpc_dem_create: `code` is H's handle, h_L host uint8 [k][N] (0/1; k = 0:
+ * may be NULL), h_priors host double [N], each in [0, 1). Forms the
+ * thresholds thr_J = floor(p_J 2^32) (what qldpc_channel_table(p, 0, 0)
+ * yields) and the stacked matrix [H; L] column by column, and uploads them
+ * once to the code's device. `code` must outlive the handle. Without a
+ * visible device the handle is still made. qldpc_dem_destroy: NULL is
+ * accepted.
+ *
+ * qldpc_dem_sample: shots shot0 .. shot0+batch-1 of the stream `seed`. Column
+ * J of shot s fires iff u < thr_J with qldpc_phenom_sample's draw, u =
+ * Philox4x32-10(key = seed, counter = (J % 64, (J / 64) / 4, s mod 2^32,
+ * s >> 32))[(J / 64) % 4]: on a phenomenological model bit for bit that
+ * sampler's fired row, and on any matrix qldpc_channel_sample_vec's errX with
+ * (px, py, pz) = (p, 0, 0).
+ *   d_det    uint8 [batch][M] (QLDPC_FMT_BYTES) or uint64 [batch][ceil(M/64)]
+ *   d_obs    uint64 [batch][ceil(K/64)]   L e mod 2, bit i % 64 of word i / 64,
+ *            nothing for K = 0 (may be NULL then)
+ *   d_fired  uint64 [batch][ceil(N/64)]   the fired row (NULL: not written)
+ * Per shot it writes O(M + K) bits, never the N error bits.
+ *
+ * qldpc_dem_count: a shot is class 2 (decoder failure) if H ehat != d, else
+ * class 1 (logical error) if L ehat != obs, else class 0 (success). It needs
+ * no error vector.
+ *   d_ehat      uint8 [batch][N] or uint64 [batch][ceil(N/64)] (ehat_format)
+ *   d_iters     int32 [batch]
+ *   d_counters  int64 [4], added to: failures, logical errors, successes,
+ *               sum of iterations
+ *   d_class     uint8 [batch]                                (NULL: not written)
+ *   d_flips     uint64 [batch][ceil(K/64)]  L ehat ^ obs, as computed for every
+ *               class, nothing for K = 0                     (NULL: not written)
+ *
+ * QLDPC_EINVAL, before any HIP call: a null handle or required buffer, a
+ * handle whose code changed, a prior outside [0, 1) or NaN, an unknown
+ * format, a negative batch. Limits (QLDPC_EUNSUP, before any launch):
+ * ceil(M/64) + ceil(K/64) <= 4096 words (a wave's LDS row; four waves and 128
+ * bytes of partial sums per workgroup must fit the device's LDS), N <= 2^24,
+ * fewer than 2^31 entries in [H; L]. The tables are read from global memory:
+ * no row or column degree is bounded, and the limits lie past every decode
+ * kernel's under per-variable priors (m, n, E <= 65535). batch == 0 returns
+ * QLDPC_OK. Asynchronous on `stream`: no allocation, copy or synchronisation. */
+int qldpc_dem_create(const qldpc_code *code, const uint8_t *h_L, int k, const double *h_priors, qldpc_dem **out);
+int qldpc_dem_destroy(qldpc_dem *dem);
+int qldpc_dem_sample(const qldpc_dem *dem, uint64_t seed, uint64_t shot0, int64_t batch, void *d_det, int det_format,
+                     uint64_t *d_obs, uint64_t *d_fired, void *stream);
+int qldpc_dem_count(const qldpc_dem *dem, int64_t batch, const void *d_det, int det_format, const uint64_t *d_obs,
+                    const void *d_ehat, int ehat_format, const int32_t *d_iters, int64_t *d_counters,
+                    uint8_t *d_class, uint64_t *d_flips, void *stream);
+
+/* The name of the sampler's or the counter's instance for this model
+ * ("dem_sample_kernel<16>", "dem_count_kernel<32>": the width of an entry of
+ * the column lists, 16 bits while 64 (ceil(M/64) + ceil(K/64)) <= 65536), into
+ * buf. kind: QLDPC_DEM_*. Needs no device. Measurement and tests. */
+#define QLDPC_DEM_SAMPLE 0
+#define QLDPC_DEM_COUNT 1
+int qldpc_dem_kernel_name(const qldpc_dem *dem, int kind, char *buf, int len);
 
 /* Kernel timing (HIP events around each decode kernel launch, on the launch
  * stream). Enabled by qldpc_timing_enable(1); qldpc_timing_read returns the

@@ -45,6 +45,7 @@ EXPORTS = (
     "qldpc_logicals_create", "qldpc_logicals_destroy", "qldpc_count_logical_ex",
     "qldpc_phenom_kernel_name", "qldpc_phenom_create", "qldpc_phenom_destroy", "qldpc_phenom_sample", "qldpc_phenom_count",
     "qldpc_phenom_window",
+    "qldpc_dem_create", "qldpc_dem_destroy", "qldpc_dem_sample", "qldpc_dem_count", "qldpc_dem_kernel_name",
     "qldpc_timing_enable", "qldpc_timing_reset", "qldpc_timing_read",
     "qldpc_set_option", "qldpc_get_option",
 )
@@ -140,6 +141,11 @@ def _load():
         "qldpc_phenom_sample": ([P, I, D, D, ctypes.c_uint64, ctypes.c_uint64, I64, P, I, P, P, P], I),
         "qldpc_phenom_count": ([P, P, I, I64, P, I, P, P, I, P, P, P, P, P, P], I),
         "qldpc_phenom_window": ([P, I, I64, I, I, I, I, P, I, P, P, I, P, I, I, P, I, P, I, P], I),
+        "qldpc_dem_create": ([P, P, I, P, PP], I),
+        "qldpc_dem_destroy": ([P], I),
+        "qldpc_dem_sample": ([P, ctypes.c_uint64, ctypes.c_uint64, I64, P, I, P, P, P], I),
+        "qldpc_dem_count": ([P, I64, P, I, P, P, I, P, P, P, P, P], I),
+        "qldpc_dem_kernel_name": ([P, I, ctypes.c_char_p, I], I),
         "qldpc_timing_enable": ([I], I),
         "qldpc_timing_reset": ([], I),
         "qldpc_timing_read": ([P, P], I),
@@ -471,6 +477,55 @@ def phenom_window(code, rounds, batch, done, west, w_fmt, witers, ehat, e_fmt, i
                                   stream))
 
 
+class DemTable:
+    """A detector error model on the code's device (qldpc_dem): `code` is H's
+    Code, L uint8 [K, N] the observables, priors float64 [N]. Keeps the Code
+    alive."""
+
+    def __init__(self, code, L, priors):
+        self.code = code
+        L = np.ascontiguousarray(np.asarray(L) % 2, dtype=np.uint8)
+        pr = np.ascontiguousarray(priors, dtype=np.float64)
+        if L.ndim != 2 or (L.shape[0] and L.shape[1] != code.n):
+            raise ValueError(f"the observable matrix must be a [K, {code.n}] matrix")
+        if pr.shape != (code.n,):
+            raise ValueError(f"priors must hold {code.n} probabilities (one per column)")
+        self.k = int(L.shape[0])
+        self.kw = (self.k + 63) // 64
+        h = ctypes.c_void_p()
+        check(lib.qldpc_dem_create(code.handle, ptr(L) if L.size else None, self.k, ptr(pr) if pr.size else None,
+                                   ctypes.byref(h)))
+        self.handle = h
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h and lib is not None:
+            lib.qldpc_dem_destroy(h)
+            self.handle = None
+
+
+def dem_sample(table, seed, shot0, batch, det, det_fmt, obs, fired=None, stream=None):
+    """qldpc_dem_sample on raw device addresses (ints; `fired` may be None, and
+    `obs` with no observable)."""
+    check(lib.qldpc_dem_sample(table.handle, int(seed) & ((1 << 64) - 1), int(shot0) & ((1 << 64) - 1), int(batch),
+                               det, int(det_fmt), obs, fired, stream))
+
+
+def dem_count(table, batch, det, det_fmt, obs, ehat, e_fmt, iters, acc, cls=None, flips=None, stream=None):
+    """qldpc_dem_count on raw device addresses (ints; the two per-shot outputs
+    may be None)."""
+    check(lib.qldpc_dem_count(table.handle, int(batch), det, int(det_fmt), obs, ehat, int(e_fmt), iters, acc, cls,
+                              flips, stream))
+
+
+def dem_kernel_name(table, kind):
+    """Name of the detector error model sampler's ("sample") or counter's
+    ("count") instance for a DemTable. Needs no device."""
+    buf = ctypes.create_string_buffer(128)
+    check(lib.qldpc_dem_kernel_name(table.handle, DEM_KERNELS[kind], buf, 128))
+    return buf.value.decode()
+
+
 def logicals_for(Hx, Hz, device_index=None):
     """Cached Logicals of a CSS pair on a device: the operators come from
     logicals.css_logicals, computed and uploaded once per pair."""
@@ -534,6 +589,7 @@ def vprior_kernel_name(H, layer_ptr, layer_rows, algo, device_index=None):
 
 CHANNEL_KERNELS = {"sample": 0, "sample_vec": 1, "count": 2, "count_logical": 3}     # QLDPC_CHANNEL_*
 PHENOM_KERNELS = {"sample": 0, "count": 1}                                            # QLDPC_PHENOM_*
+DEM_KERNELS = {"sample": 0, "count": 1}                                               # QLDPC_DEM_*
 
 
 def channel_kernel_name(Hx, Hz, kind, est_aligned=True, tabs_lds=False, device_index=None):

@@ -43,7 +43,8 @@ from . import _lib, decoders, spacetime
 from .schedule import layerize, select_layers, pack_layers  # noqa: F401  (re-exported)
 
 __all__ = ["load_matrix", "simulate_p", "simulate", "main", "layerize", "sample_channel",
-           "count_outcomes", "count_logical_outcomes", "wilson_interval", "simulate_phenomenological"]
+           "count_outcomes", "count_logical_outcomes", "wilson_interval", "simulate_phenomenological",
+           "simulate_dem"]
 
 COUNTER_KEYS = ("DecFailures_X", "DecFailures_Z", "decSuccessExact", "decSuccessDegen",
                 "nIterAccX", "nIterAccZ")
@@ -54,6 +55,8 @@ LOGICAL_KEYS = ("logicalErrors_X", "logicalErrors_Z", "decSuccessLogical")
 PHENOM_KEYS = ("DecFailures_X", "DecFailures_Z", "logicalErrors_X", "logicalErrors_Z", "nIterAccX", "nIterAccZ",
                "decSuccessLogical")
 PHENOM_Z_KEY = 0x9E3779B97F4A7C15          # the Z half's Philox key is the X half's ^ this
+# simulate_dem's counters (the all-reduced vector, in the device accumulator's order)
+DEM_KEYS = ("DecFailures", "logicalErrors", "decSuccess", "nIterAcc")
 
 
 def load_matrix(path: str) -> np.ndarray:
@@ -1252,6 +1255,221 @@ def format_phenomenological_results(p, results, shots):
     return "\n".join(lines)
 
 
+class DeviceDem:
+    """Device-side shot source and outcome counter of a detector error model
+    (dem_kernels.hip via qldpc_dem_sample / qldpc_dem_count): DevicePhenomHalf's
+    twin for a dem.Dem, without the sliding-window step. Shot s of key k is
+    the same whatever the batching. Packed outputs are int64 words, bit j % 64
+    of word j / 64."""
+
+    def __init__(self, dem, device, seed, shot0=0):
+        import torch
+        self.torch = torch
+        self.dev = torch.device(device)
+        self.dem = dem
+        self.M, self.K, self.N = dem.num_detectors, dem.num_observables, dem.num_errors
+        self.MW, self.KW, self.NW = (self.M + 63) // 64, (self.K + 63) // 64, (self.N + 63) // 64
+        with torch.cuda.device(self.dev):
+            self.code = _lib.code_for(dem.H, self.dev.index)
+            self.table = _lib.DemTable(self.code, dem.L, dem.priors)
+        self.seed = int(seed) & ((1 << 64) - 1)
+        self.shot = int(shot0)
+
+    def sample(self, B, bits=False, want_fired=False):
+        """(det, obs) of the next B shots: det uint8 [B, M] (bits: int64
+        [B, ceil(M/64)]), obs int64 [B, ceil(K/64)]; with want_fired also the
+        fired rows int64 [B, ceil(N/64)]."""
+        torch = self.torch
+        det = torch.empty((B, self.MW), dtype=torch.int64, device=self.dev) if bits else \
+            torch.empty((B, self.M), dtype=torch.uint8, device=self.dev)
+        obs = torch.empty((B, self.KW), dtype=torch.int64, device=self.dev)
+        fired = torch.empty((B, self.NW), dtype=torch.int64, device=self.dev) if want_fired else None
+        P = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        _lib.dem_sample(self.table, self.seed, self.shot, B, P(det), _fmt(bits), P(obs), P(fired), _stream(self.dev))
+        self.shot += int(B)
+        return (det, obs, fired) if want_fired else (det, obs)
+
+    def count_device(self, det, obs, ehat, iters, acc=None, want_shots=False, want_class=False):
+        """Adds the batch's four counters (failures, logical errors, successes,
+        iteration sum) to `acc` (int64 [4] device tensor, created if None),
+        without a host sync. det and obs as sample() wrote them; ehat uint8
+        [B, N] or int64 [B, ceil(N/64)]; iters int32 [B]. want_class: returns
+        (acc, class uint8 [B]); want_shots: (acc, class, flip words int64
+        [B, ceil(K/64)] = L ehat ^ obs)."""
+        torch = self.torch
+        if acc is None:
+            acc = torch.zeros(4, dtype=torch.int64, device=self.dev)
+        B = det.shape[0]
+        d_bits, e_bits = det.dtype == torch.int64, ehat.dtype == torch.int64
+        ts = (det, obs, ehat, iters, acc)
+        if not all(t.is_contiguous() and t.device == self.dev for t in ts) or \
+                tuple(det.shape) != ((B, self.MW) if d_bits else (B, self.M)) or \
+                tuple(ehat.shape) != ((B, self.NW) if e_bits else (B, self.N)) or \
+                det.dtype not in (torch.uint8, torch.int64) or ehat.dtype not in (torch.uint8, torch.int64) or \
+                tuple(obs.shape) != (B, self.KW) or obs.dtype != torch.int64 or tuple(iters.shape) != (B,) or \
+                iters.dtype != torch.int32 or tuple(acc.shape) != (4,) or acc.dtype != torch.int64:
+            raise ValueError("count_device: buffers do not match the batch layout")
+        cls = torch.empty(B, dtype=torch.uint8, device=self.dev) if (want_shots or want_class) else None
+        flips = torch.empty((B, self.KW), dtype=torch.int64, device=self.dev) if want_shots else None
+        P = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+        _lib.dem_count(self.table, B, P(det), _fmt(d_bits), P(obs), P(ehat), _fmt(e_bits), P(iters), acc.data_ptr(),
+                       P(cls), P(flips), _stream(self.dev))
+        if want_shots:
+            return acc, cls, flips
+        return (acc, cls) if want_class else acc
+
+
+class _HostDem:
+    """DeviceDem's two loop operations on the host (the NumPy twins in dem.py):
+    sample() draws from `rng`, count_device() adds to an int64 [4] NumPy array."""
+
+    def __init__(self, dem, rng):
+        self.dem, self.rng, self.shot = dem, rng, 0
+
+    def sample(self, B, bits=False):
+        from .dem import sample_dem
+        self.shot += int(B)
+        return sample_dem(self.dem, B, self.rng)
+
+    def count_device(self, det, obs, ehat, iters, acc):
+        from .dem import count_dem
+        c = count_dem(self.dem, det, obs, ehat, iters)
+        acc += (c["failures"], c["logical_errors"], c["successes"], c["iterations"])
+        return acc
+
+
+def simulate_dem(dem, shots: int = 1000, decType: str = "MS", decIterations: int = 99, decSchedule: str = "F",
+                 OSDorder: int = -1, rngSeed: Optional[int] = None, *, batch_size: Optional[int] = None,
+                 sampler: Optional[str] = None, verbose: bool = True, osd_method: str = "ref") -> dict:
+    """Monte-Carlo decoding of a detector error model (extension; no reference
+    counterpart): `dem` is a dem.Dem (dem.load_dem reads Stim's .dem text).
+    Each shot fires every mechanism independently with its own probability,
+    the detectors H f are decoded over H with the mechanisms' probabilities as
+    priors, and the estimate is scored against the observables L f (DESIGN.md
+    §3.16).
+
+    The decode takes the scalar entry point when every prior is equal (every
+    specialised kernel and the HBM-resident one apply, at any size), else
+    decode_batch(prior=dem.priors) with decode_vprior_kernel's limits: its
+    NotImplementedError is raised when the launch is planned, before any shot
+    is drawn. decType "MS" or "BP" (MS rows have at most 32 entries under
+    per-column priors; detector rows of circuit-level models are often
+    longer, and BP has no such limit); decSchedule "F", or "L" / "S" with
+    layers from schedule.layerize(dem.H). OSDorder >= 0 applies to MS and to
+    BP here (decoders.apply_osd_device on the device path, decoders.apply_osd
+    on the host), `osd_method` as in simulate_p. `sampler`: "device"
+    (dem_kernels.hip, the default with a device; Philox key
+    SeedSequence([rngSeed, rank]) as simulate_p) or "host" (dem.sample_dem
+    from np.random.default_rng([rngSeed, rank])). With torch.distributed
+    initialised the shots shard as in simulate_p: contiguous shares, a key per
+    rank, one all_reduce(SUM).
+
+    A shot is class 2 (decoder failure) if H ehat differs from the detectors,
+    else class 1 (logical error) if L ehat differs from the observables, else
+    class 0. Returns DecFailures, logicalErrors, decSuccess, nIterAcc,
+    logical_error_rate = 1 - decSuccess / shots, its 95 % Wilson interval
+    logical_error_rate_ci95, and detectors, errors, observables (M, N, K).
+
+    ValueError: decType RELAY / NG / BF or unknown, an unknown schedule or
+    sampler, negative shots, an osd_method that does not fit."""
+    from .dem import Dem
+    if not isinstance(dem, Dem):
+        raise ValueError("dem must be a qldpcsim_amd.dem.Dem (dem.load_dem / dem.parse_dem make one)")
+    if decType in ("RELAY",) + tuple(_lib.HARD_ALGOS):
+        raise ValueError(f"decType {decType} is not available on detector error models (MS or BP)")
+    if decType not in ("MS", "BP"):
+        raise ValueError("Unrecognized decoder type.")
+    if decSchedule not in ("F", "L", "S"):
+        raise ValueError("Unrecognized decoder scheduling option.")
+    decoders.osd_method_checked(osd_method, OSDorder, decType)
+    if sampler not in (None, "device", "host"):
+        raise ValueError("sampler must be 'device', 'host' or None")
+    if int(shots) < 0:
+        raise ValueError("shots must be >= 0")
+    osd = int(OSDorder) if OSDorder >= 0 else -1   # MS and BP alike: there is no reference behaviour to mirror
+    rank, my_shots, _, seed = _shard(shots, rngSeed)
+    use_dev = sampler == "device" or (sampler is None and _device_ok())
+    if batch_size is None:
+        batch_size = ((1 << 18) if osd < 0 else (1 << 14)) if use_dev else (1 << 14)
+    dec = _Decode(decType, decIterations, osd, *_path_kw(use_dev, osd, osd_method), osd_method=osd_method)
+    layers = None if decSchedule == "F" else layerize(dem.H, serial=decSchedule == "S")
+    half = _Half(dem.H, *pack_layers(layers, dem.num_detectors), *_half_prior(dem.priors, False))
+    show = _progress(f"(DEM {dem.num_detectors} x {dem.num_errors})", my_shots, verbose and rank == 0)
+    if use_dev:
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        src = DeviceDem(dem, dev, _device_key(seed))
+        acc = torch.zeros(4, dtype=torch.int64, device=dev)
+        zero = torch.zeros((1, dem.num_detectors), dtype=torch.uint8, device=dev)
+    else:
+        src = _HostDem(dem, np.random.default_rng(seed))
+        acc = np.zeros(4, np.int64)
+        zero = np.zeros((1, dem.num_detectors), np.uint8)
+    if half.kw:
+        # the vector-prior kernel's limits are met when its launch is planned: one
+        # all-zero detector row, so a model past them is refused
+        # (NotImplementedError) before any shot is drawn
+        _decode_half(half, zero, dec._replace(iters=1, kw={}))
+    done = 0
+    while done < my_shots:
+        B = min(batch_size, my_shots - done)
+        det, obs = src.sample(B, bits=dec.packed)
+        r = _decode_half(half, det, dec)
+        if use_dev and osd >= 0:
+            decoders.apply_osd_device(half.H, det, r, osd, method=osd_method)
+        src.count_device(det, obs, r.ehat, r.iters, acc)
+        done += B
+        show(done)
+    tot = _all_reduce(dict(zip(DEM_KEYS, acc.cpu().tolist() if use_dev else acc.tolist())), DEM_KEYS)
+    if verbose and rank == 0:
+        print()
+    res = dict(tot)
+    res["logical_error_rate"] = 1. - tot["decSuccess"] / float(shots) if shots else 0.0
+    res["logical_error_rate_ci95"] = wilson_interval(shots - tot["decSuccess"], shots)
+    res["detectors"], res["errors"], res["observables"] = dem.num_detectors, dem.num_errors, dem.num_observables
+    return res
+
+
+def format_dem_results(name, r, shots):
+    """The detector error model mode's table (one record)."""
+    lo, hi = r["logical_error_rate_ci95"]
+    return "\n".join([
+        "\n             ===          DETECTOR ERROR MODEL          ===\n",
+        "   Model (detectors x errors, observables) | Logical error rate |     95 % interval      | Failures | "
+        "Logical errors | Average iterations",
+        "-------------------------------------------+--------------------+------------------------+----------+-"
+        "---------------+--------------------",
+        f"   {name[-22:]:>22} ({r['detectors']} x {r['errors']}, {r['observables']})".ljust(43)
+        + f"|      {r['logical_error_rate']:7.2e}      |  [{lo:8.2e}, {hi:8.2e}]  | {r['DecFailures']:8} | "
+        f"{r['logicalErrors']:14} | {r['nIterAcc'] / max(shots, 1):10.3f}"])
+
+
+def _run_dem(path, shots, decType, decIterations, decSchedule, OSDorder, rngSeed, batch_size, sampler, resultsFile,
+             osd_method):
+    """The command line's --dem mode: load the model, simulate_dem, print the
+    table; rank 0 writes the record (with the run's parameters) to --results."""
+    from .dem import load_dem
+    _, rank, world = _dist()
+    dem = load_dem(path)
+    if sampler is None:
+        sampler = "device" if _device_ok() else "host"
+    res = simulate_dem(dem, shots=shots, decType=decType, decIterations=decIterations, decSchedule=decSchedule,
+                       OSDorder=OSDorder, rngSeed=rngSeed, batch_size=batch_size, sampler=sampler, verbose=True,
+                       osd_method=osd_method)
+    if rank == 0:
+        print(format_dem_results(path, res, shots))
+        if resultsFile:
+            meta = {"dem": path, "shots": shots, "decType": decType, "decIterations": decIterations,
+                    "decSchedule": decSchedule, "OSDorder": OSDorder, "rngSeed": rngSeed, "world": world,
+                    "sampler": sampler, **decoders._method_kw("osd_method", osd_method)}
+            import json
+            import os
+            with open(resultsFile + ".tmp", "w") as f:
+                json.dump({"meta": meta, "result": res}, f, indent=1)
+            os.replace(resultsFile + ".tmp", resultsFile)
+    return res
+
+
 def format_results(p, results, shots):
     """The reference's results table (simulator.py:342-347)."""
     lines = ["\n                             ===          SIMULATION RESULTS          ===\n",
@@ -1479,9 +1697,11 @@ def _init_dist_from_env():
 
 def main(argv=None):
     parser = argparse.ArgumentParser(description="Stim-based QC-LDPC depolarizing-channel simulator.")
-    parser.add_argument("--Hx", required=True, help="Path to Hx parity-check matrix (.npy).")
-    parser.add_argument("--Hz", required=True, help="Path to Hz parity-check matrix (.npy).")
-    parser.add_argument("--p", type=float, nargs="+", required=True, help="Depolarizing probability.")
+    # --dem replaces the code and the channel: only then are --Hx, --Hz and --p not required
+    pair = not any(a == "--dem" or a.startswith("--dem=") for a in (sys.argv[1:] if argv is None else argv))
+    parser.add_argument("--Hx", required=pair, help="Path to Hx parity-check matrix (.npy).")
+    parser.add_argument("--Hz", required=pair, help="Path to Hz parity-check matrix (.npy).")
+    parser.add_argument("--p", type=float, nargs="+", required=pair, help="Depolarizing probability.")
     parser.add_argument("--shots", type=int, default=1000, help="Number of Monte Carlo shots.")
     parser.add_argument("--rngSeed", type=int, default=None, help="RNG seed.")
     parser.add_argument("--decType", choices=["NG", "BF", "MS", "BP", "RELAY"], default="MS",
@@ -1542,7 +1762,38 @@ def main(argv=None):
                              "bounded by W whatever T is); T <= W is the whole-matrix decode.")
     parser.add_argument("--commit", type=int, default=argparse.SUPPRESS, metavar="F",
                         help="With --window: rounds committed per window, 1 <= F <= W (default 1).")
+    parser.add_argument("--dem", default=argparse.SUPPRESS, metavar="FILE",
+                        help="Decode a detector error model instead of a CSS pair: Stim's .dem text, or .npz with "
+                             "H, L and priors (MS, BP; --OSDorder applies to both). Takes the place of --Hx, --Hz "
+                             "and --p.")
     args = parser.parse_args(argv)
+    dem_file = getattr(args, "dem", None)
+    if dem_file is not None:
+        given = [f for f, v in (("--Hx", args.Hx), ("--Hz", args.Hz), ("--p", args.p),
+                                ("--rounds", getattr(args, "rounds", None)),
+                                ("--window", getattr(args, "window", None)), ("--logical", args.logical or None),
+                                ("--correlated", args.correlated), ("--bias", args.bias),
+                                ("--channel-weights", args.channel_weights)) if v is not None]
+        if given:
+            parser.error(f"--dem cannot be combined with {', '.join(given)}")
+        if args.decType not in ("MS", "BP"):
+            parser.error("--dem decodes with MS or BP")
+        if args.osd_method == "cs" and not 0 <= args.OSDorder <= decoders.OSD_CS_MAX_LAMBDA:
+            parser.error(f"--osd-method cs takes its lambda from --OSDorder: 0..{decoders.OSD_CS_MAX_LAMBDA}")
+        own_group = _init_dist_from_env()
+        _, rank, _ = _dist()
+        if rank == 0:
+            print("\n   Command line arguments:")
+            print(args)
+            print("")
+        try:
+            _run_dem(dem_file, args.shots, args.decType, args.decIterations, args.decSchedule, args.OSDorder,
+                     args.rngSeed, args.batch, args.sampler, args.results, args.osd_method)
+        finally:
+            if own_group:
+                import torch.distributed as dist
+                dist.destroy_process_group()
+        return
     if args.bias is not None and args.channel_weights is not None:
         parser.error("--bias and --channel-weights exclude each other")
     rounds, meas_error = getattr(args, "rounds", None), getattr(args, "meas_error", None)
