@@ -233,7 +233,11 @@ int qldpc_prior_destroy(qldpc_prior *prior);
  * generic LDS kernel's second twin, which keeps the row in LDS (8 n bytes per
  * workgroup): QLDPC_EUNSUP, before any launch, under the conditions of
  * qldpc_decode_device_prior (m, n or edges > 65535, MS row degree > 32, BP
- * column degree > 128, state past the LDS, option "force_hbm"). A handle made
+ * column degree > 128, state past the LDS, option "force_hbm"). With option
+ * "vprior_hbm" set those cases decode instead, with hbm_tile_vprior_kernel:
+ * the HBM-resident kernel reading L_j from the handle's row, at any size and
+ * degree, bit for bit with decode_vprior_kernel where both run ("force_hbm"
+ * as well: every call takes it). A handle made
  * for another code: QLDPC_EINVAL. Arguments are checked before any HIP call;
  * asynchronous on `stream`, a launch plan of its own per (schedule, algo). */
 int qldpc_decode_device_vprior(const qldpc_code *code, const qldpc_schedule *sched, int algo, const void *d_syn,
@@ -247,7 +251,11 @@ int qldpc_decode_host_vprior(const qldpc_code *code, const qldpc_schedule *sched
                              int32_t *h_iters, double *h_post, int32_t *h_flags);
 
 /* Name of the kernel qldpc_decode_device_vprior launches, as rocprofv3 reports
- * it (e.g. "decode_vprior_kernel<0, false, 8>"); needs no device. */
+ * it (e.g. "decode_vprior_kernel<0, false, 8>"); needs no device. With option
+ * "vprior_hbm": "hbm_tile_vprior_kernel<0, 8, 4>" (algo, row-degree bound 8 /
+ * 16 / 32 / 64, waves) where the LDS kernel cannot run; that needs no device
+ * either unless the LDS size decides (state past the LDS: asked of the launch
+ * plan when the code has a device, else the LDS kernel's name). */
 int qldpc_decode_vprior_kernel_name(const qldpc_code *code, const qldpc_schedule *sched, int algo, char *buf,
                                     int len);
 
@@ -816,6 +824,8 @@ int qldpc_timing_read(double *total_ms, int64_t *launches);
  *   "osd_hbm" (0)             GPU OSD through the device-memory kernel at any size (tests)
  *   "logical_tabs" (0)        qldpc_count_logical_ex: logical tables staged in LDS (1), read from
  *                             global memory (2), or chosen by size (0)
+ *   "vprior_hbm" (0)          qldpc_decode_*_vprior: what decode_vprior_kernel refuses decodes with the
+ *                             HBM-resident hbm_tile_vprior_kernel (with "force_hbm": every call); 0: refused
  * Unknown name: QLDPC_EINVAL. */
 int qldpc_set_option(const char *name, int64_t value);
 int qldpc_get_option(const char *name, int64_t *value);

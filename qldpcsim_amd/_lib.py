@@ -579,7 +579,8 @@ def prior_kernel_name(H, layer_ptr, layer_rows, algo, device_index=None):
 
 def vprior_kernel_name(H, layer_ptr, layer_rows, algo, device_index=None):
     """Name of the kernel a decode with prior= launches for (H, schedule,
-    algo): decode_vprior_kernel<...> (NotImplementedError where it cannot run)."""
+    algo): decode_vprior_kernel<...> (NotImplementedError where it cannot run);
+    with option vprior_hbm, hbm_tile_vprior_kernel<...> where that one cannot."""
     code = code_for(H, device_index)
     sched = code.schedule(layer_ptr, layer_rows)
     buf = ctypes.create_string_buffer(128)

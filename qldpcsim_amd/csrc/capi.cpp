@@ -51,7 +51,8 @@ static std::atomic<int64_t>* option_slot(const char* name) {
                {"waves_per_wg", &Options::waves_per_wg}, {"wg_per_cu", &Options::wg_per_cu},
                {"osd_column", &Options::osd_column},   {"osd_tickets", &Options::osd_tickets},
                {"osd_prof", &Options::osd_prof},       {"osd_hbm", &Options::osd_hbm},
-               {"logical_tabs", &Options::logical_tabs}, {"flood_qc", &Options::flood_qc}};
+               {"logical_tabs", &Options::logical_tabs}, {"flood_qc", &Options::flood_qc},
+               {"vprior_hbm", &Options::vprior_hbm}};
   for (const auto& e : table)
     if (strcmp(e.name, name) == 0) return &(g_opt.*(e.slot));
   return nullptr;

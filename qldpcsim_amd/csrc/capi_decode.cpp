@@ -165,12 +165,36 @@ static int twin_limits(const qldpc_schedule* s, int algo, const char* what) {
 // the feature's name in messages (kind: PLAN_PRIOR or PLAN_VPRIOR)
 static const char* twin_name(PlanKind kind) { return kind == PLAN_PRIOR ? "two-level priors" : "per-variable priors"; }
 
+// PLAN_VPRIOR under option vprior_hbm: what the LDS twin refuses decodes with
+// hbm_tile_vprior_kernel (the two-level twin has no HBM-resident variant)
+static bool vprior_hbm_on(PlanKind kind) { return kind == PLAN_VPRIOR && opt(&Options::vprior_hbm) != 0; }
+
+// twin_limits without the message: no LDS twin runs this (schedule, algo)
+static bool past_twin_limits(const qldpc_schedule* s, int algo) {
+  const qldpc_code* c = s->code;
+  return !s->lds_ok || (algo == QLDPC_ALGO_MS && c->max_row_deg > 32) ||
+         (algo == QLDPC_ALGO_BP && c->max_col_deg > 128) || opt(&Options::force_hbm) != 0;
+}
+
+uint32_t capi::prior_filter_word(const qldpc_code* c, const std::vector<double>& L) {
+  uint32_t f = 0;
+  const size_t n = std::min(L.size(), c->avar.size());
+  for (size_t v = 0; v < n; ++v)
+    if (L[v] < 0.0) f ^= c->avar[v];
+  return f;
+}
+
 int capi::choose_twin_kernel(const qldpc_schedule* s, int algo, PlanKind kind, KernelChoice* k) {
   const qldpc_code* c = s->code;
-  if (int rc = twin_limits(s, algo, twin_name(kind))) return rc;
   *k = KernelChoice{};
   k->max_waves = QLDPC_MAX_THREADS / 64;
   k->kind = kind;
+  if (vprior_hbm_on(kind) && past_twin_limits(s, algo)) {
+    k->hbm = true;
+    k->kernel = qldpc::select_hbm_vprior_kernel(algo, c->max_row_deg, &k->name);
+    return QLDPC_OK;
+  }
+  if (int rc = twin_limits(s, algo, twin_name(kind))) return rc;
   const auto select = kind == PLAN_PRIOR ? qldpc::select_prior_kernel : qldpc::select_vprior_kernel;
   k->kernel = select(algo, s->layered, fast_table_ok(c) ? c->uniform_deg : 0, &k->name);
   return QLDPC_OK;
@@ -257,7 +281,7 @@ static int build_plan(qldpc_schedule* s, int algo, PlanKind kind, LaunchPlan* p)
   KernelChoice pk;
   if (prior) {
     if (int rc = choose_twin_kernel(s, algo, kind, &pk)) return rc;
-    p->hbm = false;
+    p->hbm = pk.hbm;
   }
   if (!p->hbm) {
     const KernelChoice k = prior ? pk : choose_kernel(s, algo);
@@ -300,16 +324,28 @@ static int build_plan(qldpc_schedule* s, int algo, PlanKind kind, LaunchPlan* p)
     // no LDS kernel holds the graph's per-half-shot state and tables: the
     // HBM-resident kernel decodes it; decided once per plan, not per launch
     p->hbm = best_waves == 0;
-    if (prior && p->hbm)
+    if (prior && p->hbm && !vprior_hbm_on(kind))
       return fail(QLDPC_EUNSUP, "%s: the tables and one wave's state (%d + %d B) do not fit the %d B "
                   "of LDS; there is no HBM-resident variant", twin_name(kind), image_lds, p->args.wave_bytes, max_lds);
   }
   if (p->hbm) {
-    p->kernel = qldpc::select_hbm_kernel(algo, c->max_row_deg, &p->name);
+    p->kernel = (kind == PLAN_VPRIOR ? qldpc::select_hbm_vprior_kernel : qldpc::select_hbm_kernel)(
+        algo, c->max_row_deg, &p->name);
     p->waves = p->blocks_per_cu = p->lds = p->team = 0;
     plan_static_hbm(s, &p->hargs);
-    int per_cu = 0;                                   // resident tiles at the kernel's register use
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, p->kernel, 64 * qldpc::kHbmWaves, 0));
+    if (kind == PLAN_VPRIOR && algo == QLDPC_ALGO_BP && c->max_col_deg > 128) {
+      // np.sum splits a column of more than 128 entries: one pending sum per
+      // level and lane, for the deepest column the code has
+      int depth = 0;
+      for (int v = 0; v < c->n; ++v) depth = std::max(depth, qldpc::hbm_column_depth(c->csc_ptr[v + 1] - c->csc_ptr[v]));
+      p->hbm_lds = qldpc::hbm_vprior_lds(depth);
+      if (p->hbm_lds > (size_t)max_lds / 2)
+        return fail(QLDPC_EUNSUP, "%s: BP column degree %d needs %zu B of LDS for its column sums", twin_name(kind),
+                    c->max_col_deg, p->hbm_lds);
+      HIP_TRY(qldpc::configure_kernel(p->kernel, max_lds / 2));   // (beside 6.4 KB of static LDS)
+    }
+    int per_cu = 0;                                  // resident tiles at the kernel's register use
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, p->kernel, 64 * qldpc::kHbmWaves, p->hbm_lds));
     p->hbm_tiles_cap = p->cus * std::max(per_cu, 1);
   }
   return QLDPC_OK;
@@ -432,8 +468,11 @@ static HbmLayout hbm_layout(const qldpc_code* c, size_t w, int64_t t) {
 // tiles = min(what the batch fills, the workgroups a CU holds at the kernel's
 // register use, what a 64 GiB (or half the free memory) workspace holds); the
 // workspace belongs to the schedule and an event orders launches that share it.
+// With `vp` (hbm_tile_vprior_kernel) the priors come from the handle's row and
+// its filter word; q.p is unread.
 static int decode_hbm(const qldpc_code* code, qldpc_schedule* s, int algo, const LaunchPlan& plan,
-                      const DecodeCall& q) {
+                      const DecodeCall& q, const qldpc_prior* vp) {
+  if (vp && !vp->d_L.p) return fail(QLDPC_EHIP, "no HIP device was visible when the prior handle was created");
   const size_t w = algo == QLDPC_ALGO_MS ? 4 : 8;   // message / posterior row element (MS: f32 S)
   const size_t per_tile = ((size_t)code->E * w + (size_t)code->n * w + (size_t)code->m) * 64;
   std::lock_guard<std::mutex> lk(s->mu);
@@ -469,13 +508,21 @@ static int decode_hbm(const qldpc_code* code, qldpc_schedule* s, int algo, const
   a.syn_bits = q.syn_format == QLDPC_FMT_BITS, a.eh_bits = q.ehat_format == QLDPC_FMT_BITS;
   a.batch = q.batch;
   a.queue = s->d_queue + (s->qnext.fetch_add(1) % qldpc_schedule::kQueueSlots);
-  a.L = qldpc_prior_llr(q.p, q.eps);                // np.log prior (decoders.py:147, :232)
-  a.L32 = (float)a.L;
+  if (vp) {
+    a.L = 0.0, a.L32 = 0.0f;                        // (unread: every prior comes from the handle's row)
+  } else {
+    a.L = qldpc_prior_llr(q.p, q.eps);              // np.log prior (decoders.py:147, :232)
+    a.L32 = (float)a.L;
+  }
   a.beta = q.beta, a.eps = q.eps, a.max_iter = q.max_iter;
   HIP_TRY(hipMemsetAsync(a.queue, 0, sizeof(uint32_t), q.st));
   TimedLaunch t;
   if (int rc = timing_begin(&t, q.st)) return rc;
-  HIP_TRY(qldpc::launch_hbm(plan.kernel, a, (int)tiles, s->d_h_fl_var, s->d_h_fl_pos, s->hbm_lazy ? 1 : 0, q.st));
+  if (vp)
+    HIP_TRY(qldpc::launch_hbm_vprior(plan.kernel, a, qldpc::HbmPrior{vp->d_L, vp->filt0}, (int)tiles, s->d_h_fl_var,
+                                     s->d_h_fl_pos, s->hbm_lazy ? 1 : 0, plan.hbm_lds, q.st));
+  else
+    HIP_TRY(qldpc::launch_hbm(plan.kernel, a, (int)tiles, s->d_h_fl_var, s->d_h_fl_pos, s->hbm_lazy ? 1 : 0, q.st));
   if (int rc = timing_end(&t, q.st)) return rc;
   HIP_TRY(hipEventRecord(s->hbm_ev, q.st));
   return QLDPC_OK;
@@ -574,7 +621,8 @@ static int decode_device(const qldpc_code* code, const qldpc_schedule* sched_c, 
   if (plan.hbm)
     return decode_hbm(code, sched, algo, plan,
                       DecodeCall{d_syn, d_ehat, syn_format, ehat_format, max_iter, batch, p, beta, eps, d_iters,
-                                 d_flags, d_post, st});
+                                 d_flags, d_post, st},
+                      vp);
 
   DecodeArgs a = plan.args;
   a.syn = (const uint8_t*)d_syn, a.ehat = (uint8_t*)d_ehat;
@@ -647,6 +695,13 @@ static int twin_kernel_name(const qldpc_code* code, const qldpc_schedule* sched,
   if (algo != QLDPC_ALGO_MS && algo != QLDPC_ALGO_BP) return fail(QLDPC_EINVAL, "Unrecognized decoder type.");
   KernelChoice k;                                     // (no device needed: the name depends on the code alone)
   if (int rc = choose_twin_kernel(sched, algo, kind, &k)) return rc;
+  if (vprior_hbm_on(kind) && !k.hbm && code->device >= 0 && sched->generic.dev) {
+    // option vprior_hbm: whether the LDS twin or hbm_tile_vprior_kernel runs is
+    // then a question of the device's LDS size, answered by the launch plan
+    LaunchPlan plan;
+    if (int rc = resolve_plan(code, const_cast<qldpc_schedule*>(sched), algo, &plan, kind)) return rc;
+    k.name = plan.name;
+  }
   snprintf(buf, (size_t)len, "%s", k.name);
   return QLDPC_OK;
 }
@@ -817,6 +872,7 @@ extern "C" int qldpc_prior_create(const qldpc_code* code, const double* h_p, dou
       return fail(QLDPC_EINVAL, "code lives on device %d, current device is %d", code->device, dev);
     HIP_TRY(pr->d_L.upload(pr->L));
   }
+  pr->filt0 = prior_filter_word(code, pr->L);
   *out = pr.release();
   return QLDPC_OK;
 }

@@ -41,7 +41,7 @@ int fail(int code, const char* fmt, ...);
 struct Options {
   std::atomic<int64_t> force_hbm{0}, flood_generic{0}, layered_generic{0}, ms_lanes_per_check{0}, bp_wave{0},
       bp_lg{1}, bp_team_w{0}, static_sched{0}, waves_per_wg{0}, wg_per_cu{0}, osd_column{0}, osd_tickets{1},
-      osd_prof{0}, osd_hbm{0}, logical_tabs{0}, flood_qc{1};
+      osd_prof{0}, osd_hbm{0}, logical_tabs{0}, flood_qc{1}, vprior_hbm{0};
   std::atomic<uint32_t> gen{1};
 };
 extern Options g_opt;
@@ -136,10 +136,15 @@ struct KernelChoice {
   // PLAN_PRIOR (decode_prior_kernel): the wave slice also holds the selector
   // bits; PLAN_VPRIOR (decode_vprior_kernel): the prior row lies behind the graph image
   PlanKind kind = PLAN_SCALAR;
+  // PLAN_VPRIOR under option vprior_hbm, past the LDS twin's limits (or with
+  // force_hbm): hbm_tile_vprior_kernel; `kernel` and `name` are that instance's
+  bool hbm = false;
 };
 
 struct LaunchPlan {
-  bool hbm = false;         // hbm_tile_kernel decodes: the LDS kernels cannot hold this schedule, or force_hbm
+  // hbm_tile_kernel (PLAN_VPRIOR: hbm_tile_vprior_kernel) decodes: the LDS
+  // kernels cannot hold this schedule, or force_hbm
+  bool hbm = false;
   const void* kernel = nullptr;
   const char* name = "";
   int waves = 0, blocks_per_cu = 0, lds = 0;   // LDS kernels: waves per workgroup, workgroups per CU, LDS bytes
@@ -148,6 +153,7 @@ struct LaunchPlan {
   qldpc::DecodeArgs args{};  // every static field filled (LDS kernels)
   qldpc::HbmArgs hargs{};    // the same for hbm_tile_kernel
   int hbm_tiles_cap = 0;    // CUs x resident 64-slot tiles per CU
+  size_t hbm_lds = 0;       // hbm_tile_vprior_kernel, BP: dynamic LDS bytes (qldpc::hbm_vprior_lds; 0 up to 128 entries per column)
   uint32_t gen = 0;         // g_opt.gen the plan was built under
   bool ok = false;
 };
@@ -235,6 +241,7 @@ struct qldpc_prior {
   double eps = 0.0;
   std::vector<double> L;         // [n] L_j = log((1 - p_j) / max(p_j, eps)), relabeled variable order
   capi::DevBuf<double> d_L;
+  uint32_t filt0 = 0;            // prior_filter_word(code, L): hbm_tile_vprior_kernel's filter word at start
 };
 
 // ---------------------------------------------------------------------------
@@ -294,7 +301,8 @@ KernelChoice choose_kernel(const qldpc_schedule* s, int algo);
 // decode_prior_kernel (PLAN_PRIOR) or decode_vprior_kernel (PLAN_VPRIOR) for
 // (schedule, algo): QLDPC_EUNSUP where the generic LDS kernel cannot run the
 // code (16-bit tables, MS row degree > 32, BP column degree > 128) or option
-// force_hbm is set; calls no HIP function
+// force_hbm is set; calls no HIP function. PLAN_VPRIOR with option vprior_hbm
+// set: those cases take hbm_tile_vprior_kernel instead (k->hbm)
 int choose_twin_kernel(const qldpc_schedule* s, int algo, PlanKind kind, KernelChoice* k);
 // The generated protograph table (qc_tables.h) whose expansion is exactly the
 // code's H, or -1: compared entry by entry, not by shape or hash
@@ -305,6 +313,10 @@ int plan_static(const qldpc_schedule* s, int algo, const KernelChoice& k, qldpc:
 // LDS bytes of a workgroup of `waves` waves; sets a->off_libm
 int plan_lds(int algo, int image_lds, int team, int waves, qldpc::DecodeArgs* a);
 void plan_static_hbm(const qldpc_schedule* s, qldpc::HbmArgs* a);
+// XOR of the stop-test filter words avar[v] over the relabeled variables whose
+// prior L[v] is negative: the filters of a decode whose posteriors all stand at
+// their priors (hbm_tile_vprior_kernel's HbmArgs::filt0); calls no HIP function
+uint32_t prior_filter_word(const qldpc_code* c, const std::vector<double>& L);
 // The code's host staging workspace (caller holds ws_mu), grown to `batch`
 // half-shots; posterior buffers only when wanted
 int ws_reserve(qldpc_code* code, int64_t batch, bool want_post);

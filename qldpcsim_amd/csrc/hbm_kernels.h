@@ -47,12 +47,37 @@ struct HbmArgs {
   float L32;
   int max_iter;
 };
+// What hbm_tile_vprior_kernel takes on top (HbmArgs::L and L32 are then
+// unread): one prior per variable. Kernel parameters of their own, not HbmArgs
+// fields: with the struct two fields longer the scalar min-sum instances
+// compiled to other register allocations.
+struct HbmPrior {
+  const double* Lv;         // [n]   L_v of relabeled variable v (qldpc_prior::d_L)
+  uint32_t filt0;           // XOR of avar[v] over the variables with Lv[v] < 0: a slot's filter word at start
+};
 
 // dcmax: row degree bound of the instantiation (8, 16, 32 or 64)
 const void* select_hbm_kernel(int algo, int dcmax, const char** name);
+// hbm_tile_vprior_kernel<algo, D, 4>, chosen by the row degree in the same way
+const void* select_hbm_vprior_kernel(int algo, int dcmax, const char** name);
 // fl_var / fl_pos: first layer reaching each variable / CSC position; lazy =
 // the layers partition the rows (no state initialisation pass)
 hipError_t launch_hbm(const void* kernel, const HbmArgs& a, int tiles, const int32_t* fl_var, const int32_t* fl_pos,
                       int lazy, hipStream_t stream);
+// NumPy's pairwise summation splits a column of more than 128 entries in two,
+// again and again: the levels below the root for d entries (0 up to 128). BP's
+// hbm_tile_vprior_kernel keeps one pending sum per level and lane in dynamic
+// LDS, hbm_vprior_lds(deepest column of the code) bytes (0 for most codes).
+inline int hbm_column_depth(int d) {
+  if (d <= 128) return 0;
+  int n2 = d / 2;
+  n2 -= n2 % 8;
+  const int left = hbm_column_depth(n2), right = hbm_column_depth(d - n2);
+  return 1 + (left > right ? left : right);
+}
+inline size_t hbm_vprior_lds(int depth) { return (size_t)depth * 64 * kHbmWaves * sizeof(double); }
+// lds: hbm_vprior_lds of the plan (BP; min-sum sums its columns in sequence: 0)
+hipError_t launch_hbm_vprior(const void* kernel, const HbmArgs& a, const HbmPrior& pr, int tiles, const int32_t* fl_var,
+                             const int32_t* fl_pos, int lazy, size_t lds, hipStream_t stream);
 
 }  // namespace qldpc

@@ -154,7 +154,13 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
     packages), shared by every shot of the batch; `p` must then be None. Runs
     decode_vprior_kernel on both paths, with the limits of
     the prior_mask kernel; not combinable with prior_mask, relay= or NG / BF.
-    A uniform vector gives the scalar decode's result bit for bit.
+    A uniform vector gives the scalar decode's result bit for bit. There is
+    no keyword for the HBM-resident variant: library option vprior_hbm is its
+    switch (`with _lib.options(vprior_hbm=1): ...`, set once around a run, since
+    every option change invalidates the cached launch plans). With it a code
+    past those limits decodes with hbm_tile_vprior_kernel at
+    any size and degree instead of raising, and with force_hbm=1 as well every
+    prior= decode does; prior_mask stays refused there.
     `osd_method` (with osd_order >= 0): "ref" is the reference's OSDdec of that
     order (order 1 flips one bit, orders >= 2 equal order 0); "cs" is OSD-CS,
     the combination sweep with lambda = osd_order in 0..64:

@@ -1029,6 +1029,14 @@ class _HostPhenomHalf:
         return spacetime.window_advance(n, m, self.T, det, ehat, iters, done, west, witers, nxt)
 
 
+def _hbm_priors_checked(hbm_priors):
+    """hbm_priors= of simulate_phenomenological / simulate_dem / simulate as a
+    bool (ValueError for anything else: a truthy path or number is a mistake)."""
+    if not isinstance(hbm_priors, (bool, np.bool_)):
+        raise ValueError("hbm_priors must be True or False")
+    return bool(hbm_priors)
+
+
 def _window_schedule(T, window, commit):
     """spacetime.window_schedule of window= / commit= (None without window=),
     with the ValueErrors every entry point raises."""
@@ -1072,7 +1080,7 @@ def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float
                               OSDorder: int = -1, rngSeed: Optional[int] = None, *,
                               batch_size: Optional[int] = None, sampler: Optional[str] = None,
                               verbose: bool = True, window: Optional[int] = None, commit: Optional[int] = None,
-                              osd_method: str = "ref", **unsupported) -> dict:
+                              osd_method: str = "ref", hbm_priors: bool = False, **unsupported) -> dict:
     """Phenomenological noise (extension; no reference counterpart): `rounds`
     = T rounds of syndrome extraction with measurement error probability `q`,
     the last round measured perfectly, decoded over each half's space-time
@@ -1088,6 +1096,10 @@ def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float
     equal (every specialised kernel and the HBM-resident one apply, at any
     size), else decode_batch(prior=spacetime_prior(...)) with
     decode_vprior_kernel's limits (its NotImplementedError is passed on).
+    `hbm_priors`: library option vprior_hbm is set around the whole run, so a
+    matrix past those limits (windows included) decodes with
+    hbm_tile_vprior_kernel (DESIGN.md §3.17) at any size instead of raising;
+    matrices within them decode as without it.
 
     decType "MS" or "BP"; decSchedule "F", or "L" / "S" with layers from
     schedule.layerize of the half's own space-time matrix (none of the
@@ -1130,8 +1142,14 @@ def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float
     ValueError: decType RELAY / NG / BF, correlated= and channel_weights= (not
     defined for this model), probabilities outside [0, 1), rounds < 1, a pair
     that is not CSS, window < 1, commit outside [1, window], either one not an
-    integer, commit without window."""
+    integer, commit without window, hbm_priors not a bool."""
     from .logicals import css_logicals
+    if _hbm_priors_checked(hbm_priors):
+        with _lib.options(vprior_hbm=1):       # once around the run: an option change drops the cached launch plans
+            return simulate_phenomenological(Hx, Hz, p, q, rounds, shots, decType, decIterations, decSchedule,
+                                             OSDorder, rngSeed, batch_size=batch_size, sampler=sampler,
+                                             verbose=verbose, window=window, commit=commit, osd_method=osd_method,
+                                             **unsupported)
     for k_ in unsupported:
         if k_ in ("correlated", "channel_weights", "correlated_q1", "logical", "samples"):
             raise ValueError(f"simulate_phenomenological does not take {k_}=: the phenomenological model has "
@@ -1340,7 +1358,8 @@ class _HostDem:
 
 def simulate_dem(dem, shots: int = 1000, decType: str = "MS", decIterations: int = 99, decSchedule: str = "F",
                  OSDorder: int = -1, rngSeed: Optional[int] = None, *, batch_size: Optional[int] = None,
-                 sampler: Optional[str] = None, verbose: bool = True, osd_method: str = "ref") -> dict:
+                 sampler: Optional[str] = None, verbose: bool = True, osd_method: str = "ref",
+                 hbm_priors: bool = False) -> dict:
     """Monte-Carlo decoding of a detector error model (extension; no reference
     counterpart): `dem` is a dem.Dem (dem.load_dem reads Stim's .dem text).
     Each shot fires every mechanism independently with its own probability,
@@ -1354,7 +1373,10 @@ def simulate_dem(dem, shots: int = 1000, decType: str = "MS", decIterations: int
     NotImplementedError is raised when the launch is planned, before any shot
     is drawn. decType "MS" or "BP" (MS rows have at most 32 entries under
     per-column priors; detector rows of circuit-level models are often
-    longer, and BP has no such limit); decSchedule "F", or "L" / "S" with
+    longer, and BP has no such limit). `hbm_priors`: library option vprior_hbm
+    is set around the whole run, so a model past those limits decodes with
+    hbm_tile_vprior_kernel at any size and row degree
+    instead of raising; a model within them decodes as without it. decSchedule "F", or "L" / "S" with
     layers from schedule.layerize(dem.H). OSDorder >= 0 applies to MS and to
     BP here (decoders.apply_osd_device on the device path, decoders.apply_osd
     on the host), `osd_method` as in simulate_p. `sampler`: "device"
@@ -1371,10 +1393,15 @@ def simulate_dem(dem, shots: int = 1000, decType: str = "MS", decIterations: int
     logical_error_rate_ci95, and detectors, errors, observables (M, N, K).
 
     ValueError: decType RELAY / NG / BF or unknown, an unknown schedule or
-    sampler, negative shots, an osd_method that does not fit."""
+    sampler, negative shots, an osd_method that does not fit, hbm_priors not
+    a bool."""
     from .dem import Dem
     if not isinstance(dem, Dem):
         raise ValueError("dem must be a qldpcsim_amd.dem.Dem (dem.load_dem / dem.parse_dem make one)")
+    if _hbm_priors_checked(hbm_priors):
+        with _lib.options(vprior_hbm=1):       # once around the run: an option change drops the cached launch plans
+            return simulate_dem(dem, shots, decType, decIterations, decSchedule, OSDorder, rngSeed,
+                                batch_size=batch_size, sampler=sampler, verbose=verbose, osd_method=osd_method)
     if decType in ("RELAY",) + tuple(_lib.HARD_ALGOS):
         raise ValueError(f"decType {decType} is not available on detector error models (MS or BP)")
     if decType not in ("MS", "BP"):
@@ -1445,9 +1472,10 @@ def format_dem_results(name, r, shots):
 
 
 def _run_dem(path, shots, decType, decIterations, decSchedule, OSDorder, rngSeed, batch_size, sampler, resultsFile,
-             osd_method):
+             osd_method, hbm_priors=False):
     """The command line's --dem mode: load the model, simulate_dem, print the
-    table; rank 0 writes the record (with the run's parameters) to --results."""
+    table; rank 0 writes the record (with the run's parameters; "hbm_priors"
+    only when set) to --results."""
     from .dem import load_dem
     _, rank, world = _dist()
     dem = load_dem(path)
@@ -1455,13 +1483,14 @@ def _run_dem(path, shots, decType, decIterations, decSchedule, OSDorder, rngSeed
         sampler = "device" if _device_ok() else "host"
     res = simulate_dem(dem, shots=shots, decType=decType, decIterations=decIterations, decSchedule=decSchedule,
                        OSDorder=OSDorder, rngSeed=rngSeed, batch_size=batch_size, sampler=sampler, verbose=True,
-                       osd_method=osd_method)
+                       osd_method=osd_method, **({"hbm_priors": True} if _hbm_priors_checked(hbm_priors) else {}))
     if rank == 0:
         print(format_dem_results(path, res, shots))
         if resultsFile:
             meta = {"dem": path, "shots": shots, "decType": decType, "decIterations": decIterations,
                     "decSchedule": decSchedule, "OSDorder": OSDorder, "rngSeed": rngSeed, "world": world,
-                    "sampler": sampler, **decoders._method_kw("osd_method", osd_method)}
+                    "sampler": sampler, **decoders._method_kw("osd_method", osd_method),
+                    **({"hbm_priors": True} if hbm_priors else {})}
             import json
             import os
             with open(resultsFile + ".tmp", "w") as f:
@@ -1548,7 +1577,8 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
              relay_legs: int = 11, relay_leg_iters: int = 60, relay_sols: int = 1, relay_gamma0: float = 0.125,
              relay_gamma_range=(-0.24, 0.66), relay_seed: int = 0, bias: Optional[float] = None,
              channel_weights=None, rounds: Optional[int] = None, meas_error: Optional[float] = None,
-             window: Optional[int] = None, commit: Optional[int] = None, osd_method: str = "ref"):
+             window: Optional[int] = None, commit: Optional[int] = None, osd_method: str = "ref",
+             hbm_priors: bool = False):
     """p-sweep + results table (simulator.py:319-347). Returns None like the
     reference unless return_results=True.
 
@@ -1579,6 +1609,10 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
     resumed sweep with other values is a different sweep) and the table shows
     W/F. window without rounds, commit without window, window < 1, commit
     outside [1, window] and non-integers raise ValueError.
+    hbm_priors (extension; with rounds): simulate_phenomenological's
+    hbm_priors for every point; when set it enters the results file's meta as
+    "hbm_priors": true. Without rounds it raises ValueError (the pair's own
+    halves are always within decode_vprior_kernel's limits or refused alike).
 
     osd_method (extension; decType MS): simulate_p's / simulate_phenomenological's
     OSD method for every point, "ref" or "cs" (OSD-CS, lambda = OSDorder). A
@@ -1600,6 +1634,8 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
         raise ValueError("meas_error needs rounds (the phenomenological model)")
     if rounds is None and (window is not None or commit is not None):
         raise ValueError("window / commit need rounds (the phenomenological model)")
+    if _hbm_priors_checked(hbm_priors) and rounds is None:
+        raise ValueError("hbm_priors needs rounds (the phenomenological model) or a detector error model")
     if rounds is not None:
         if logical or correlated is not None or bias is not None or channel_weights is not None:
             raise ValueError("rounds= (phenomenological noise) cannot be combined with logical, correlated, bias or "
@@ -1609,10 +1645,13 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
         meta = {"Hx": HxFile, "Hz": HzFile, "shots": shots, "decType": decType, "decIterations": decIterations,
                 "decSchedule": decSchedule, "OSDorder": OSDorder, "rngSeed": rngSeed, "world": world,
                 "sampler": sampler, "rounds": int(rounds), "q": None if meas_error is None else float(meas_error)}
-        win = {}                                   # window= / commit=: passed on and recorded only when given
+        win = {}                                   # window= / commit= / hbm_priors=: passed on and recorded only when given
         if _window_schedule(rounds, window, commit) is not None:
             win = {"window": int(window), "commit": 1 if commit is None else int(commit)}
             meta.update(win)
+        if hbm_priors:
+            win["hbm_priors"] = True
+            meta["hbm_priors"] = True
         meta.update(method)
         results = _sweep(p, meta, resultsFile, on_point, rank, lambda pT: simulate_phenomenological(
             Hx, Hz, pT, 2 * pT / 3 if meas_error is None else meas_error, rounds, shots=shots, decType=decType,
@@ -1766,6 +1805,10 @@ def main(argv=None):
                         help="Decode a detector error model instead of a CSS pair: Stim's .dem text, or .npz with "
                              "H, L and priors (MS, BP; --OSDorder applies to both). Takes the place of --Hx, --Hz "
                              "and --p.")
+    parser.add_argument("--hbm-priors", action="store_true", default=argparse.SUPPRESS, dest="hbm_priors",
+                        help="With --rounds or --dem: decode unequal priors past the LDS kernel's limits (matrix "
+                             "size, min-sum rows of more than 32 entries, state past the LDS) with the HBM-resident "
+                             "per-variable-prior kernel instead of refusing them.")
     args = parser.parse_args(argv)
     dem_file = getattr(args, "dem", None)
     if dem_file is not None:
@@ -1788,7 +1831,8 @@ def main(argv=None):
             print("")
         try:
             _run_dem(dem_file, args.shots, args.decType, args.decIterations, args.decSchedule, args.OSDorder,
-                     args.rngSeed, args.batch, args.sampler, args.results, args.osd_method)
+                     args.rngSeed, args.batch, args.sampler, args.results, args.osd_method,
+                     hbm_priors=getattr(args, "hbm_priors", False))
         finally:
             if own_group:
                 import torch.distributed as dist
@@ -1808,6 +1852,8 @@ def main(argv=None):
         parser.error("--window must be >= 1")
     if commit is not None and not (1 <= commit <= window):
         parser.error("--commit must lie in [1, --window]")
+    if getattr(args, "hbm_priors", False) and rounds is None:
+        parser.error("--hbm-priors needs --rounds or --dem")
     if rounds is not None:
         if rounds < 1:
             parser.error("--rounds must be >= 1")
@@ -1831,6 +1877,7 @@ def main(argv=None):
                  **({"channel_weights": np.load(args.channel_weights)} if args.channel_weights else {}),
                  **({"rounds": rounds, "meas_error": meas_error} if rounds is not None else {}),
                  **({"window": window, "commit": commit} if window is not None else {}),
+                 **({"hbm_priors": True} if getattr(args, "hbm_priors", False) else {}),
                  **({"osd_method": args.osd_method} if args.osd_method != "ref" else {}),
                  **({k: getattr(args, k) for k in ("relay_legs", "relay_leg_iters", "relay_sols", "relay_gamma0",
                                                    "relay_gamma_range", "relay_seed")}
