@@ -312,6 +312,47 @@ int qldpc_decode_relay_kernel_name(const qldpc_code *code, const qldpc_relay *re
 int qldpc_decode_relay_launch_info(const qldpc_code *code, const qldpc_relay *relay, int *waves_per_wg,
                                    int *wg_per_cu, int *lds_bytes);
 
+/* Relay min-sum with one prior per variable:
+ * qldpc_decode_device_relay with the prior handle's row in place of p, so
+ *   Lam_j = fl((1 - gamma[r][j]) L_j) + fl(gamma[r][j] M_j),   leg 0 starts from M_j = L_j,
+ * and everything else as there. `prior` is a qldpc_prior of the same code
+ * (another code's: QLDPC_EINVAL) and `eps` must be the eps its row was formed
+ * with (QLDPC_EINVAL otherwise: the row cannot be re-formed per call).
+ * `cost` chooses what "lightest" means among the solutions found:
+ *   QLDPC_RELAY_COST_HAMMING  the number of set bits, as qldpc_decode_device_relay
+ *   QLDPC_RELAY_COST_PRIOR    sum of W_j over the set bits, W_j = llrint(L_j 2^20)
+ *                             (int64, round-half-even; exact, so independent of
+ *                             the order of summation; W_j < 0 where p_j > 1/2)
+ * ties keep the earlier solution under both; any other value is QLDPC_EINVAL.
+ * With every p_j equal and QLDPC_RELAY_COST_HAMMING the outputs equal
+ * qldpc_decode_device_relay's bit for bit. Runs relay_vprior_kernel, which
+ * keeps the row in LDS behind the graph image (8 n bytes, rounded up to 16,
+ * per workgroup); the limits are qldpc_relay_create's, QLDPC_EUNSUP where the
+ * image, the row and one wave's state pass the LDS. Arguments are checked
+ * before any HIP call; a launch plan of its own per relay handle. */
+#define QLDPC_RELAY_COST_HAMMING 0
+#define QLDPC_RELAY_COST_PRIOR 1
+int qldpc_decode_device_relay_vprior(const qldpc_code *code, const qldpc_relay *relay, const qldpc_prior *prior,
+                                     int cost, const void *d_syn, int syn_format, int64_t batch, double beta,
+                                     double eps, void *d_ehat, int ehat_format, int32_t *d_iters, double *d_post,
+                                     int32_t *d_flags, int32_t *d_info, void *stream);
+
+/* Same with host buffers (one byte per bit), staged like qldpc_decode_host. */
+int qldpc_decode_host_relay_vprior(const qldpc_code *code, const qldpc_relay *relay, const qldpc_prior *prior,
+                                   int cost, const uint8_t *h_syn, int64_t batch, double beta, double eps,
+                                   uint8_t *h_ehat, int32_t *h_iters, double *h_post, int32_t *h_flags,
+                                   int32_t *h_info);
+
+/* Name of the kernel qldpc_decode_device_relay_vprior launches
+ * ("relay_vprior_kernel<8>", the instance chosen as relay_ms_kernel's; needs
+ * no device), its launch geometry, and its LDS layout (no device needed):
+ * qldpc_relay_layout's with the prior row counted in out7[0], the slice and
+ * its offsets unchanged. */
+int qldpc_decode_relay_vprior_kernel_name(const qldpc_code *code, const qldpc_relay *relay, char *buf, int len);
+int qldpc_decode_relay_vprior_launch_info(const qldpc_code *code, const qldpc_relay *relay, int *waves_per_wg,
+                                          int *wg_per_cu, int *lds_bytes);
+int qldpc_relay_vprior_layout(const qldpc_relay *relay, int32_t *out7);
+
 /* The hard-decision decoders, batched, device pointers, asynchronous on
  * `stream`. Replaces `batch` calls of NG_decoder(H, syndrome)
  * (decoders.py:27-66) or BF_decoder(H, syndrome, max_iter) (:74-102) — what

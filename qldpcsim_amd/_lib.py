@@ -19,6 +19,7 @@ ALGO = {"MS": 0, "BP": 1, "NG": 2, "BF": 3}
 HARD_ALGOS = ("NG", "BF")            # no schedule, prior or posteriors (qldpc_hard_decode_*)
 FLAG_CONVERGED, FLAG_MIN_ZERO, FLAG_NONFINITE = 1, 2, 4
 FMT_BYTES, FMT_BITS = 0, 1          # syndrome / estimate formats (QLDPC_FMT_*)
+RELAY_COST = {"hamming": 0, "prior": 1}   # what "lightest solution" means (QLDPC_RELAY_COST_*)
 
 # every symbol include/qldpc_decoder.h declares
 EXPORTS = (
@@ -32,6 +33,8 @@ EXPORTS = (
     "qldpc_decode_vprior_kernel_name",
     "qldpc_relay_create", "qldpc_relay_destroy", "qldpc_relay_layout", "qldpc_decode_device_relay",
     "qldpc_decode_host_relay", "qldpc_decode_relay_kernel_name", "qldpc_decode_relay_launch_info",
+    "qldpc_decode_device_relay_vprior", "qldpc_decode_host_relay_vprior", "qldpc_decode_relay_vprior_kernel_name",
+    "qldpc_decode_relay_vprior_launch_info", "qldpc_relay_vprior_layout",
     "qldpc_hard_decode_device", "qldpc_hard_decode_host", "qldpc_hard_kernel_name", "qldpc_hard_launch_info",
     "qldpc_osd_decode", "qldpc_osd_decode_batch", "qldpc_osd_device", "qldpc_osd_order_device",
     "qldpc_osd_device_ordered", "qldpc_osd_device_ordered_ex", "qldpc_cpython_setdiff_first",
@@ -102,6 +105,11 @@ def _load():
         "qldpc_decode_host_relay": ([P, P, P, I64, D, D, D, P, P, P, P, P], I),
         "qldpc_decode_relay_kernel_name": ([P, P, ctypes.c_char_p, I], I),
         "qldpc_decode_relay_launch_info": ([P, P, ctypes.POINTER(I), ctypes.POINTER(I), ctypes.POINTER(I)], I),
+        "qldpc_decode_device_relay_vprior": ([P, P, P, I, P, I, I64, D, D, P, I, P, P, P, P, P], I),
+        "qldpc_decode_host_relay_vprior": ([P, P, P, I, P, I64, D, D, P, P, P, P, P], I),
+        "qldpc_decode_relay_vprior_kernel_name": ([P, P, ctypes.c_char_p, I], I),
+        "qldpc_decode_relay_vprior_launch_info": ([P, P, ctypes.POINTER(I), ctypes.POINTER(I), ctypes.POINTER(I)], I),
+        "qldpc_relay_vprior_layout": ([P, P], I),
         "qldpc_hard_decode_device": ([P, I, P, I, I64, I, P, I, P, P, P], I),
         "qldpc_hard_decode_host": ([P, I, P, I64, I, P, P, P], I),
         "qldpc_hard_kernel_name": ([P, I, ctypes.c_char_p, I], I),
@@ -213,10 +221,13 @@ class Schedule:
 class Relay:
     """Legs, memory strengths and solution count of a relay min-sum decoder
     bound to a Code (qldpc_relay). `gammas` is float64 [legs, n] in original
-    column order."""
+    column order. `prior` (a Prior of the same code, or None): the handle
+    decodes with relay_vprior_kernel and that row, and
+    layout(), kernel_name() and launch_info() describe that kernel."""
 
-    def __init__(self, code, leg_iters, gammas, sols):
+    def __init__(self, code, leg_iters, gammas, sols, prior=None):
         self.code = code
+        self.prior = prior
         self.leg_iters = np.ascontiguousarray(leg_iters, dtype=np.int32).reshape(-1)
         g = np.ascontiguousarray(gammas, dtype=np.float64)
         if g.ndim != 2 or g.shape[0] != len(self.leg_iters):
@@ -232,20 +243,22 @@ class Relay:
         """Per-wave LDS layout of the relay kernel (no device needed): bytes of
         the graph image and of a wave's slice, and the offsets inside it."""
         out = np.zeros(7, np.int32)
-        check(lib.qldpc_relay_layout(self.handle, ptr(out)))
+        check((lib.qldpc_relay_layout if self.prior is None else lib.qldpc_relay_vprior_layout)(self.handle, ptr(out)))
         return dict(zip(("image", "wave_bytes", "off_c2v", "off_synw", "off_m", "off_ew", "off_best"),
                         (int(x) for x in out)))
 
     def kernel_name(self):
         buf = ctypes.create_string_buffer(128)
-        check(lib.qldpc_decode_relay_kernel_name(self.code.handle, self.handle, buf, 128))
+        check((lib.qldpc_decode_relay_kernel_name if self.prior is None else
+               lib.qldpc_decode_relay_vprior_kernel_name)(self.code.handle, self.handle, buf, 128))
         return buf.value.decode()
 
     def launch_info(self):
         """(waves per workgroup, workgroups per CU, LDS bytes per workgroup)"""
         w, b, l = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-        check(lib.qldpc_decode_relay_launch_info(self.code.handle, self.handle, ctypes.byref(w), ctypes.byref(b),
-                                                 ctypes.byref(l)))
+        check((lib.qldpc_decode_relay_launch_info if self.prior is None else
+               lib.qldpc_decode_relay_vprior_launch_info)(self.code.handle, self.handle, ctypes.byref(w),
+                                                          ctypes.byref(b), ctypes.byref(l)))
         return w.value, b.value, l.value
 
     def __del__(self):
@@ -306,14 +319,20 @@ class Code:
                 self._prior[key] = r
             return r
 
-    def relay(self, leg_iters, gammas, sols):
-        """Cached Relay handle per (leg counts, table bytes, sols), as schedules are."""
+    def relay(self, leg_iters, gammas, sols, *, prior=None, eps=1e-9):
+        """Cached Relay handle per (leg counts, table bytes, sols), as schedules
+        are. `prior` (float64 [n] probabilities, original column order) with
+        `eps`: a handle of its own per prior row, bound to self.prior(prior, eps)."""
         key = (np.asarray(leg_iters, np.int32).tobytes(), np.ascontiguousarray(gammas, np.float64).tobytes(),
                int(sols))
+        pr = None
+        if prior is not None:
+            pr = self.prior(prior, eps)
+            key += (pr.probs.tobytes(), pr.eps)
         with self._lock:
             r = self._relay.get(key)
             if r is None:
-                r = Relay(self, leg_iters, gammas, sols)
+                r = Relay(self, leg_iters, gammas, sols, pr)
                 self._relay[key] = r
             return r
 

@@ -865,12 +865,15 @@ extern "C" int qldpc_prior_create(const qldpc_code* code, const double* h_p, dou
       return fail(QLDPC_EINVAL, "per-variable priors: p[%d] = %g with eps = %g has no finite prior", code->vperm[j],
                   h_p[code->vperm[j]], eps);
   }
+  pr->W.resize(n);                                    // |L_j| < 750: L_j 2^20 is exact and fits; round-half-even
+  for (int j = 0; j < n; ++j) pr->W[j] = (int64_t)std::llrint(std::ldexp(pr->L[j], 20));
   if (code->device >= 0) {
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
     if (dev != code->device)
       return fail(QLDPC_EINVAL, "code lives on device %d, current device is %d", code->device, dev);
     HIP_TRY(pr->d_L.upload(pr->L));
+    HIP_TRY(pr->d_W.upload(pr->W));
   }
   pr->filt0 = prior_filter_word(code, pr->L);
   *out = pr.release();

@@ -241,6 +241,8 @@ struct qldpc_prior {
   double eps = 0.0;
   std::vector<double> L;         // [n] L_j = log((1 - p_j) / max(p_j, eps)), relabeled variable order
   capi::DevBuf<double> d_L;
+  std::vector<int64_t> W;        // [n] llrint(L_j 2^20): relay_vprior_kernel's solution weights
+  capi::DevBuf<int64_t> d_W;
   uint32_t filt0 = 0;            // prior_filter_word(code, L): hbm_tile_vprior_kernel's filter word at start
 };
 

@@ -1,6 +1,7 @@
 // capi_relay.cpp — relay min-sum: the qldpc_relay handle
-// (legs, memory strengths, a flooding schedule of its own), its launch plan
-// and the decode entry points.
+// (legs, memory strengths, a flooding schedule of its own), its launch plans
+// and the decode entry points, the scalar-prior ones (relay_ms_kernel) and
+// the per-variable-prior ones (relay_vprior_kernel, §3.18).
 
 #include <cmath>
 #include <cstdio>
@@ -12,6 +13,7 @@
 
 using namespace capi;
 using qldpc::RelayArgs;
+using qldpc::RelayVpriorArgs;
 
 namespace {
 
@@ -35,7 +37,7 @@ struct qldpc_relay {
   DevBuf<int32_t> d_leg_iters;
   DevBuf<double> d_gamma;
   std::mutex mu;                         // the plan, and the host path's info buffer
-  RelayPlan plan;
+  RelayPlan plan[2];                     // [0] relay_ms_kernel, [1] relay_vprior_kernel
   DevBuf<int32_t> ws_info;
   int64_t ws_info_cap = 0;
   ~qldpc_relay() { qldpc_schedule_destroy(sched); }
@@ -55,12 +57,16 @@ static int relay_limits(const qldpc_code* c) {
   return QLDPC_OK;
 }
 
-static const void* relay_choose(const qldpc_code* c, const char** name) {
-  return qldpc::select_relay_kernel(fast_table_ok(c) ? c->uniform_deg : 0, name);
+// `vp`: relay_vprior_kernel, the same instance of it
+static const void* relay_choose(const qldpc_code* c, bool vp, const char** name) {
+  return (vp ? qldpc::select_relay_vprior_kernel : qldpc::select_relay_kernel)(fast_table_ok(c) ? c->uniform_deg : 0,
+                                                                              name);
 }
 
-// X f64[n] | c2v f32[E + 8] | syndrome words | M f64[n] | hard-decision words | best-solution words
-static int relay_plan_static(const qldpc_relay* r, RelayArgs* ra) {
+// X f64[n] | c2v f32[E + 8] | syndrome words | M f64[n] | hard-decision words | best-solution words;
+// `vp`: the prior row f64[n] between the image and the slices, counted in the
+// bytes returned, the slices as without it
+static int relay_plan_static(const qldpc_relay* r, bool vp, RelayArgs* ra) {
   const qldpc_code* c = r->code;
   const TableImage& t = r->sched->generic;
   qldpc::DecodeArgs& a = ra->d;
@@ -85,7 +91,8 @@ static int relay_plan_static(const qldpc_relay* r, RelayArgs* ra) {
   a.wave_bytes = std::max(off, 16);
   ra->gamma = r->d_gamma, ra->leg_iters = r->d_leg_iters;
   ra->legs = r->legs, ra->sols = r->sols;
-  return t.lds_bytes;
+  a.vprior_bytes = vp ? align16(8 * c->n) : 0;
+  return t.lds_bytes + a.vprior_bytes;
 }
 
 // ---------------------------------------------------------------------------
@@ -136,36 +143,51 @@ extern "C" int qldpc_relay_destroy(qldpc_relay* relay) {
   return QLDPC_OK;
 }
 
-extern "C" int qldpc_relay_layout(const qldpc_relay* relay, int32_t* out7) {
+static int relay_layout(const qldpc_relay* relay, bool vp, int32_t* out7) {
   if (!relay || !out7) return fail(QLDPC_EINVAL, "null argument");
   if (int rc = relay_limits(relay->code)) return rc;
   RelayArgs ra{};
-  out7[0] = relay_plan_static(relay, &ra);
+  out7[0] = relay_plan_static(relay, vp, &ra);
   out7[1] = ra.d.wave_bytes, out7[2] = ra.d.off_c2v, out7[3] = ra.d.off_synw;
   out7[4] = ra.off_m, out7[5] = ra.off_ew, out7[6] = ra.off_best;
   return QLDPC_OK;
 }
 
-extern "C" int qldpc_decode_relay_kernel_name(const qldpc_code* code, const qldpc_relay* relay, char* buf, int len) {
+extern "C" int qldpc_relay_layout(const qldpc_relay* relay, int32_t* out7) { return relay_layout(relay, false, out7); }
+
+extern "C" int qldpc_relay_vprior_layout(const qldpc_relay* relay, int32_t* out7) {
+  return relay_layout(relay, true, out7);
+}
+
+static int relay_kernel_name(const qldpc_code* code, const qldpc_relay* relay, bool vp, char* buf, int len) {
   if (!code || !relay || !buf || len <= 0) return fail(QLDPC_EINVAL, "null argument");
   if (relay->code != code) return fail(QLDPC_EINVAL, "relay handle was built for a different code");
   if (int rc = relay_limits(code)) return rc;
   const char* name = "";
-  (void)relay_choose(code, &name);
+  (void)relay_choose(code, vp, &name);
   snprintf(buf, (size_t)len, "%s", name);
   return QLDPC_OK;
+}
+
+extern "C" int qldpc_decode_relay_kernel_name(const qldpc_code* code, const qldpc_relay* relay, char* buf, int len) {
+  return relay_kernel_name(code, relay, false, buf, len);
+}
+
+extern "C" int qldpc_decode_relay_vprior_kernel_name(const qldpc_code* code, const qldpc_relay* relay, char* buf,
+                                                     int len) {
+  return relay_kernel_name(code, relay, true, buf, len);
 }
 
 // ---------------------------------------------------------------------------
 // launch plan, device half: occupancy; cached in the handle per option generation
 // ---------------------------------------------------------------------------
-static int build_plan(qldpc_relay* r, RelayPlan* p) {
+static int build_plan(qldpc_relay* r, bool vp, RelayPlan* p) {
   int dev = 0, max_lds = 0;
   HIP_TRY(hipGetDevice(&dev));
   HIP_TRY(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
   HIP_TRY(hipDeviceGetAttribute(&p->cus, hipDeviceAttributeMultiprocessorCount, dev));
-  p->kernel = relay_choose(r->code, &p->name);
-  const int image_lds = relay_plan_static(r, &p->args);
+  p->kernel = relay_choose(r->code, vp, &p->name);
+  const int image_lds = relay_plan_static(r, vp, &p->args);
   HIP_TRY(qldpc::configure_relay_kernel(p->kernel, max_lds));
   const int max_waves = QLDPC_MAX_THREADS / 64;
   const int wb = p->args.d.wave_bytes;
@@ -181,8 +203,8 @@ static int build_plan(qldpc_relay* r, RelayPlan* p) {
     if (nb * w > best) p->waves = w, p->blocks_per_cu = nb, p->lds = lds, best = nb * w;
   }
   if (best == 0)
-    return fail(QLDPC_EUNSUP, "relay min-sum: the tables and one wave's state (%d + %d B) do not fit the %d B of "
-                "LDS; there is no HBM-resident variant", image_lds, wb, max_lds);
+    return fail(QLDPC_EUNSUP, "relay min-sum: the tables%s and one wave's state (%d + %d B) do not fit the %d B of "
+                "LDS; there is no HBM-resident variant", vp ? ", the prior row" : "", image_lds, wb, max_lds);
   // Tuning overrides (experiments, tests): options waves_per_wg, wg_per_cu.
   if (const int64_t ow = opt(&Options::waves_per_wg)) {
     const int w = (int)ow, lds = image_lds + w * wb;
@@ -197,39 +219,57 @@ static int build_plan(qldpc_relay* r, RelayPlan* p) {
   return QLDPC_OK;
 }
 
-static int resolve_plan(qldpc_relay* r, RelayPlan* out) {
+static int resolve_plan(qldpc_relay* r, bool vp, RelayPlan* out) {
   std::lock_guard<std::mutex> lk(r->mu);
   const uint32_t gen = g_opt.gen.load();
-  if (!r->plan.ok || r->plan.gen != gen) {
+  RelayPlan& slot = r->plan[vp ? 1 : 0];
+  if (!slot.ok || slot.gen != gen) {
     RelayPlan p{};                                    // built aside, published whole
-    if (int rc = build_plan(r, &p)) return rc;
+    if (int rc = build_plan(r, vp, &p)) return rc;
     p.ok = true;
     p.gen = gen;
-    r->plan = p;
+    slot = p;
   }
-  *out = r->plan;
+  *out = slot;
   return QLDPC_OK;
 }
 
-extern "C" int qldpc_decode_relay_launch_info(const qldpc_code* code, const qldpc_relay* relay_c, int* waves_per_wg,
-                                              int* wg_per_cu, int* lds_bytes) {
+static int relay_launch_info(const qldpc_code* code, const qldpc_relay* relay_c, bool vp, int* waves_per_wg,
+                             int* wg_per_cu, int* lds_bytes) {
   auto* relay = const_cast<qldpc_relay*>(relay_c);
   if (!code || !relay || !waves_per_wg || !wg_per_cu || !lds_bytes) return fail(QLDPC_EINVAL, "null argument");
   if (relay->code != code) return fail(QLDPC_EINVAL, "relay handle was built for a different code");
   if (int rc = relay_limits(code)) return rc;
   if (code->device < 0) return fail(QLDPC_EHIP, "no HIP device was visible when the code was created");
   RelayPlan plan;
-  if (int rc = resolve_plan(relay, &plan)) return rc;
+  if (int rc = resolve_plan(relay, vp, &plan)) return rc;
   *waves_per_wg = plan.waves, *wg_per_cu = plan.blocks_per_cu, *lds_bytes = plan.lds;
   return QLDPC_OK;
+}
+
+extern "C" int qldpc_decode_relay_launch_info(const qldpc_code* code, const qldpc_relay* relay, int* waves_per_wg,
+                                              int* wg_per_cu, int* lds_bytes) {
+  return relay_launch_info(code, relay, false, waves_per_wg, wg_per_cu, lds_bytes);
+}
+
+extern "C" int qldpc_decode_relay_vprior_launch_info(const qldpc_code* code, const qldpc_relay* relay,
+                                                     int* waves_per_wg, int* wg_per_cu, int* lds_bytes) {
+  return relay_launch_info(code, relay, true, waves_per_wg, wg_per_cu, lds_bytes);
 }
 
 // ---------------------------------------------------------------------------
 // decode
 // ---------------------------------------------------------------------------
 // everything checked before any HIP call; *done: nothing to launch
+// what a per-variable-prior call brings on top of the scalar one's arguments
+struct VpriorCall {
+  const qldpc_prior* prior;
+  int cost;
+};
+
 static int validate(const qldpc_code* code, const qldpc_relay* relay, int syn_format, int ehat_format, int64_t batch,
-                    const void* syn, const void* ehat, const void* iters, bool* done) {
+                    const void* syn, const void* ehat, const void* iters, bool* done, const VpriorCall* vp = nullptr,
+                    double eps = 0.0) {
   *done = false;
   if ((syn_format != QLDPC_FMT_BYTES && syn_format != QLDPC_FMT_BITS) ||
       (ehat_format != QLDPC_FMT_BYTES && ehat_format != QLDPC_FMT_BITS))
@@ -237,6 +277,17 @@ static int validate(const qldpc_code* code, const qldpc_relay* relay, int syn_fo
   if (!code || !relay) return fail(QLDPC_EINVAL, "code/relay is null");
   if (relay->code != code) return fail(QLDPC_EINVAL, "relay handle was built for a different code");
   if (batch < 0) return fail(QLDPC_EINVAL, "negative batch");
+  if (vp) {
+    const qldpc_prior* pr = vp->prior;
+    if (!pr) return fail(QLDPC_EINVAL, "prior handle is null");
+    if (pr->code != code || pr->n != code->n || pr->m != code->m || pr->E != code->E)
+      return fail(QLDPC_EINVAL, "prior handle was built for a different code");
+    if (!(eps == pr->eps))
+      return fail(QLDPC_EINVAL, "relay min-sum: eps = %g, but the prior row was formed with eps = %g", eps, pr->eps);
+    if (vp->cost != QLDPC_RELAY_COST_HAMMING && vp->cost != QLDPC_RELAY_COST_PRIOR)
+      return fail(QLDPC_EINVAL, "relay min-sum: unknown solution cost %d (0: Hamming weight, 1: prior weight)",
+                  vp->cost);
+  }
   if (int rc = relay_limits(code)) return rc;
   if (batch == 0) {
     *done = true;
@@ -245,22 +296,26 @@ static int validate(const qldpc_code* code, const qldpc_relay* relay, int syn_fo
   if (!syn || !ehat || !iters) return fail(QLDPC_EINVAL, "null buffer");
   if (code->device < 0 || !relay->sched->generic.dev)
     return fail(QLDPC_EHIP, "no HIP device was visible when the code/relay handle was created");
+  if (vp && (!vp->prior->d_L.p || !vp->prior->d_W.p))
+    return fail(QLDPC_EHIP, "no HIP device was visible when the prior handle was created");
   return QLDPC_OK;
 }
 
-extern "C" int qldpc_decode_device_relay(const qldpc_code* code, const qldpc_relay* relay_c, const void* d_syn,
-                                         int syn_format, int64_t batch, double p, double beta, double eps,
-                                         void* d_ehat, int ehat_format, int32_t* d_iters, double* d_post,
-                                         int32_t* d_flags, int32_t* d_info, void* stream) {
+// qldpc_decode_device_relay, and with `vp` qldpc_decode_device_relay_vprior (p is then unread)
+static int relay_device(const qldpc_code* code, const qldpc_relay* relay_c, const VpriorCall* vp, const void* d_syn,
+                        int syn_format, int64_t batch, double p, double beta, double eps, void* d_ehat,
+                        int ehat_format, int32_t* d_iters, double* d_post, int32_t* d_flags, int32_t* d_info,
+                        void* stream) {
   auto* relay = const_cast<qldpc_relay*>(relay_c);
   bool done = false;
-  if (int rc = validate(code, relay, syn_format, ehat_format, batch, d_syn, d_ehat, d_iters, &done)) return rc;
+  if (int rc = validate(code, relay, syn_format, ehat_format, batch, d_syn, d_ehat, d_iters, &done, vp, eps))
+    return rc;
   if (done) return QLDPC_OK;
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
   if (dev != code->device) return fail(QLDPC_EINVAL, "code lives on device %d, current device is %d", code->device, dev);
   RelayPlan plan;
-  if (int rc = resolve_plan(relay, &plan)) return rc;
+  if (int rc = resolve_plan(relay, vp != nullptr, &plan)) return rc;
   hipStream_t st = (hipStream_t)stream;
   RelayArgs ra = plan.args;
   qldpc::DecodeArgs& a = ra.d;
@@ -269,8 +324,13 @@ extern "C" int qldpc_decode_device_relay(const qldpc_code* code, const qldpc_rel
   a.iters = d_iters, a.post = d_post, a.flags = d_flags;
   ra.info = d_info;
   a.batch = batch;
-  a.L = qldpc_prior_llr(p, eps);                      // np.log prior, as MS takes it
-  a.L32 = (float)a.L;
+  if (vp) {
+    a.vprior = vp->prior->d_L;
+    a.L = 0.0, a.L32 = 0.0f;                          // (unread: every prior comes from the row)
+  } else {
+    a.L = qldpc_prior_llr(p, eps);                    // np.log prior, as MS takes it
+    a.L32 = (float)a.L;
+  }
   a.beta = beta, a.eps = eps;
   a.max_iter = relay->leg_iters[0];                   // (unread: the legs carry the counts)
   qldpc_schedule* s = relay->sched;
@@ -284,17 +344,41 @@ extern "C" int qldpc_decode_device_relay(const qldpc_code* code, const qldpc_rel
   const int grid = (int)std::max<int64_t>(1, std::min(need, resident));
   TimedLaunch t;
   if (int rc = timing_begin(&t, st)) return rc;
-  HIP_TRY(qldpc::launch_relay(plan.kernel, ra, grid, 64 * plan.waves, plan.lds, st));
+  if (vp)
+    HIP_TRY(qldpc::launch_relay_vprior(plan.kernel, RelayVpriorArgs{ra, (const long long*)vp->prior->d_W.p, vp->cost},
+                                       grid, 64 * plan.waves, plan.lds, st));
+  else
+    HIP_TRY(qldpc::launch_relay(plan.kernel, ra, grid, 64 * plan.waves, plan.lds, st));
   return timing_end(&t, st);
 }
 
-extern "C" int qldpc_decode_host_relay(const qldpc_code* code_c, const qldpc_relay* relay_c, const uint8_t* h_syn,
-                                       int64_t batch, double p, double beta, double eps, uint8_t* h_ehat,
-                                       int32_t* h_iters, double* h_post, int32_t* h_flags, int32_t* h_info) {
+extern "C" int qldpc_decode_device_relay(const qldpc_code* code, const qldpc_relay* relay, const void* d_syn,
+                                         int syn_format, int64_t batch, double p, double beta, double eps,
+                                         void* d_ehat, int ehat_format, int32_t* d_iters, double* d_post,
+                                         int32_t* d_flags, int32_t* d_info, void* stream) {
+  return relay_device(code, relay, nullptr, d_syn, syn_format, batch, p, beta, eps, d_ehat, ehat_format, d_iters,
+                      d_post, d_flags, d_info, stream);
+}
+
+extern "C" int qldpc_decode_device_relay_vprior(const qldpc_code* code, const qldpc_relay* relay,
+                                                const qldpc_prior* prior, int cost, const void* d_syn, int syn_format,
+                                                int64_t batch, double beta, double eps, void* d_ehat, int ehat_format,
+                                                int32_t* d_iters, double* d_post, int32_t* d_flags, int32_t* d_info,
+                                                void* stream) {
+  const VpriorCall vp{prior, cost};
+  return relay_device(code, relay, &vp, d_syn, syn_format, batch, 0.0, beta, eps, d_ehat, ehat_format, d_iters,
+                      d_post, d_flags, d_info, stream);
+}
+
+// qldpc_decode_host_relay, and with `vp` qldpc_decode_host_relay_vprior
+static int relay_host(const qldpc_code* code_c, const qldpc_relay* relay_c, const VpriorCall* vp, const uint8_t* h_syn,
+                      int64_t batch, double p, double beta, double eps, uint8_t* h_ehat, int32_t* h_iters,
+                      double* h_post, int32_t* h_flags, int32_t* h_info) {
   auto* code = const_cast<qldpc_code*>(code_c);
   auto* relay = const_cast<qldpc_relay*>(relay_c);
   bool done = false;
-  if (int rc = validate(code, relay, QLDPC_FMT_BYTES, QLDPC_FMT_BYTES, batch, h_syn, h_ehat, h_iters, &done)) return rc;
+  if (int rc = validate(code, relay, QLDPC_FMT_BYTES, QLDPC_FMT_BYTES, batch, h_syn, h_ehat, h_iters, &done, vp, eps))
+    return rc;
   if (done) return QLDPC_OK;
   std::lock_guard<std::mutex> lk(code->ws_mu);
   const int64_t m = code->m, n = code->n;
@@ -312,9 +396,9 @@ extern "C" int qldpc_decode_host_relay(const qldpc_code* code_c, const qldpc_rel
     memcpy(code->hp_syn, h_syn, batch * m);
     HIP_TRY(hipMemcpyAsync(code->ws_syn, code->hp_syn, batch * m, hipMemcpyHostToDevice, st));
   }
-  if (int rc = qldpc_decode_device_relay(code, relay, code->ws_syn, QLDPC_FMT_BYTES, batch, p, beta, eps, code->ws_ehat,
-                                         QLDPC_FMT_BYTES, code->ws_iters, h_post ? code->ws_post.p : nullptr,
-                                         code->ws_flags, h_info ? relay->ws_info.p : nullptr, st))
+  if (int rc = relay_device(code, relay, vp, code->ws_syn, QLDPC_FMT_BYTES, batch, p, beta, eps, code->ws_ehat,
+                            QLDPC_FMT_BYTES, code->ws_iters, h_post ? code->ws_post.p : nullptr, code->ws_flags,
+                            h_info ? relay->ws_info.p : nullptr, st))
     return rc;
   if (batch * n) HIP_TRY(hipMemcpyAsync(code->hp_ehat, code->ws_ehat, batch * n, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(code->hp_iters, code->ws_iters, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, st));
@@ -328,4 +412,18 @@ extern "C" int qldpc_decode_host_relay(const qldpc_code* code_c, const qldpc_rel
   if (h_flags) memcpy(h_flags, code->hp_flags, sizeof(int32_t) * batch);
   if (h_post && batch * n) memcpy(h_post, code->hp_post, sizeof(double) * batch * n);
   return QLDPC_OK;
+}
+
+extern "C" int qldpc_decode_host_relay(const qldpc_code* code, const qldpc_relay* relay, const uint8_t* h_syn,
+                                       int64_t batch, double p, double beta, double eps, uint8_t* h_ehat,
+                                       int32_t* h_iters, double* h_post, int32_t* h_flags, int32_t* h_info) {
+  return relay_host(code, relay, nullptr, h_syn, batch, p, beta, eps, h_ehat, h_iters, h_post, h_flags, h_info);
+}
+
+extern "C" int qldpc_decode_host_relay_vprior(const qldpc_code* code, const qldpc_relay* relay,
+                                              const qldpc_prior* prior, int cost, const uint8_t* h_syn, int64_t batch,
+                                              double beta, double eps, uint8_t* h_ehat, int32_t* h_iters,
+                                              double* h_post, int32_t* h_flags, int32_t* h_info) {
+  const VpriorCall vp{prior, cost};
+  return relay_host(code, relay, &vp, h_syn, batch, 0.0, beta, eps, h_ehat, h_iters, h_post, h_flags, h_info);
 }

@@ -36,7 +36,8 @@
 // (bp_team_kernels.hip, built without SLP vectorization; ms_flood_kernels.hip,
 // built with the max-ILP machine scheduler), and so are the two-level-prior
 // kernels (decode_prior_kernels.hip), the per-variable-prior kernels
-// (decode_vprior_kernels.hip) and relay min-sum (relay_kernels.hip). Each
+// (decode_vprior_kernels.hip) and relay min-sum (relay_kernels.hip,
+// relay_vprior_kernels.hip). Each
 // includes its family's header (bp_team.h, ms_flood.h, ms_layered.h,
 // decode_generic.h) over decoder_common.h and wave_common.h.
 

@@ -26,4 +26,19 @@ hipError_t launch_relay(const void* kernel, const RelayArgs& args, int grid, int
                         hipStream_t stream);
 hipError_t configure_relay_kernel(const void* kernel, int lds_bytes);
 
+// relay_vprior_kernel's arguments: relay_ms_kernel's, with
+// the prior row in d.vprior / d.vprior_bytes as decode_vprior_kernel takes it
+// (staged into LDS between the graph image and the wave slices; d.L is
+// unread), and the solution cost behind them.
+struct RelayVpriorArgs {
+  RelayArgs r;
+  const long long* wgt;       // [n] W_j = llrint(L_j 2^20), relabeled variable order (global)
+  int cost;                   // 0: a solution weighs its set bits, 1: the sum of wgt over them
+};
+
+// relay_vprior_kernel<dc>, chosen as relay_ms_kernel<dc> is
+const void* select_relay_vprior_kernel(int dc, const char** name);
+hipError_t launch_relay_vprior(const void* kernel, const RelayVpriorArgs& args, int grid, int block, int lds_bytes,
+                               hipStream_t stream);
+
 }  // namespace qldpc

@@ -84,10 +84,17 @@ class DecodeResult:
 class RelayConfig:
     """Settings of decode_batch(algo="RELAY"): iterations per leg, the memory
     strengths float64 [legs, n] in original column order (relay_gammas), and
-    the number of solutions to stop at."""
+    the number of solutions to stop at. `prior`: one error
+    probability per column of H, float64 [n] in original column order, every
+    0 <= q_j < 1, in place of decode_batch's scalar `p` (which must then be
+    None). `cost`: which of the solutions found is kept, "hamming" (the fewest
+    set bits) or "prior" (the smallest sum of the set bits' prior weights
+    llrint(L_j 2^20); needs `prior`); ties keep the earlier one."""
     leg_iters: object
     gammas: object
     sols: int = 1
+    prior: object = None
+    cost: str = "hamming"
 
 
 def relay_gammas(n, legs, gamma0=0.125, lo=-0.24, hi=0.66, seed=0):
@@ -173,6 +180,12 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
     osd_order >= 0 raise ValueError (post is returned with want_post, so a
     caller can run OSDdec on the failures). The result's `info` (`found`,
     `best_leg`) says how many solutions each shot met and which leg's was kept.
+    With `relay.prior` (one probability per column; `p` must be None) the
+    blend takes each variable's own prior and relay_vprior_kernel runs
+    (DESIGN.md §3.18); `relay.cost="prior"` keeps the solution of least prior
+    weight instead of least Hamming weight. A uniform row with cost "hamming"
+    gives the scalar relay's result bit for bit. The top-level `prior=` stays
+    refused with RELAY.
     """
     osd_method_checked(osd_method, osd_order, algo)
     if prior is not None:
@@ -232,9 +245,16 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
 
 def _decode_batch_relay(H, syndromes, p, relay, layers, beta, eps, want_post, osd_order, layer_ptr, layer_rows,
                         stream, out, ehat_bits, prior_mask, p_masked):
-    """decode_batch for algo "RELAY" (relay_ms_kernel)."""
+    """decode_batch for algo "RELAY" (relay_ms_kernel; with relay.prior
+    relay_vprior_kernel)."""
     if not isinstance(relay, RelayConfig):
         raise ValueError('algo="RELAY" needs relay=RelayConfig(leg_iters, gammas, sols)')
+    if relay.cost not in _lib.RELAY_COST:
+        raise ValueError(f"relay.cost must be one of {tuple(_lib.RELAY_COST)}, got {relay.cost!r}")
+    if relay.prior is None and relay.cost == "prior":
+        raise ValueError('relay.cost="prior" weighs solutions by relay.prior: give the prior row')
+    if relay.prior is not None and p is not None:
+        raise ValueError("give either p (one scalar prior) or relay.prior (one per column), not both")
     if prior_mask is not None or p_masked is not None:
         raise ValueError("relay min-sum takes no two-level prior (prior_mask)")
     if osd_order >= 0:
@@ -252,10 +272,22 @@ def _decode_batch_relay(H, syndromes, p, relay, layers, beta, eps, want_post, os
     if G.shape != (len(T), n):
         raise ValueError(f"relay.gammas must be float64 [{len(T)}, {n}] (one row per leg, one entry per variable)")
     host = not _is_torch(syndromes)
+    make = _lib.Code.relay
+    if relay.prior is not None:
+        q = np.ascontiguousarray(relay.prior, dtype=np.float64)
+        if q.shape != (n,):
+            raise ValueError(f"relay.prior must hold {n} probabilities (one per column of H), got shape {q.shape}")
+
+        def make(code, *made_from):
+            return code.relay(*made_from, prior=q, eps=eps)
     code, rl, res, ins, _, outs, held = (_host_batch if host else _device_batch)(
-        H, syndromes, _lib.Code.relay, (T, G, relay.sols), want_post, out=out, stream=stream, ehat_bits=ehat_bits,
+        H, syndromes, make, (T, G, relay.sols), want_post, out=out, stream=stream, ehat_bits=ehat_bits,
         has_info=True)
     L = _lib.lib
+    if relay.prior is not None:
+        _lib.check((L.qldpc_decode_host_relay_vprior if host else L.qldpc_decode_device_relay_vprior)(
+            code.handle, rl.handle, rl.prior.handle, _lib.RELAY_COST[relay.cost], *ins, float(beta), float(eps), *outs))
+        return res
     _lib.check((L.qldpc_decode_host_relay if host else L.qldpc_decode_device_relay)(
         code.handle, rl.handle, *ins, float(p), float(beta), float(eps), *outs))
     return res
@@ -1024,15 +1056,18 @@ def BP_decoder(H: np.ndarray, syndrome: np.ndarray, p: float, max_iter: int = 99
 
 
 def Relay_decoder(H: np.ndarray, syndrome: np.ndarray, p: float, leg_iters, gammas, sols: int = 1,
-                  beta: float = 0.75, eps: float = 1e-9):
+                  beta: float = 0.75, eps: float = 1e-9, cost: str = "hamming"):
     """Relay min-sum of one syndrome on the GPU, in the style
     of MS_decoder: (e_hat int8 [n], passes run over all legs). `gammas` is
-    float64 [len(leg_iters), n] (relay_gammas)."""
+    float64 [len(leg_iters), n] (relay_gammas). `p` may be an array of n
+    probabilities, one per column, as MS_decoder's (RelayConfig.prior, §3.18);
+    `cost` is RelayConfig.cost ("prior" needs the array)."""
     H, syndrome, bare = _shot(H, syndrome)
     if bare is not None:
         return bare
-    r = decode_batch(H, _row(H, syndrome), p, 0, algo="RELAY", beta=beta, eps=eps,
-                     relay=RelayConfig(leg_iters, gammas, sols))
+    vec = np.ndim(p) > 0
+    r = decode_batch(H, _row(H, syndrome), None if vec else p, 0, algo="RELAY", beta=beta, eps=eps,
+                     relay=RelayConfig(leg_iters, gammas, sols, prior=p if vec else None, cost=cost))
     return r.ehat[0].astype(np.int8), int(r.iters[0])
 
 

@@ -523,6 +523,27 @@ def _osd_method(osd_method, OSDorder, decType):
     return decoders.osd_method_checked(osd_method, OSDorder)
 
 
+def _relay_cost(cost, vector):
+    """relay_cost of a half decoded with a prior row (`vector`) or one scalar
+    prior: None is "prior" with a row and "hamming" without; "prior" without a
+    row and anything unknown raise ValueError."""
+    if cost not in (None,) + tuple(_lib.RELAY_COST):
+        raise ValueError(f"relay_cost must be one of {tuple(_lib.RELAY_COST)} or None, got {cost!r}")
+    if cost == "prior" and not vector:
+        raise ValueError('relay_cost="prior" weighs solutions by a prior row: this half decodes with one scalar prior '
+                         "(relay_priors and unequal priors give it a row)")
+    return cost if cost is not None else ("prior" if vector else "hamming")
+
+
+def _relay_config(leg_iters, gammas, sols, row, cost):
+    """decode_batch's relay= of a half: the scalar relay's exactly as ever
+    where `row` (the half's prior row) is None, else with the row and its cost."""
+    if row is None:
+        _relay_cost(cost, False)
+        return decoders.RelayConfig(leg_iters, gammas, int(sols))
+    return decoders.RelayConfig(leg_iters, gammas, int(sols), prior=row, cost=_relay_cost(cost, True))
+
+
 def _decode_half(half, syn, dec, mask=None):
     """Decode one half's syndromes. `mask`: the other half's estimate, for the
     second half of a correlated decode (prior_mask=, p_masked=)."""
@@ -573,7 +594,7 @@ def _plan(Hx, Hz, p, decType, decIterations, decSchedule, OSDorder, rngSeed, sam
         probs = channel_probs(p, channel_weights, n)
         w = _weights_3n(channel_weights, n)
         priors = [_half_prior(float(p) * (w[0] + w[1]), hard), _half_prior(float(p) * (w[2] + w[1]), hard)]
-        if decType == "RELAY" and (priors[0][1] or priors[1][1]):
+        if decType == "RELAY" and (priors[0][1] or priors[1][1]) and not relay.get("priors"):
             raise ValueError("decType RELAY takes one scalar prior per half: channel_weights must give every "
                              "qubit the same marginals")
     if decType == "RELAY":
@@ -588,6 +609,10 @@ def _plan(Hx, Hz, p, decType, decIterations, decSchedule, OSDorder, rngSeed, sam
         lo, hi = (float(x) for x in relay["gamma_range"])
         if not (np.isfinite([lo, hi, float(relay["gamma0"])]).all() and lo <= hi):
             raise ValueError("relay_gamma0 and relay_gamma_range (lo <= hi) must be finite")
+        _relay_cost(relay.get("cost"), bool(priors[0][1]))
+        _relay_cost(relay.get("cost"), bool(priors[1][1]))
+    elif relay.get("priors") or relay.get("cost") is not None:
+        raise ValueError("relay_priors and relay_cost go with decType RELAY")
     if rngSeed is not None:
         np.random.seed(rngSeed)                    # reference side effect (:187-188); it refuses a bad seed here
     if Hz.size and Hz.shape[1] != n:
@@ -599,11 +624,13 @@ def _plan(Hx, Hz, p, decType, decIterations, decSchedule, OSDorder, rngSeed, sam
     if decType == "RELAY":
         leg_iters = [int(decIterations)] + [int(relay["leg_iters"])] * (int(relay["legs"]) - 1)
         grng = np.random.default_rng(relay["seed"])   # one generator: the Hz-decoded half draws first
-        for kw in relays:
+        for i, kw in enumerate(relays):
             gammas = np.empty((len(leg_iters), n), np.float64)
             gammas[0] = relay["gamma0"]
             gammas[1:] = grng.uniform(lo, hi, (len(leg_iters) - 1, n))
-            kw["relay"] = decoders.RelayConfig(leg_iters, gammas, int(relay["sols"]))
+            kw["relay"] = _relay_config(leg_iters, gammas, relay["sols"], priors[i][1].get("prior"), relay.get("cost"))
+            if priors[i][1]:
+                priors[i] = (None, {})             # relay_priors: the row travels in the RelayConfig, not as prior=
     if correlated not in (None, "XZ", "ZX"):
         raise ValueError("correlated must be 'XZ', 'ZX' or None")
     masked = None
@@ -769,7 +796,7 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
                logical: bool = False, correlated: Optional[str] = None, correlated_q1: float = 0.49,
                relay_legs: int = 11, relay_leg_iters: int = 60, relay_sols: int = 1, relay_gamma0: float = 0.125,
                relay_gamma_range=(-0.24, 0.66), relay_seed: int = 0, channel_weights=None,
-               osd_method: str = "ref") -> dict:
+               osd_method: str = "ref", relay_priors: bool = False, relay_cost: Optional[str] = None) -> dict:
     """One depolarizing probability: sample, decode both halves, count.
 
     Returns the reference's dict (simulator.py:308-315). `samples`, if given,
@@ -825,12 +852,22 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
     point with that value and keeps the specialised kernels, any other runs
     decode_batch(prior=...) (decode_vprior_kernel). NG / BF
     take no prior: only the sampling changes. Not combinable with correlated=;
-    decType "RELAY" needs uniform marginals in both halves (ValueError).
+    decType "RELAY" needs uniform marginals in both halves (ValueError) unless
+    `relay_priors` is set.
+
+    `relay_priors`, `relay_cost` (extension; decType "RELAY"): with
+    relay_priors=True a half whose marginals differ decodes with
+    RelayConfig(prior=marginals) (relay_vprior_kernel); a half
+    with equal marginals takes the scalar relay exactly as without the flag.
+    relay_cost is "hamming", "prior" or None: None keeps the solution of least
+    prior weight in a half decoded with a row and of least Hamming weight in a
+    scalar half; an explicit "prior" on a scalar half raises ValueError.
     """
     plan = _plan(Hx, Hz, p, decType, decIterations, decSchedule, OSDorder, rngSeed, samples, sampler, logical,
                  correlated, correlated_q1,
                  dict(legs=relay_legs, leg_iters=relay_leg_iters, sols=relay_sols, gamma0=relay_gamma0,
-                      gamma_range=relay_gamma_range, seed=relay_seed), channel_weights, osd_method)
+                      gamma_range=relay_gamma_range, seed=relay_seed, priors=bool(relay_priors), cost=relay_cost),
+                 channel_weights, osd_method)
     osd = plan.dec.osd
     rank, my_shots, my_start, seed = _shard(shots, rngSeed)
     keys = COUNTER_KEYS + LOGICAL_KEYS if logical else COUNTER_KEYS
@@ -1359,7 +1396,9 @@ class _HostDem:
 def simulate_dem(dem, shots: int = 1000, decType: str = "MS", decIterations: int = 99, decSchedule: str = "F",
                  OSDorder: int = -1, rngSeed: Optional[int] = None, *, batch_size: Optional[int] = None,
                  sampler: Optional[str] = None, verbose: bool = True, osd_method: str = "ref",
-                 hbm_priors: bool = False) -> dict:
+                 hbm_priors: bool = False, relay_priors: bool = False, relay_cost: Optional[str] = None,
+                 relay_legs: int = 11, relay_leg_iters: int = 60, relay_sols: int = 1, relay_gamma0: float = 0.125,
+                 relay_gamma_range=(-0.24, 0.66), relay_seed: int = 0) -> dict:
     """Monte-Carlo decoding of a detector error model (extension; no reference
     counterpart): `dem` is a dem.Dem (dem.load_dem reads Stim's .dem text).
     Each shot fires every mechanism independently with its own probability,
@@ -1392,22 +1431,55 @@ def simulate_dem(dem, shots: int = 1000, decType: str = "MS", decIterations: int
     logical_error_rate = 1 - decSuccess / shots, its 95 % Wilson interval
     logical_error_rate_ci95, and detectors, errors, observables (M, N, K).
 
-    ValueError: decType RELAY / NG / BF or unknown, an unknown schedule or
-    sampler, negative shots, an osd_method that does not fit, hbm_priors not
-    a bool."""
+    decType "RELAY" with `relay_priors=True`: relay min-sum with the
+    mechanisms' probabilities as its prior row (relay_vprior_kernel, DESIGN.md
+    §3.18; the scalar relay when they are all equal). decIterations is the
+    first leg's count and relay_legs, relay_leg_iters, relay_sols,
+    relay_gamma0, relay_gamma_range, relay_seed and relay_cost are
+    simulate_p's (one table of memory strengths; the defaults still come from
+    the code-capacity trial). OSDorder >= 0, a decSchedule other than "F" and
+    hbm_priors raise ValueError with it; a model past the relay's limits (a
+    detector row of more than 32 entries, tables past 16 bits or the LDS)
+    raises NotImplementedError before any shot is drawn.
+
+    ValueError: decType RELAY without relay_priors, NG / BF or unknown, an
+    unknown schedule or sampler, negative shots, an osd_method that does not
+    fit, hbm_priors not a bool."""
     from .dem import Dem
     if not isinstance(dem, Dem):
         raise ValueError("dem must be a qldpcsim_amd.dem.Dem (dem.load_dem / dem.parse_dem make one)")
+    relay_on = decType == "RELAY" and bool(relay_priors)
+    if relay_on and _hbm_priors_checked(hbm_priors):
+        raise ValueError("decType RELAY has no HBM-resident variant (hbm_priors)")
+    if (relay_priors or relay_cost is not None) and decType != "RELAY":
+        raise ValueError("relay_priors and relay_cost go with decType RELAY")
     if _hbm_priors_checked(hbm_priors):
         with _lib.options(vprior_hbm=1):       # once around the run: an option change drops the cached launch plans
             return simulate_dem(dem, shots, decType, decIterations, decSchedule, OSDorder, rngSeed,
                                 batch_size=batch_size, sampler=sampler, verbose=verbose, osd_method=osd_method)
-    if decType in ("RELAY",) + tuple(_lib.HARD_ALGOS):
+    if decType in _lib.HARD_ALGOS or (decType == "RELAY" and not relay_on):
         raise ValueError(f"decType {decType} is not available on detector error models (MS or BP)")
-    if decType not in ("MS", "BP"):
+    if decType not in ("MS", "BP", "RELAY"):
         raise ValueError("Unrecognized decoder type.")
     if decSchedule not in ("F", "L", "S"):
         raise ValueError("Unrecognized decoder scheduling option.")
+    relay_kw = {}
+    if relay_on:
+        if OSDorder >= 0:
+            raise ValueError("decType RELAY has no OSD step (OSDorder must be < 0)")
+        if decSchedule != "F":
+            raise ValueError("decType RELAY runs the flooding schedule only (decSchedule 'F')")
+        if int(relay_legs) < 1 or int(relay_leg_iters) < 1 or int(relay_sols) < 1 or int(decIterations) < 1:
+            raise ValueError("relay_legs, relay_leg_iters, relay_sols and decIterations must be >= 1")
+        lo, hi = (float(x) for x in relay_gamma_range)
+        if not (np.isfinite([lo, hi, float(relay_gamma0)]).all() and lo <= hi):
+            raise ValueError("relay_gamma0 and relay_gamma_range (lo <= hi) must be finite")
+        p_half, kw_half = _half_prior(dem.priors, False)
+        leg_iters = [int(decIterations)] + [int(relay_leg_iters)] * (int(relay_legs) - 1)
+        gammas = np.empty((len(leg_iters), dem.num_errors), np.float64)
+        gammas[0] = relay_gamma0
+        gammas[1:] = np.random.default_rng(relay_seed).uniform(lo, hi, (len(leg_iters) - 1, dem.num_errors))
+        relay_kw = {"relay": _relay_config(leg_iters, gammas, relay_sols, kw_half.get("prior"), relay_cost)}
     decoders.osd_method_checked(osd_method, OSDorder, decType)
     if sampler not in (None, "device", "host"):
         raise ValueError("sampler must be 'device', 'host' or None")
@@ -1420,7 +1492,10 @@ def simulate_dem(dem, shots: int = 1000, decType: str = "MS", decIterations: int
         batch_size = ((1 << 18) if osd < 0 else (1 << 14)) if use_dev else (1 << 14)
     dec = _Decode(decType, decIterations, osd, *_path_kw(use_dev, osd, osd_method), osd_method=osd_method)
     layers = None if decSchedule == "F" else layerize(dem.H, serial=decSchedule == "S")
-    half = _Half(dem.H, *pack_layers(layers, dem.num_detectors), *_half_prior(dem.priors, False))
+    if relay_on:                                   # the row, if any, travels in the RelayConfig
+        half = _Half(dem.H, *pack_layers(layers, dem.num_detectors), p_half, relay_kw)
+    else:
+        half = _Half(dem.H, *pack_layers(layers, dem.num_detectors), *_half_prior(dem.priors, False))
     show = _progress(f"(DEM {dem.num_detectors} x {dem.num_errors})", my_shots, verbose and rank == 0)
     if use_dev:
         import torch
@@ -1433,9 +1508,9 @@ def simulate_dem(dem, shots: int = 1000, decType: str = "MS", decIterations: int
         acc = np.zeros(4, np.int64)
         zero = np.zeros((1, dem.num_detectors), np.uint8)
     if half.kw:
-        # the vector-prior kernel's limits are met when its launch is planned: one
-        # all-zero detector row, so a model past them is refused
-        # (NotImplementedError) before any shot is drawn
+        # the vector-prior kernel's and the relay's limits are met when the
+        # launch is planned: one all-zero detector row, so a model past them is
+        # refused (NotImplementedError) before any shot is drawn
         _decode_half(half, zero, dec._replace(iters=1, kw={}))
     done = 0
     while done < my_shots:
@@ -1472,10 +1547,12 @@ def format_dem_results(name, r, shots):
 
 
 def _run_dem(path, shots, decType, decIterations, decSchedule, OSDorder, rngSeed, batch_size, sampler, resultsFile,
-             osd_method, hbm_priors=False):
+             osd_method, hbm_priors=False, relay=None):
     """The command line's --dem mode: load the model, simulate_dem, print the
     table; rank 0 writes the record (with the run's parameters; "hbm_priors"
-    only when set) to --results."""
+    only when set; `relay`, simulate_dem's relay_* keywords under
+    --relay-priors, only when given) to --results."""
+    relay = dict(relay or {})
     from .dem import load_dem
     _, rank, world = _dist()
     dem = load_dem(path)
@@ -1483,14 +1560,16 @@ def _run_dem(path, shots, decType, decIterations, decSchedule, OSDorder, rngSeed
         sampler = "device" if _device_ok() else "host"
     res = simulate_dem(dem, shots=shots, decType=decType, decIterations=decIterations, decSchedule=decSchedule,
                        OSDorder=OSDorder, rngSeed=rngSeed, batch_size=batch_size, sampler=sampler, verbose=True,
-                       osd_method=osd_method, **({"hbm_priors": True} if _hbm_priors_checked(hbm_priors) else {}))
+                       osd_method=osd_method, **({"hbm_priors": True} if _hbm_priors_checked(hbm_priors) else {}),
+                       **relay)
     if rank == 0:
         print(format_dem_results(path, res, shots))
         if resultsFile:
             meta = {"dem": path, "shots": shots, "decType": decType, "decIterations": decIterations,
                     "decSchedule": decSchedule, "OSDorder": OSDorder, "rngSeed": rngSeed, "world": world,
                     "sampler": sampler, **decoders._method_kw("osd_method", osd_method),
-                    **({"hbm_priors": True} if hbm_priors else {})}
+                    **({"hbm_priors": True} if hbm_priors else {}),
+                    **{k: (list(v) if k == "relay_gamma_range" else v) for k, v in relay.items()}}
             import json
             import os
             with open(resultsFile + ".tmp", "w") as f:
@@ -1578,7 +1657,7 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
              relay_gamma_range=(-0.24, 0.66), relay_seed: int = 0, bias: Optional[float] = None,
              channel_weights=None, rounds: Optional[int] = None, meas_error: Optional[float] = None,
              window: Optional[int] = None, commit: Optional[int] = None, osd_method: str = "ref",
-             hbm_priors: bool = False):
+             hbm_priors: bool = False, relay_priors: bool = False, relay_cost: Optional[str] = None):
     """p-sweep + results table (simulator.py:319-347). Returns None like the
     reference unless return_results=True.
 
@@ -1592,7 +1671,10 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
     is never resumed across modes.
 
     relay_* (extension; decType "RELAY"): simulate_p's relay min-sum settings;
-    all of them enter the results file's meta.
+    all of them enter the results file's meta. relay_priors, relay_cost:
+    simulate_p's, passed on and recorded ("relay_priors": true, "relay_cost")
+    only when relay_priors is set; relay_cost without it, or either of them
+    with rounds, raises ValueError.
 
     bias, channel_weights (extension; one of them at most): simulate_p's
     channel_weights for every point, given as a bias eta (bias_weights) or as
@@ -1636,6 +1718,11 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
         raise ValueError("window / commit need rounds (the phenomenological model)")
     if _hbm_priors_checked(hbm_priors) and rounds is None:
         raise ValueError("hbm_priors needs rounds (the phenomenological model) or a detector error model")
+    if relay_cost is not None and not relay_priors:
+        raise ValueError("relay_cost needs relay_priors")
+    if relay_priors and (decType != "RELAY" or rounds is not None):
+        raise ValueError("relay_priors goes with decType RELAY, without rounds (a phenomenological model decodes "
+                         "as a detector error model: simulate_dem)")
     if rounds is not None:
         if logical or correlated is not None or bias is not None or channel_weights is not None:
             raise ValueError("rounds= (phenomenological noise) cannot be combined with logical, correlated, bias or "
@@ -1678,6 +1765,8 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
         extra.update(relay_legs=int(relay_legs), relay_leg_iters=int(relay_leg_iters), relay_sols=int(relay_sols),
                      relay_gamma0=float(relay_gamma0), relay_gamma_range=[float(x) for x in relay_gamma_range],
                      relay_seed=int(relay_seed))
+        if relay_priors:
+            extra.update(relay_priors=True, relay_cost=relay_cost)
         meta.update({k: v for k, v in extra.items() if k.startswith("relay_")})
     if bias is not None and channel_weights is not None:
         raise ValueError("give either bias or channel_weights, not both")
@@ -1759,6 +1848,14 @@ def main(argv=None):
                         dest="relay_gamma_range", help="RELAY: later legs draw their memory strengths from U(LO, HI).")
     parser.add_argument("--relay-seed", type=int, default=0, dest="relay_seed",
                         help="RELAY: seed of the memory-strength tables.")
+    # (argparse.SUPPRESS: without the flags the printed namespace is what it was)
+    parser.add_argument("--relay-priors", action="store_true", default=argparse.SUPPRESS, dest="relay_priors",
+                        help="RELAY: decode unequal priors (--channel-weights marginals, a --dem model's mechanism "
+                             "probabilities) with the per-variable-prior relay kernel instead of refusing them.")
+    parser.add_argument("--relay-cost", choices=["hamming", "prior"], default=argparse.SUPPRESS, dest="relay_cost",
+                        help="With --relay-priors: which of the solutions found is kept, the one of least Hamming "
+                             "weight or of least prior weight (default: prior where a prior row decodes, else "
+                             "hamming).")
     parser.add_argument("--decIterations", type=int, default=99, help="Number of decoding iterations.")
     parser.add_argument("--decSchedule", choices=["F", "L", "S"], default="F",
                         help="Decoder scheduling method: [F] flooding; [L] layered; [S] serial.")
@@ -1810,6 +1907,12 @@ def main(argv=None):
                              "size, min-sum rows of more than 32 entries, state past the LDS) with the HBM-resident "
                              "per-variable-prior kernel instead of refusing them.")
     args = parser.parse_args(argv)
+    relay_priors = getattr(args, "relay_priors", False)
+    if hasattr(args, "relay_cost") and not relay_priors:
+        parser.error("--relay-cost needs --relay-priors")
+    if relay_priors and args.decType != "RELAY":
+        parser.error("--relay-priors needs --decType RELAY")
+    relay_names = ("relay_legs", "relay_leg_iters", "relay_sols", "relay_gamma0", "relay_gamma_range", "relay_seed")
     dem_file = getattr(args, "dem", None)
     if dem_file is not None:
         given = [f for f, v in (("--Hx", args.Hx), ("--Hz", args.Hz), ("--p", args.p),
@@ -1819,8 +1922,10 @@ def main(argv=None):
                                 ("--channel-weights", args.channel_weights)) if v is not None]
         if given:
             parser.error(f"--dem cannot be combined with {', '.join(given)}")
-        if args.decType not in ("MS", "BP"):
+        if args.decType not in ("MS", "BP") and not (args.decType == "RELAY" and relay_priors):
             parser.error("--dem decodes with MS or BP")
+        if relay_priors and getattr(args, "hbm_priors", False):
+            parser.error("--relay-priors cannot be combined with --hbm-priors")
         if args.osd_method == "cs" and not 0 <= args.OSDorder <= decoders.OSD_CS_MAX_LAMBDA:
             parser.error(f"--osd-method cs takes its lambda from --OSDorder: 0..{decoders.OSD_CS_MAX_LAMBDA}")
         own_group = _init_dist_from_env()
@@ -1832,7 +1937,9 @@ def main(argv=None):
         try:
             _run_dem(dem_file, args.shots, args.decType, args.decIterations, args.decSchedule, args.OSDorder,
                      args.rngSeed, args.batch, args.sampler, args.results, args.osd_method,
-                     hbm_priors=getattr(args, "hbm_priors", False))
+                     hbm_priors=getattr(args, "hbm_priors", False),
+                     relay=({**{k: getattr(args, k) for k in relay_names}, "relay_priors": True,
+                             "relay_cost": getattr(args, "relay_cost", None)} if relay_priors else None))
         finally:
             if own_group:
                 import torch.distributed as dist
@@ -1861,6 +1968,8 @@ def main(argv=None):
             parser.error("--rounds cannot be combined with --logical, --correlated, --bias or --channel-weights")
         if args.decType not in ("MS", "BP"):
             parser.error("--rounds decodes with MS or BP")
+        if relay_priors:
+            parser.error("--relay-priors cannot be combined with --rounds (decode the model as a --dem)")
     own_group = _init_dist_from_env()              # torchrun: shots shard over the ranks
     _, rank, _ = _dist()
     if rank == 0:
@@ -1879,9 +1988,8 @@ def main(argv=None):
                  **({"window": window, "commit": commit} if window is not None else {}),
                  **({"hbm_priors": True} if getattr(args, "hbm_priors", False) else {}),
                  **({"osd_method": args.osd_method} if args.osd_method != "ref" else {}),
-                 **({k: getattr(args, k) for k in ("relay_legs", "relay_leg_iters", "relay_sols", "relay_gamma0",
-                                                   "relay_gamma_range", "relay_seed")}
-                    if args.decType == "RELAY" else {}))
+                 **({k: getattr(args, k) for k in relay_names} if args.decType == "RELAY" else {}),
+                 **({"relay_priors": True, "relay_cost": getattr(args, "relay_cost", None)} if relay_priors else {}))
     finally:
         if own_group:
             import torch.distributed as dist
