@@ -17,7 +17,9 @@ using qldpc::DecodeArgs;
 // launch plan, device-free half: which kernel, and its static arguments
 // ---------------------------------------------------------------------------
 // per-wave state slice: post f64[n] | c2v (f32|f64)[E] | syn words | parity words
-// (ms_layered_kernel, colsum_f32: the "parity words" slot holds the syndrome
+// (flooding: no parity words, and syndrome words only past the register of the
+// generic kernels, QLDPC_SYNREG_CHECKS;
+// ms_layered_kernel, colsum_f32: the "parity words" slot holds the syndrome
 // bits in layer order instead, 2 ceil(synl_rows / 64) words; the lane-group
 // instance <DC, 0> only; decode_prior_kernel: selector words behind them)
 static void wave_layout(const qldpc_code* c, bool layered, int algo, bool colsum_f32, int synl_rows, bool prior,
@@ -27,7 +29,9 @@ static void wave_layout(const qldpc_code* c, bool layered, int algo, bool colsum
   off = align16(off + (algo == QLDPC_ALGO_MS ? 4 : 8) * (c->E + 8));  // +8: VN over-read pad
   const int words = 2 * ((c->m + 63) / 64);
   a->off_synw = off;
-  if (layered) off = align16(off + 4 * words);
+  // (flooding: the generic kernels hold the bits in a register up to
+  // QLDPC_SYNREG_CHECKS checks, so no existing slice grows; the *_tall ones read these)
+  if (layered || c->m > QLDPC_SYNREG_CHECKS) off = align16(off + 4 * words);
   a->off_parw = off;
   if (layered && !colsum_f32) off = align16(off + 4 * words);
   if (layered && colsum_f32) off = align16(off + 4 * 2 * ((synl_rows + 63) / 64));
@@ -78,6 +82,10 @@ int capi::qc_table_of(const qldpc_code* c) {
 #undef QLDPC_QC_MATCH
   return -1;
 }
+
+// flooding past the syndrome register of the generic LDS kernels: the *_tall
+// instances (such a code has no fast table: 8 E < 65536 caps it at 1170 checks)
+static bool flooding_tall(const qldpc_schedule* s) { return !s->layered && s->code->m > QLDPC_SYNREG_CHECKS; }
 
 KernelChoice capi::choose_kernel(const qldpc_schedule* s, int algo) {
   const qldpc_code* c = s->code;
@@ -143,7 +151,7 @@ KernelChoice capi::choose_kernel(const qldpc_schedule* s, int algo) {
     }
     if (!k.kernel) k.team = 0;
   }
-  if (!k.kernel) k.kernel = qldpc::select_kernel(algo, s->layered, dc, &k.name);
+  if (!k.kernel) k.kernel = qldpc::select_kernel(algo, s->layered, dc, flooding_tall(s), &k.name);
   return k;
 }
 
@@ -196,7 +204,7 @@ int capi::choose_twin_kernel(const qldpc_schedule* s, int algo, PlanKind kind, K
   }
   if (int rc = twin_limits(s, algo, twin_name(kind))) return rc;
   const auto select = kind == PLAN_PRIOR ? qldpc::select_prior_kernel : qldpc::select_vprior_kernel;
-  k->kernel = select(algo, s->layered, fast_table_ok(c) ? c->uniform_deg : 0, &k->name);
+  k->kernel = select(algo, s->layered, fast_table_ok(c) ? c->uniform_deg : 0, flooding_tall(s), &k->name);
   return QLDPC_OK;
 }
 

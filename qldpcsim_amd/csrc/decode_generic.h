@@ -379,31 +379,64 @@ __device__ __forceinline__ double vn_post(const DecodeArgs& a, const LdsView& g,
 template <int ALGO, bool LAYERED, int DC>
 __global__ void __launch_bounds__(QLDPC_MAX_THREADS) decode_kernel(DecodeArgs a) {
   constexpr int PRI = PRI_SCALAR;
+  constexpr bool TALL = false;
 #include "decode_kernel_body.inc"
 }
 
 template <int ALGO, bool LAYERED, int DC>
 __global__ void __launch_bounds__(QLDPC_MAX_THREADS) decode_prior_kernel(DecodeArgs a) {
   constexpr int PRI = PRI_MASK;
+  constexpr bool TALL = false;
 #include "decode_kernel_body.inc"
 }
 
 template <int ALGO, bool LAYERED, int DC>
 __global__ void __launch_bounds__(QLDPC_MAX_THREADS) decode_vprior_kernel(DecodeArgs a) {
   constexpr int PRI = PRI_ROW;
+  constexpr bool TALL = false;
+#include "decode_kernel_body.inc"
+}
+
+// Flooding with more than QLDPC_SYNREG_CHECKS checks (DC = 0: the fast table's
+// 8 E < 65536 leaves row degree 7 / 8 at most 1170 checks): the same body with
+// the syndrome bits in the slice's words instead of a register. Kernels of
+// their own, so that the instances above stay instruction for instruction what
+// they were.
+template <int ALGO>
+__global__ void __launch_bounds__(QLDPC_MAX_THREADS) decode_kernel_tall(DecodeArgs a) {
+  constexpr int PRI = PRI_SCALAR, DC = 0;
+  constexpr bool LAYERED = false, TALL = true;
+#include "decode_kernel_body.inc"
+}
+
+template <int ALGO>
+__global__ void __launch_bounds__(QLDPC_MAX_THREADS) decode_prior_kernel_tall(DecodeArgs a) {
+  constexpr int PRI = PRI_MASK, DC = 0;
+  constexpr bool LAYERED = false, TALL = true;
+#include "decode_kernel_body.inc"
+}
+
+template <int ALGO>
+__global__ void __launch_bounds__(QLDPC_MAX_THREADS) decode_vprior_kernel_tall(DecodeArgs a) {
+  constexpr int PRI = PRI_ROW, DC = 0;
+  constexpr bool LAYERED = false, TALL = true;
 #include "decode_kernel_body.inc"
 }
 
 // The selector of one of the three kernels above, defined once per kernel in
-// the translation unit that instantiates it: FN(algo, layered, dc, &name)
-// answers KERNEL<algo, layered, 7 | 8 | 0> and its name, the template
-// arguments spelled as rocprofv3 prints them.
+// the translation unit that instantiates it: FN(algo, layered, dc, tall, &name)
+// answers KERNEL<algo, layered, 7 | 8 | 0> (tall: KERNEL_tall<algo>, flooding
+// and the generic table by necessity) and its name, the template arguments
+// spelled as rocprofv3 prints them.
 static_assert(ALGO_MS == 0 && ALGO_BP == 1, "the selector spells the algorithm as 0 / 1");
 #define QLDPC_GENERIC_CASE(KERNEL, A, LAY, D) \
   if (al == A && layered == LAY && d == D) QLDPC_NAMED((&KERNEL<A, LAY, D>), #KERNEL "<" #A ", " #LAY ", " #D ">");
 #define QLDPC_GENERIC_SELECTOR(FN, KERNEL)                                                      \
-  const void* FN(int algo, bool layered, int dc, const char** name) {                           \
+  const void* FN(int algo, bool layered, int dc, bool tall, const char** name) {                \
     const int al = algo == ALGO_MS ? 0 : 1, d = dc == 7 || dc == 8 ? dc : 0;                    \
+    if (tall && (layered || d != 0)) return nullptr;                                            \
+    if (tall && al == 0) QLDPC_NAMED((&KERNEL##_tall<0>), #KERNEL "_tall<0>");                  \
+    if (tall) QLDPC_NAMED((&KERNEL##_tall<1>), #KERNEL "_tall<1>");                             \
     QLDPC_GENERIC_CASE(KERNEL, 0, true, 7) QLDPC_GENERIC_CASE(KERNEL, 0, false, 7)              \
     QLDPC_GENERIC_CASE(KERNEL, 0, true, 8) QLDPC_GENERIC_CASE(KERNEL, 0, false, 8)              \
     QLDPC_GENERIC_CASE(KERNEL, 0, true, 0) QLDPC_GENERIC_CASE(KERNEL, 0, false, 0)              \

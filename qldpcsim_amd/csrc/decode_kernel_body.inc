@@ -1,7 +1,8 @@
 // decode_kernel_body.inc — the body of decode_kernel / decode_prior_kernel /
 // decode_vprior_kernel (decode_generic.h), included inside each kernel with
-// `a` (DecodeArgs), the template parameters ALGO, LAYERED, DC and a constexpr
-// int PRI (PRI_SCALAR / PRI_MASK / PRI_ROW) in scope.
+// `a` (DecodeArgs), ALGO, LAYERED, DC, a constexpr int PRI (PRI_SCALAR /
+// PRI_MASK / PRI_ROW) and a constexpr bool TALL (flooding past
+// QLDPC_SYNREG_CHECKS checks: the *_tall kernels, DC = 0) in scope.
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
   // Stage the read-only graph blob into LDS (16-byte vector copies).
@@ -72,8 +73,20 @@
 
     if constexpr (!LAYERED) {
       // ---------------- flooding: one layer holding every check ------------
+      // Syndrome bits: a lane's checks are lane + 64 i, and one 32-bit register
+      // holds bit i of up to 32 passes, QLDPC_SYNREG_CHECKS = 2048 checks. A
+      // taller code runs the TALL instance, which keeps them in the slice's
+      // synw words (wave_layout allocates those for flooding in that case
+      // alone); every other instance is the code it was.
       uint32_t synreg = 0;  // bit i = syndrome of check lane + 64 i
-      for (int i = 0, c = lane; c < m; ++i, c += 64) synreg |= syn_bit(a, hs, c) << i;
+      if constexpr (!TALL) {
+        for (int i = 0, c = lane; c < m; ++i, c += 64) synreg |= syn_bit(a, hs, c) << i;
+      } else {
+        for (int c0 = 0; c0 < m; c0 += 64)
+          store_bits64(synw, c0, c0 + lane < m ? (int)syn_bit(a, hs, c0 + lane) : 0, lane);
+        wave_sync();
+      }
+#define QLDPC_SYNB(i, c) (TALL ? (synw[(c) >> 5] >> ((c) & 31)) & 1u : (synreg >> (i)) & 1u)
       if constexpr (ALGO == ALGO_BP) {
         // BP's first check-node pass reads v2c = L0 (decoders.py:235):
         // post = L0, c2v = 0. (MS's first pass reads float32(L) directly.)
@@ -92,7 +105,7 @@
           for (int i = 0, c = lane; c < m; ++i, c += 64) {
             uint32_t t[1][8];
             load_row8(g.cn_tab + c * 8, t[0]);
-            const uint32_t sb[1] = {(synreg >> i) & 1u};
+            const uint32_t sb[1] = {QLDPC_SYNB(i, c)};
             const bool live[1] = {true};
             if (PRI && it == 0)
               (void)cn_update<ALGO, DC, PRI>(a, g, c, sb[0], true, post, c2v, fl, selw);
@@ -103,10 +116,10 @@
           }
         } else if (it == 0) {
           for (int i = 0, c = lane; c < m; ++i, c += 64)
-            (void)cn_update<ALGO, DC, PRI>(a, g, c, (synreg >> i) & 1u, true, post, c2v, fl, selw);
+            (void)cn_update<ALGO, DC, PRI>(a, g, c, QLDPC_SYNB(i, c), true, post, c2v, fl, selw);
         } else {
           for (int i = 0, c = lane; c < m; ++i, c += 64)
-            unsat |= cn_update<ALGO, DC, PRI>(a, g, c, (synreg >> i) & 1u, false, post, c2v, fl, selw);
+            unsat |= cn_update<ALGO, DC, PRI>(a, g, c, QLDPC_SYNB(i, c), false, post, c2v, fl, selw);
         }
         if (it > 0 && ballot(unsat != 0) == 0) {
           iters = it;
@@ -131,12 +144,13 @@
             const int deg = DC ? DC : (int)g.row_ptr[c + 1] - e0;
             uint32_t par = 0;
             for (int k = 0; k < deg; ++k) par ^= (uint32_t)(post[tab_var<DC>(g.cn_tab[e0 + k])] < 0.0);
-            un |= par ^ ((synreg >> i) & 1u);
+            un |= par ^ QLDPC_SYNB(i, c);
           }
           conv = ballot(un != 0) == 0;
           break;
         }
       }
+#undef QLDPC_SYNB
     } else {
       // ---------------- layered / serial: explicit row lists ----------------
       // State starts at c2v = 0, post = L (msg_v2c = L, :148-149 / :235).

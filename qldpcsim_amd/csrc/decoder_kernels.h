@@ -7,6 +7,12 @@
 #define QLDPC_MAX_THREADS 768
 // max runs of equal column degree the flooding MS kernel handles
 #define QLDPC_MAX_RUNS 8
+// checks whose syndrome bits the generic LDS kernels' flooding branch keeps in
+// one 32-bit register per lane (decode_kernel_body.inc): bit i of lane l is
+// check l + 64 i, so 32 bits x 64 lanes. A taller code runs the *_tall kernels
+// (decode_generic.h), with syndrome words in its wave slices instead
+// (wave_layout, capi_decode.cpp).
+#define QLDPC_SYNREG_CHECKS 2048
 #define QLDPC_FLOOD_HDR 128  // LDS bytes of ms_flood_kernel's runs header (4 * 8 ints)
 
 namespace qldpc {
@@ -68,12 +74,13 @@ struct DecodeArgs {
   int vprior_bytes;           // LDS bytes of that copy (8 n rounded up to 16)
 };
 
-// `name` (nullable) receives the kernel's name as rocprofv3 reports it
-const void* select_kernel(int algo, bool layered, int dc, const char** name);
+// `name` (nullable) receives the kernel's name as rocprofv3 reports it. `tall`:
+// flooding with more than QLDPC_SYNREG_CHECKS checks, the *_tall instances
+const void* select_kernel(int algo, bool layered, int dc, bool tall, const char** name);
 // its two-level-prior twin decode_prior_kernel (same template arguments)
-const void* select_prior_kernel(int algo, bool layered, int dc, const char** name);
+const void* select_prior_kernel(int algo, bool layered, int dc, bool tall, const char** name);
 // its per-variable-prior twin decode_vprior_kernel (same template arguments)
-const void* select_vprior_kernel(int algo, bool layered, int dc, const char** name);
+const void* select_vprior_kernel(int algo, bool layered, int dc, bool tall, const char** name);
 // flooding MS, uniform row degree: global tables (fblob), LDS = wave state only
 const void* select_ms_flood_kernel(int dc, int kc, const char** name);  // nullptr if no instantiation fits
 int ms_flood_max_waves(int kc);                      // waves per workgroup it was compiled for

@@ -147,9 +147,15 @@ def decode(algo, H, syn, L, max_iter, layers=None, beta=0.75, eps=1e-9):
         Lj = L[np.ix_(idx, js)]
         post[np.ix_(idx, js)] = Lj + S.astype(np.float64) if ms else Lj + S
 
+    Rv = g.R >= 0
+    Rcols = g.ec[np.where(Rv, g.R, 0)]                  # [m, d] variable of each check's edges
+
     def satisfied(idx):
-        e = (post[idx] < 0).astype(np.int64)
-        return np.all((e @ g.H.T) % 2 == syn[idx], axis=1)
+        # H e == s (mod 2) edge by edge (a dense product per layer is what a
+        # schedule of many layers on a matrix of thousands of rows spends its time in)
+        e = post[idx] < 0
+        par = (e[:, Rcols] & Rv).sum(2) & 1
+        return np.all(par == syn[idx], axis=1)
 
     first = True
     for it in range(max_iter):
