@@ -153,6 +153,28 @@ struct RowQueue {
 #define QLDPC_QC_CN32 0
 #endif
 
+// Where a check block keeps its single bits (-DQLDPC_QC_S31=n for A/B;
+// DESIGN.md §3.1.1 for the measured choice):
+//   0  at bit 0: the syndrome bit as (synreg >> B) & 1, the sign product and
+//      the hard-decision parity shifted down to it, npm shifted back up
+//   1  at bit 31, where the float64 high words carry them: the caller passes
+//      s31 = synreg << (31 - B) (bit 31 the check's syndrome bit, the bits
+//      below it other checks' and not used), npm = (sh ^ s31) & 0x80000000 and
+//      the running unsat word takes ph ^ s31; its bit 31 is the stop test's
+#ifndef QLDPC_QC_S31
+#define QLDPC_QC_S31 1
+#endif
+// What the wave-uniform rare branch of qc_min_select_f64 redefines
+// (-DQLDPC_QC_RARE32=n for A/B):
+//   0  the float64 minima m1, m2 that fl32(beta * m) is then formed from, so
+//      the fast path copies min1 and min2 into the joined registers
+//   1  the two float32 words themselves: they are formed from min1 and min2
+//      ahead of the branch and the rare branch forms them again from the
+//      substituted minima; no float64 value of the branch is read after it
+#ifndef QLDPC_QC_RARE32
+#define QLDPC_QC_RARE32 1
+#endif
+
 // The float64 minimum and select of one check (decoders.py:160-169), with the
 // reference's substitutions for infinite and zero minima and FLAG_MIN_ZERO
 template <int DC>
@@ -160,6 +182,21 @@ __device__ __forceinline__ void qc_min_select_f64(const DecodeArgs& a, const dou
                                                   uint32_t npm, float (&cv)[DC], int& fl) {
   double min1, min2;                                      // first min / min of the rest (:160-164)
   min12_tree<DC>(v, min1, min2);
+#if QLDPC_QC_RARE32
+  // (opaque: otherwise the two roundings are sunk below the branch again and
+  // joined on their float64 operands)
+  uint32_t c1 = opaque_always(__builtin_bit_cast(uint32_t, (float)(a.beta * min1)));
+  uint32_t c2 = opaque_always(__builtin_bit_cast(uint32_t, (float)(a.beta * min2)));
+  if (__builtin_expect(ballot((min1 == 0.0) | (min2 == __builtin_inf())) != 0, 0)) {
+    const double m1 = __builtin_isinf(min1) ? 0.0 : min1;  // (:165)
+    const double m2 = __builtin_isinf(min2) ? 0.0 : min2;  // (:166)
+    c1 = __builtin_bit_cast(uint32_t, (float)(a.beta * m1));
+    c2 = __builtin_bit_cast(uint32_t, (float)(a.beta * m2));
+    if (m1 == 0.0) fl |= FLAG_MIN_ZERO;
+  }
+  const uint32_t c1n = opaque_always(c1 ^ npm);
+  const uint32_t c2n = opaque_always(c2 ^ npm);
+#else
   double m1 = min1, m2 = min2;
   if (__builtin_expect(ballot((min1 == 0.0) | (min2 == __builtin_inf())) != 0, 0)) {
     m1 = __builtin_isinf(min1) ? 0.0 : min1;              // (:165)
@@ -168,6 +205,7 @@ __device__ __forceinline__ void qc_min_select_f64(const DecodeArgs& a, const dou
   }
   const uint32_t c1n = opaque_always(__builtin_bit_cast(uint32_t, (float)(a.beta * m1)) ^ npm);
   const uint32_t c2n = opaque_always(__builtin_bit_cast(uint32_t, (float)(a.beta * m2)) ^ npm);
+#endif
   static_for<DC>([&](auto E) __attribute__((always_inline)) {
     constexpr int e = E;
     const uint32_t c = (__builtin_fabs(v[e]) == min1) ? c2n : c1n;
@@ -187,10 +225,12 @@ __device__ __forceinline__ double qc_edge_post(double L, const float (&S)[T::NB]
 // Min-sum update of check block B (decoders.py:155-169 for the lane's check):
 // cn_ms_compute with the posteriors rotated in from P (or formed from the
 // rotated S) and the messages in registers. Returns the check's "unsatisfied"
-// bit for the posteriors it read.
+// bit for the posteriors it read, or (QLDPC_QC_S31) ORs a word with that bit
+// at bit 31 into unsat_acc; synb is then s31.
 template <typename T, int B>
 __device__ __forceinline__ uint32_t qc_check(const DecodeArgs& a, double L, float (&S)[T::NB], double (&P)[T::NB],
-                                             float (&c2v)[T::MB][T::DC], uint32_t synb, int& fl) {
+                                             float (&c2v)[T::MB][T::DC], uint32_t synb, int& fl,
+                                             uint32_t& unsat_acc) {
   constexpr int DC = T::DC;
   // one check block's working set at a time: the inputs are pinned behind the
   // previous block's outputs (volatile asm statements keep their order), so no
@@ -215,7 +255,11 @@ __device__ __forceinline__ uint32_t qc_check(const DecodeArgs& a, double L, floa
   });
   const uint32_t ph = xor_tree<DC>(hp);                   // hard-decision parity (:174)
   const uint32_t sh = xor_tree<DC>(hv);                   // np.sign product (:157-159)
+#if QLDPC_QC_S31
+  const uint32_t npm = (sh ^ synb) & 0x80000000u;
+#else
   const uint32_t npm = ((sh >> 31) ^ synb) << 31;
+#endif
 #if QLDPC_QC_CN32
   uint32_t w[DC];
   static_for<DC>([&](auto E) __attribute__((always_inline)) {
@@ -239,6 +283,15 @@ __device__ __forceinline__ uint32_t qc_check(const DecodeArgs& a, double L, floa
 #else
   qc_min_select_f64<DC>(a, v, hv, npm, c2v[B], fl);
 #endif
+#if QLDPC_QC_S31
+  unsat_acc |= ph ^ synb;
+  static_for<DC>([&](auto E) __attribute__((always_inline)) {
+    float& cx = c2v[B][E];
+    asm volatile("" : "+v"(cx));
+  });
+  asm volatile("" : "+v"(unsat_acc));
+  return 0;
+#else
   uint32_t unsat = (ph >> 31) ^ synb;
   static_for<DC>([&](auto E) __attribute__((always_inline)) {
     float& cx = c2v[B][E];
@@ -246,6 +299,7 @@ __device__ __forceinline__ uint32_t qc_check(const DecodeArgs& a, double L, floa
   });
   asm volatile("" : "+v"(unsat));
   return unsat;
+#endif
 }
 
 // lane i of a DPP row takes x of lane (i - N) % 16 (row_ror:N)
@@ -260,15 +314,22 @@ __device__ __forceinline__ uint32_t row_ror_u32(uint32_t x) {
 
 // parity of check block B's hard decisions XOR its syndrome bit (the stop
 // test after the last iteration, decoders.py:174-176); hw: this lane's hard
-// decisions, bit c & 31 of word c >> 5 for variable block c
+// decisions, bit c & 31 of word c >> 5 for variable block c. With QLDPC_QC_S31
+// synb is s31 and the result's bit 31 is the parity (the bits below are not).
 template <typename T, int B>
 __device__ __forceinline__ uint32_t qc_parity(const uint32_t (&hw)[(T::NB + 31) / 32], uint32_t synb) {
   uint32_t ph = synb;
   static_for<T::DC>([&](auto E) __attribute__((always_inline)) {
     constexpr int e = E, c = T::cvar[B][e], s = T::cshift[B][e];
+#if QLDPC_QC_S31
+    ph ^= row_ror_u32<(16 - s) & 15>(hw[c >> 5]) << (31 - (c & 31));
+#else
     ph ^= row_ror_u32<(16 - s) & 15>(hw[c >> 5]) >> (c & 31);
+#endif
   });
+#if !QLDPC_QC_S31
   ph &= 1u;
+#endif
   asm volatile("" : "+v"(ph));                            // one check block at a time
   return ph;
 }
@@ -430,20 +491,35 @@ __device__ __forceinline__ void flood_qc_body(const DecodeArgs& a) {
           hw[C / 32] |= (hi_word(qc_post<T, C>(a.L, S, P)) >> 31) << (C % 32);
         });
         uint32_t un = 0;
+#if QLDPC_QC_S31
+        static_for<MB>([&](auto B) __attribute__((always_inline)) {
+          un |= qc_parity<T, B>(hw, synreg << (31 - B));
+        });
+        fin = true, iters = it;
+        conv = row_bits(ballot_b((int32_t)un < 0), rowsh) == 0;
+#else
         static_for<MB>([&](auto B) __attribute__((always_inline)) {
           un |= qc_parity<T, B>(hw, (synreg >> B) & 1u);
         });
         fin = true, iters = it;
         conv = row_bits(ballot_b(un != 0), rowsh) == 0;
+#endif
       }
     }
     if (live && !fin) {
       uint32_t unsat = 0;
-      static_for<MB>([&](auto B) __attribute__((always_inline)) {
-        unsat |= qc_check<T, B>(a, a.L, S, P, c2v, (synreg >> B) & 1u, fl);
-      });
       // stop test of iteration it - 1 (decoders.py:175-176)
+#if QLDPC_QC_S31
+      static_for<MB>([&](auto B) __attribute__((always_inline)) {
+        qc_check<T, B>(a, a.L, S, P, c2v, synreg << (31 - B), fl, unsat);
+      });
+      if (row_bits(ballot_b((int32_t)unsat < 0), rowsh) == 0) fin = true, conv = true, iters = it;
+#else
+      static_for<MB>([&](auto B) __attribute__((always_inline)) {
+        unsat |= qc_check<T, B>(a, a.L, S, P, c2v, (synreg >> B) & 1u, fl, unsat);
+      });
       if (row_bits(ballot_b(unsat != 0), rowsh) == 0) fin = true, conv = true, iters = it;
+#endif
     }
   }
 }

@@ -41,7 +41,9 @@
 enum Op {
   ADD_F64, MUL_F64, MIN_F64, MAX_F64, CMP_EQ_F64_CNDMASK, CVT_F64_F32, CVT_F32_F64, MUL_ABS_F64_CVT_F32,
   ADD_F32, MIN_F32, MAX_F32, MIN3_F32, MED3_F32, AND_B32, MIN_U32, MAX_U32, MIN3_U32, MED3_U32, BITOP3_B32, CNDMASK_VCC, MOV_B32, MOV_ROW_ROR, VALU_THEN_DPP,
-  VALU_NOP_PAIR, NUM_OPS
+  VALU_NOP_PAIR,
+  OR_B32_ROW_ROR, AND_B32_ROW_ROR, ADD_F32_ROW_ROR, MOV_B64, LSHLREV_B32, LSHRREV_B32, CNDMASK_ALONE, CMP_EQ_F64_VCC,
+  CMP_EQ_F64_SGPR, BFI_B32, XOR_B32, NUM_OPS
 };
 struct OpInfo { const char* name; int inst_per_step; };   // instructions per chain step
 static const OpInfo kOps[NUM_OPS] = {
@@ -54,6 +56,13 @@ static const OpInfo kOps[NUM_OPS] = {
     {"v_mov_b32 row_ror (source not written in the loop)", 1},
     {"v_add_u32 ; s_nop 1 ; v_mov_b32 row_ror of its result (pair)", 2},
     {"v_add_u32 ; s_nop 1 ; v_mov_b32 of another register (pair)", 2},
+    {"v_or_b32 row_ror (DPP source not written in the loop, other operand zero)", 1},
+    {"v_and_b32 row_ror (DPP source not written in the loop, other operand all ones)", 1},
+    {"v_add_f32 row_ror (DPP source not written in the loop, added to the chain)", 1},
+    {"v_mov_b64", 1}, {"v_lshlrev_b32 (by a constant)", 1}, {"v_lshrrev_b32 (by a constant)", 1},
+    {"v_cndmask_b32 alone (mask in an SGPR pair set before the loop)", 1},
+    {"v_cmp_eq_f64 alone, into vcc", 1}, {"v_cmp_eq_f64 alone, into an SGPR pair", 1},
+    {"v_bfi_b32", 1}, {"v_xor_b32", 1},
 };
 
 constexpr int kChains = 8, kUnroll = 32;  // 256 steps per loop trip
@@ -78,6 +87,10 @@ __global__ void __launch_bounds__(256) rate_kernel(uint64_t* cyc, uint32_t* done
   }
   double one = 1.0;
   asm volatile("" : "+v"(one));
+  uint32_t zero = 0, ones = 0xffffffffu;
+  asm volatile("" : "+v"(zero), "+v"(ones));
+  uint64_t sel = 0x5555aaaa3333ccccull, cm[kChains] = {};   // cndmask's mask; the compares' SGPR results
+  asm volatile("" : "+s"(sel));
   const uint64_t t0 = __builtin_readcyclecounter();
   // chunks of kChunk trips; fixed-work mode runs `trips` of them, window mode
   // goes on until the window has passed (the clock is read once per chunk)
@@ -131,6 +144,21 @@ __global__ void __launch_bounds__(256) rate_kernel(uint64_t* cyc, uint32_t* done
                        : "+v"(u[i]), "+v"(w[i]) : "v"(threadIdx.x));
         if constexpr (OP == VALU_NOP_PAIR)   // (the same three issue slots without DPP)
           asm volatile("v_add_u32 %0, %0, %2\n\ts_nop 1\n\tv_mov_b32 %1, %2" : "+v"(u[i]), "+v"(w[i]) : "v"(threadIdx.x));
+        if constexpr (OP == OR_B32_ROW_ROR)
+          asm volatile("v_or_b32_dpp %0, %1, %2 row_ror:3 row_mask:0xf bank_mask:0xf" : "+v"(u[i]) : "v"(w[i]), "v"(zero));
+        if constexpr (OP == AND_B32_ROW_ROR)
+          asm volatile("v_and_b32_dpp %0, %1, %2 row_ror:3 row_mask:0xf bank_mask:0xf" : "+v"(u[i]) : "v"(w[i]), "v"(ones));
+        if constexpr (OP == ADD_F32_ROW_ROR)
+          asm volatile("v_add_f32_dpp %0, %1, %0 row_ror:3 row_mask:0xf bank_mask:0xf" : "+v"(f[i]) : "v"(g[i]));
+        if constexpr (OP == MOV_B64) asm volatile("v_mov_b64 %0, %1" : "=v"(d[i]) : "v"(e[i]));
+        if constexpr (OP == LSHLREV_B32) asm volatile("v_lshlrev_b32 %0, 3, %1" : "=v"(u[i]) : "v"(w[i]));
+        if constexpr (OP == LSHRREV_B32) asm volatile("v_lshrrev_b32 %0, 31, %1" : "=v"(u[i]) : "v"(w[i]));
+        if constexpr (OP == CNDMASK_ALONE) asm volatile("v_cndmask_b32 %0, %0, %1, %2" : "+v"(u[i]) : "v"(w[i]), "s"(sel));
+        if constexpr (OP == CMP_EQ_F64_VCC) asm volatile("v_cmp_eq_f64 vcc, %0, %1" : : "v"(d[i]), "v"(e[i]) : "vcc");
+        if constexpr (OP == CMP_EQ_F64_SGPR) asm volatile("v_cmp_eq_f64 %0, %1, %2" : "=s"(cm[i]) : "v"(d[i]), "v"(e[i]));
+        if constexpr (OP == BFI_B32)
+          asm volatile("v_bfi_b32 %0, %1, %2, %0" : "+v"(u[i]) : "v"(w[i]), "v"(w[(i + 1) % kChains]));
+        if constexpr (OP == XOR_B32) asm volatile("v_xor_b32 %0, %0, %1" : "+v"(u[i]) : "v"(w[i]));
       }
     }
   }
@@ -141,7 +169,7 @@ __global__ void __launch_bounds__(256) rate_kernel(uint64_t* cyc, uint32_t* done
 #pragma unroll
   for (int i = 0; i < kChains; ++i) {
     acc ^= u[i] ^ w[i] ^ __float_as_uint(f[i]) ^ __float_as_uint(g[i]) ^ (uint32_t)__double_as_longlong(d[i]) ^
-           (uint32_t)__double_as_longlong(e[i]);
+           (uint32_t)__double_as_longlong(e[i]) ^ (uint32_t)cm[i];
   }
   const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);
   if ((threadIdx.x & 63) == 0) cyc[gw] = t1 - t0, done[gw] = (uint32_t)ran;
