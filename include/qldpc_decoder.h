@@ -522,8 +522,33 @@ int qldpc_osd_device_ordered_ex_cs(const qldpc_code *code, int64_t count, const 
                                    const double *d_post, int lambda, uint8_t *d_ehat, int32_t *d_status,
                                    int32_t *d_perm, int32_t *d_tiepos, double *d_spill_post,
                                    int32_t *d_spill_idx, int32_t *d_spill_count, int64_t spill_cap, void *stream);
-/* The name of the kernel qldpc_osd_device(_cs) launches for this code
- * ("osd_block_kernel<17, 8, 2>", "osd_block_cs_kernel<17, 8, 2>", ...), into buf. Measurement and tests. */
+/* OSD-CS with the prior-weighted cost: the same candidates in
+ * the same order, but the cost of an estimate e is sum_j e_j W_j with W_j =
+ * llrint(L_j 2^20), L_j the prior LLR of column j as `prior` holds it (exact
+ * int64; W_j < 0 where p_j > 1/2). The first candidate of strictly smallest
+ * cost wins, the base wins ties. `prior` must come from qldpc_prior_create for
+ * this very code: a null handle or another code's gives QLDPC_EINVAL. A
+ * uniform row with p < 1/2 gives the Hamming-cost result bit for bit. All else
+ * (lambda, limits, errors, status values, the order-0 cases) as the _cs entry
+ * point each one is named after; status-2 shots of the ordered forms are
+ * finished with qldpc_osd_device_cs_prior. */
+int qldpc_osd_decode_batch_cs_prior(const qldpc_code *code, int64_t count, const uint8_t *h_syn,
+                                    const int32_t *h_perm, int lambda, const qldpc_prior *prior, uint8_t *h_ehat,
+                                    int nthreads);
+int qldpc_osd_device_cs_prior(const qldpc_code *code, int64_t count, const uint8_t *d_syn, const int32_t *d_perm,
+                              int lambda, const qldpc_prior *prior, uint8_t *d_ehat, int32_t *d_status,
+                              void *stream);
+int qldpc_osd_device_ordered_cs_prior(const qldpc_code *code, int64_t count, const uint8_t *d_syn,
+                                      const double *d_post, int lambda, const qldpc_prior *prior, uint8_t *d_ehat,
+                                      int32_t *d_status, int32_t *d_perm, int32_t *d_tiepos, void *stream);
+int qldpc_osd_device_ordered_ex_cs_prior(const qldpc_code *code, int64_t count, const uint8_t *d_syn,
+                                         const double *d_post, int lambda, const qldpc_prior *prior,
+                                         uint8_t *d_ehat, int32_t *d_status, int32_t *d_perm, int32_t *d_tiepos,
+                                         double *d_spill_post, int32_t *d_spill_idx, int32_t *d_spill_count,
+                                         int64_t spill_cap, void *stream);
+/* The name of the kernel qldpc_osd_device(_cs, _cs_prior) launches for this code, into buf: cs = 0
+ * ("osd_block_kernel<17, 8, 2>", ...), 1 ("osd_block_cs_kernel<17, 8, 2>") or 2, the prior-weighted cost
+ * ("osd_block_cs_prior_kernel<17, 8, 2>"). Measurement and tests. */
 int qldpc_osd_kernel_name(const qldpc_code *code, int cs, char *buf, int len);
 
 /* First element of CPython's `set(range(n)) - set(J)` iteration order

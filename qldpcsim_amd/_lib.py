@@ -40,6 +40,8 @@ EXPORTS = (
     "qldpc_osd_device_ordered", "qldpc_osd_device_ordered_ex", "qldpc_cpython_setdiff_first",
     "qldpc_osd_decode_batch_cs", "qldpc_osd_device_cs", "qldpc_osd_device_ordered_cs",
     "qldpc_osd_device_ordered_ex_cs", "qldpc_osd_kernel_name",
+    "qldpc_osd_decode_batch_cs_prior", "qldpc_osd_device_cs_prior", "qldpc_osd_device_ordered_cs_prior",
+    "qldpc_osd_device_ordered_ex_cs_prior",
     "qldpc_osd_order_host", "qldpc_np_argsort_host", "qldpc_osd_keys_host", "qldpc_libm_eval_host",
     "qldpc_channel_thresholds", "qldpc_channel_sample", "qldpc_channel_sample_ex", "qldpc_count_outcomes",
     "qldpc_count_outcomes_ex",
@@ -124,6 +126,10 @@ def _load():
         "qldpc_osd_device_cs": ([P, I64, P, P, I, P, P, P], I),
         "qldpc_osd_device_ordered_cs": ([P, I64, P, P, I, P, P, P, P, P], I),
         "qldpc_osd_device_ordered_ex_cs": ([P, I64, P, P, I, P, P, P, P, P, P, P, I64, P], I),
+        "qldpc_osd_decode_batch_cs_prior": ([P, I64, P, P, I, P, P, I], I),
+        "qldpc_osd_device_cs_prior": ([P, I64, P, P, I, P, P, P, P], I),
+        "qldpc_osd_device_ordered_cs_prior": ([P, I64, P, P, I, P, P, P, P, P, P], I),
+        "qldpc_osd_device_ordered_ex_cs_prior": ([P, I64, P, P, I, P, P, P, P, P, P, P, P, I64, P], I),
         "qldpc_osd_kernel_name": ([P, I, ctypes.c_char_p, I], I),
         "qldpc_cpython_setdiff_first": ([I, P, I], I),
         "qldpc_osd_order_host": ([P, I64, I, P, P, I], I),

@@ -875,6 +875,8 @@ extern "C" int qldpc_prior_create(const qldpc_code* code, const double* h_p, dou
   }
   pr->W.resize(n);                                    // |L_j| < 750: L_j 2^20 is exact and fits; round-half-even
   for (int j = 0; j < n; ++j) pr->W[j] = (int64_t)std::llrint(std::ldexp(pr->L[j], 20));
+  pr->Wo.resize(n);
+  for (int j = 0; j < n; ++j) pr->Wo[code->vperm[j]] = pr->W[j];
   if (code->device >= 0) {
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
@@ -882,6 +884,7 @@ extern "C" int qldpc_prior_create(const qldpc_code* code, const double* h_p, dou
       return fail(QLDPC_EINVAL, "code lives on device %d, current device is %d", code->device, dev);
     HIP_TRY(pr->d_L.upload(pr->L));
     HIP_TRY(pr->d_W.upload(pr->W));
+    HIP_TRY(pr->d_Wo.upload(pr->Wo));
   }
   pr->filt0 = prior_filter_word(code, pr->L);
   *out = pr.release();

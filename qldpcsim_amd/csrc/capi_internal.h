@@ -243,7 +243,9 @@ struct qldpc_prior {
   capi::DevBuf<double> d_L;
   std::vector<int64_t> W;        // [n] llrint(L_j 2^20): relay_vprior_kernel's solution weights
   capi::DevBuf<int64_t> d_W;
-  uint32_t filt0 = 0;            // prior_filter_word(code, L): hbm_tile_vprior_kernel's filter word at start
+  std::vector<int64_t> Wo;       // [n] the same weights by original column: OSD-CS's prior cost indexes them
+  capi::DevBuf<int64_t> d_Wo;    // through perm
+  uint32_t filt0 = 0;           // prior_filter_word(code, L): hbm_tile_vprior_kernel's filter word at start
 };
 
 // ---------------------------------------------------------------------------
@@ -296,6 +298,8 @@ struct Gf2Basis {
   Gf2Basis(int m, int mw_) : mw(mw_), vec((size_t)std::max(m, 1) * std::max(mw_, 1), 0), has(std::max(m, 1), 0) {}
   bool insert(uint64_t* x);   // true if x (modified) was independent and got inserted
 };
+// QLDPC_EINVAL unless `prior` is a handle built for `code` (the _cs_prior entry points, host and device)
+int osd_cs_prior_checked(const qldpc_code* code, const qldpc_prior* prior);
 
 // capi_decode.cpp. choose_kernel and plan_static call no HIP function: the
 // static kernel arguments can be checked on a machine without a device.

@@ -60,8 +60,8 @@ static hipError_t osd_chunks(const qldpc::OsdArgs& a, int64_t count, int64_t chu
   return e;
 }
 
-// Which OSD kernel runs a code: all that (m, n, zero_col, the options, cs)
-// decide, without a HIP call; the launchers and qldpc_osd_kernel_name read it
+// Which OSD kernel runs a code: all that (m, n, zero_col, the options, cs = 0,
+// kOsdCsHamming or kOsdCsPrior) decide, without a HIP call; the launchers and qldpc_osd_kernel_name read it
 struct OsdChoice {
   const void *kernel = nullptr, *kblk = nullptr;   // osd_hbm_kernel or osd_kernel<nw>; the block kernel in front of it, or null
   const char* name = "";              // of the kernel that does the work: kblk's, else kernel's
@@ -69,11 +69,14 @@ struct OsdChoice {
   int nw = 0, rt = 1;                 // row words of the instance (0 past 33); block kernel: rows per thread
   int block = 0, bblk = 0, mr = 0;    // threads of kernel and of kblk; kblk's rt * bblk row slots
 };
+static int cs_kind(int cs_lambda, const qldpc_prior* prior) {
+  return cs_lambda < 0 ? 0 : prior ? qldpc::kOsdCsPrior : qldpc::kOsdCsHamming;
+}
 static int osd_threads(int rows) { return std::max(64, (rows + 63) / 64 * 64); }   // one per row, whole waves
 
 // QLDPC_EUNSUP where cs asks for OSD-CS and the code cannot have it on the device:
 // it is osd_block_kernel's epilogue (that kernel's range, and no other kernel)
-static int choose_osd_kernel(const qldpc_code* code, bool cs, OsdChoice* c) {
+static int choose_osd_kernel(const qldpc_code* code, int cs, OsdChoice* c) {
   const int m = code->m, n = code->n;
   const bool column = opt(&Options::osd_column) != 0, hbm = opt(&Options::osd_hbm) != 0;
   const char* why = !cs                     ? nullptr
@@ -146,14 +149,16 @@ static int osd_hbm_impl(const qldpc_code* code, const OsdChoice& c, qldpc::OsdAr
 }
 
 // cs_lambda < 0: the reference's OSD of `order`; else OSD-CS (order unused;
-// the _cs entry points have checked lambda's range)
+// the _cs entry points have checked lambda's range), with the prior-weighted
+// cost where `prior` is given (checked by the _cs_prior entry points)
 static int osd_device_impl(const qldpc_code* code, int64_t count, const uint8_t* d_syn, const int32_t* d_perm,
                            const int32_t* d_tiepos, const double* d_post, int order, int cs_lambda,
-                           uint8_t* d_ehat, int32_t* d_status, void* stream, const SpillCfg& spill = {}) {
+                           uint8_t* d_ehat, int32_t* d_status, void* stream, const SpillCfg& spill = {},
+                           const qldpc_prior* prior = nullptr) {
   if (!code) return fail(QLDPC_EINVAL, "code is null");
   const bool cs = cs_lambda >= 0;
   OsdChoice c;
-  if (const int rc = choose_osd_kernel(code, cs, &c)) return rc;
+  if (const int rc = choose_osd_kernel(code, cs_kind(cs_lambda, prior), &c)) return rc;
   if (cs) order = 0;                                // the base estimate, and the redo pass's semantics
   if (count < 0) return fail(QLDPC_EINVAL, "negative count");
   if (count == 0) return QLDPC_OK;
@@ -180,6 +185,12 @@ static int osd_device_impl(const qldpc_code* code, int64_t count, const uint8_t*
     a.spill_cap = spill.cap;
   }
   a.cs_lambda = cs ? cs_lambda : 0;
+  if (cs && prior) {
+    if (code->device >= 0 && !prior->d_Wo.p) return fail(QLDPC_EINVAL, "the prior handle holds no device weights");
+    for (const int64_t w : prior->Wo)                 // (holds by construction: |L| < 750)
+      if (w >= (1ll << 30) || w <= -(1ll << 30)) return fail(QLDPC_EUNSUP, "OSD-CS prior weight past 2^30");
+    a.cs_w = prior->d_Wo.p;
+  }
   int dev = 0, max_lds = 0;
   HIP_TRY(hipGetDevice(&dev));
   HIP_TRY(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
@@ -193,7 +204,8 @@ static int osd_device_impl(const qldpc_code* code, int64_t count, const uint8_t*
   HIP_TRY(hipFuncSetAttribute(kcol, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
   if (kblk && lds_blk > (size_t)max_lds) kblk = nullptr;
   // OSD-CS has the block kernel alone, and works in its block-loop LDS (Wd .. CT)
-  if (cs && (!kblk || qldpc::osd_cs_lds(c.nw, c.mr) > qldpc::osd_block_cs_room(c.nw, c.mr)))
+  const size_t cs_need = prior ? qldpc::osd_cs_prior_lds(c.nw, c.mr) : qldpc::osd_cs_lds(c.nw, c.mr);
+  if (cs && (!kblk || cs_need > qldpc::osd_block_cs_room(c.nw, c.mr)))
     return fail(QLDPC_EUNSUP, "OSD-CS on the device needs the block kernel (m = %d, n = %d)", m, n);
   if (kblk) HIP_TRY(hipFuncSetAttribute(kblk, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
   // rank(H) and the column bit-vectors: built on first use, after every
@@ -284,17 +296,17 @@ extern "C" int qldpc_osd_device_ordered(const qldpc_code* code, int64_t count, c
 static int osd_ordered_impl(const qldpc_code* code, int64_t count, const uint8_t* d_syn, const double* d_post,
                             int order, int cs_lambda, uint8_t* d_ehat, int32_t* d_status, int32_t* d_perm,
                             int32_t* d_tiepos, double* d_spill_post, int32_t* d_spill_idx, int32_t* d_spill_count,
-                            int64_t spill_cap, void* stream) {
+                            int64_t spill_cap, void* stream, const qldpc_prior* prior = nullptr) {
   if (d_spill_count && (!d_spill_post || !d_spill_idx || spill_cap < 0))
     return fail(QLDPC_EINVAL, "spill buffers incomplete");
   if (d_spill_count && count > INT32_MAX) return fail(QLDPC_EINVAL, "spill indices are int32");
   OsdChoice c;                                       // (OSD-CS is refused before the order kernel's launch too)
   if (cs_lambda >= 0 && code)
-    if (const int rc = choose_osd_kernel(code, true, &c)) return rc;
+    if (const int rc = choose_osd_kernel(code, cs_kind(cs_lambda, prior), &c)) return rc;
   const int rc = qldpc_osd_order_device(code, count, d_post, d_perm, d_tiepos, stream);
   if (rc != QLDPC_OK) return rc;
   return osd_device_impl(code, count, d_syn, d_perm, d_tiepos, d_post, order, cs_lambda, d_ehat, d_status, stream,
-                         SpillCfg{d_spill_post, d_spill_idx, d_spill_count, spill_cap});
+                         SpillCfg{d_spill_post, d_spill_idx, d_spill_count, spill_cap}, prior);
 }
 
 extern "C" int qldpc_osd_device_ordered_ex(const qldpc_code* code, int64_t count, const uint8_t* d_syn,
@@ -323,12 +335,41 @@ extern "C" int qldpc_osd_device_ordered_ex_cs(const qldpc_code* code, int64_t co
                           d_spill_idx, d_spill_count, spill_cap, stream);
 }
 
+extern "C" int qldpc_osd_device_cs_prior(const qldpc_code* code, int64_t count, const uint8_t* d_syn,
+                                         const int32_t* d_perm, int lambda, const qldpc_prior* prior,
+                                         uint8_t* d_ehat, int32_t* d_status, void* stream) {
+  if (const int rc = cs_lambda_checked(lambda)) return rc;
+  if (const int rc = osd_cs_prior_checked(code, prior)) return rc;
+  return osd_device_impl(code, count, d_syn, d_perm, nullptr, nullptr, 0, lambda, d_ehat, d_status, stream, {},
+                         prior);
+}
+
+extern "C" int qldpc_osd_device_ordered_cs_prior(const qldpc_code* code, int64_t count, const uint8_t* d_syn,
+                                                 const double* d_post, int lambda, const qldpc_prior* prior,
+                                                 uint8_t* d_ehat, int32_t* d_status, int32_t* d_perm,
+                                                 int32_t* d_tiepos, void* stream) {
+  return qldpc_osd_device_ordered_ex_cs_prior(code, count, d_syn, d_post, lambda, prior, d_ehat, d_status, d_perm,
+                                              d_tiepos, nullptr, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int qldpc_osd_device_ordered_ex_cs_prior(const qldpc_code* code, int64_t count, const uint8_t* d_syn,
+                                                    const double* d_post, int lambda, const qldpc_prior* prior,
+                                                    uint8_t* d_ehat, int32_t* d_status, int32_t* d_perm,
+                                                    int32_t* d_tiepos, double* d_spill_post, int32_t* d_spill_idx,
+                                                    int32_t* d_spill_count, int64_t spill_cap, void* stream) {
+  if (const int rc = cs_lambda_checked(lambda)) return rc;
+  if (const int rc = osd_cs_prior_checked(code, prior)) return rc;
+  return osd_ordered_impl(code, count, d_syn, d_post, 0, lambda, d_ehat, d_status, d_perm, d_tiepos, d_spill_post,
+                          d_spill_idx, d_spill_count, spill_cap, stream, prior);
+}
+
 // The kernel choose_osd_kernel picks: the block kernel's instance (NW row
 // words, SL engine slots, RT rows per thread), or the kernel that runs instead
 extern "C" int qldpc_osd_kernel_name(const qldpc_code* code, int cs, char* buf, int len) {
   if (!code || !buf || len <= 0) return fail(QLDPC_EINVAL, "null argument");
   OsdChoice c;
-  if (const int rc = choose_osd_kernel(code, cs != 0, &c)) return rc;
+  if (const int rc = choose_osd_kernel(code, cs == 2 ? qldpc::kOsdCsPrior : cs != 0 ? qldpc::kOsdCsHamming : 0, &c))
+    return rc;
   snprintf(buf, len, "%s", c.name);
   return QLDPC_OK;
 }

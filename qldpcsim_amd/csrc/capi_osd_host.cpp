@@ -222,12 +222,15 @@ extern "C" int qldpc_osd_decode(const qldpc_code* code, const uint8_t* h_syn, co
 // ascending) and, in pivot row k, column k of B^-1 H_T and of B^-1 s. The base
 // estimate e0 is the order-0 result; candidates, in order: e0, every single
 // flip of T[k], every pair T[a], T[b] with a < b < min(lambda, |T|); the first
-// of strictly smallest Hamming weight wins. Three cases have no B^-1 and
-// return the order-0 result of osd_one: an all-zero column perm[0] (J's
-// unconditional first entry is no pivot), a syndrome outside H's column space,
-// and rank(H) <= 1 (the reference's IndexError case, QLDPC_ERANGE).
+// of strictly smallest cost wins. The cost is the Hamming weight, or with a
+// weight row Wo (one int64 per original column, qldpc_prior::Wo; DESIGN.md
+// §3.19) the exact sum of Wo over the estimate's support. Three cases have no
+// B^-1 and return the order-0 result of osd_one: an all-zero column perm[0]
+// (J's unconditional first entry is no pivot), a syndrome outside H's column
+// space, and rank(H) <= 1 (the reference's IndexError case, QLDPC_ERANGE).
 // ---------------------------------------------------------------------------
-static int osd_cs_one(const qldpc_code* c, const uint8_t* syn, const int32_t* perm, int lambda, uint8_t* ehat) {
+static int osd_cs_one(const qldpc_code* c, const uint8_t* syn, const int32_t* perm, int lambda, uint8_t* ehat,
+                      const int64_t* Wo = nullptr) {
   const int m = c->m, n = c->n, mw = c->mw;
   if (n == 0) return QLDPC_OK;
   code_osd_prep(c);
@@ -291,26 +294,39 @@ static int osd_cs_one(const qldpc_code* c, const uint8_t* syn, const int32_t* pe
     for (int k = 0; k < nJ; ++k)
       if ((R[(size_t)k * nw + (i >> 6)] >> (i & 63)) & 1) out[k >> 6] |= 1ull << (k & 63);
   };
-  // cost change of XOR-ing `col` into e_J: +1 per 0 it sets, -1 per 1 it clears
+  // signed weight of pivot row k: what flipping e0_J[k] adds to the cost
+  std::vector<int64_t> sw(Wo ? nJ : 0);
+  for (int k = 0; k < (int)sw.size(); ++k) sw[k] = ((eJ[k >> 6] >> (k & 63)) & 1) ? -Wo[perm[J[k]]] : Wo[perm[J[k]]];
+  // cost change of XOR-ing `col` into e_J: +1 (+W) per 0 it sets, -1 (-W) per 1 it clears
   auto delta = [&](const uint64_t* col) {
-    int d = 0;
-    for (int w = 0; w < kw; ++w) d += __builtin_popcountll(col[w]) - 2 * __builtin_popcountll(col[w] & eJ[w]);
+    int64_t d = 0;
+    for (int w = 0; w < kw; ++w) {
+      if (!Wo) {
+        d += __builtin_popcountll(col[w]) - 2 * __builtin_popcountll(col[w] & eJ[w]);
+        continue;
+      }
+      for (uint64_t bits = col[w]; bits; bits &= bits - 1) d += sw[64 * w + __builtin_ctzll(bits)];
+    }
     return d;
   };
-  auto flip_cost = [&](int i) { return ((eT[i >> 6] >> (i & 63)) & 1) ? -1 : 1; };
+  auto flip_cost = [&](int i) -> int64_t {
+    const int64_t wt = Wo ? Wo[perm[i]] : 1;
+    return ((eT[i >> 6] >> (i & 63)) & 1) ? -wt : wt;
+  };
   const int L = std::min(lambda, nT);
   std::vector<uint64_t> first((size_t)std::max(L, 1) * std::max(kw, 1)), col(std::max(kw, 1));
-  int best = 0, ba = -1, bb = -1;                     // strictly below the base's 0, first such
+  int64_t best = 0;                                   // strictly below the base's 0, first such
+  int ba = -1, bb = -1;
   for (int k = 0; k < nT; ++k) {
     uint64_t* dst = k < L ? &first[(size_t)k * kw] : col.data();
     column(T[k], dst);
-    const int d = flip_cost(T[k]) + delta(dst);
+    const int64_t d = flip_cost(T[k]) + delta(dst);
     if (d < best) best = d, ba = k, bb = -1;
   }
   for (int a = 0; a < L; ++a)
     for (int b = a + 1; b < L; ++b) {
       for (int w = 0; w < kw; ++w) col[w] = first[(size_t)a * kw + w] ^ first[(size_t)b * kw + w];
-      const int d = flip_cost(T[a]) + flip_cost(T[b]) + delta(col.data());
+      const int64_t d = flip_cost(T[a]) + flip_cost(T[b]) + delta(col.data());
       if (d < best) best = d, ba = a, bb = b;
     }
   for (int f : {ba, bb})
@@ -325,9 +341,9 @@ static int osd_cs_one(const qldpc_code* c, const uint8_t* syn, const int32_t* pe
 
 int qldpc_host_thread_budget();                         // np_order.cpp
 
-// lambda < 0: the reference's OSD of `order`; else OSD-CS with that lambda
+// lambda < 0: the reference's OSD of `order`; else OSD-CS with that lambda, and with the weight row Wo if given
 static int osd_batch(const qldpc_code* code, int64_t count, const uint8_t* h_syn, const int32_t* h_perm, int order,
-                     int lambda, uint8_t* h_ehat, int nthreads) {
+                     int lambda, uint8_t* h_ehat, int nthreads, const int64_t* Wo = nullptr) {
   if (!code) return fail(QLDPC_EINVAL, "code is null");
   if (count <= 0) return QLDPC_OK;
   if (nthreads <= 0) nthreads = qldpc_host_thread_budget();
@@ -346,7 +362,7 @@ static int osd_batch(const qldpc_code* code, int64_t count, const uint8_t* h_syn
         r = qldpc_osd_decode(code, h_syn + b * m, h_perm + b * n, order, h_ehat + b * n, nullptr, nullptr, -1);
       } else {
         r = osd_check_perm(code, h_perm + b * n);
-        if (r == QLDPC_OK) r = osd_cs_one(code, h_syn + b * m, h_perm + b * n, lambda, h_ehat + b * n);
+        if (r == QLDPC_OK) r = osd_cs_one(code, h_syn + b * m, h_perm + b * n, lambda, h_ehat + b * n, Wo);
       }
       if (r != QLDPC_OK) {
         std::lock_guard<std::mutex> lk(emu);
@@ -368,10 +384,31 @@ extern "C" int qldpc_osd_decode_batch(const qldpc_code* code, int64_t count, con
   return osd_batch(code, count, h_syn, h_perm, order, -1, h_ehat, nthreads);
 }
 
-extern "C" int qldpc_osd_decode_batch_cs(const qldpc_code* code, int64_t count, const uint8_t* h_syn,
-                                         const int32_t* h_perm, int lambda, uint8_t* h_ehat, int nthreads) {
+// the prior handle of an OSD-CS call with the weighted cost: built for this code
+int capi::osd_cs_prior_checked(const qldpc_code* code, const qldpc_prior* prior) {
+  if (!code) return fail(QLDPC_EINVAL, "code is null");
+  if (!prior) return fail(QLDPC_EINVAL, "OSD-CS with the prior cost needs a prior handle (null)");
+  if (prior->code != code || prior->n != code->n || (int)prior->Wo.size() != code->n)
+    return fail(QLDPC_EINVAL, "the prior handle was built for another code");
+  return QLDPC_OK;
+}
+
+static int osd_batch_cs(const qldpc_code* code, int64_t count, const uint8_t* h_syn, const int32_t* h_perm,
+                        int lambda, const int64_t* Wo, uint8_t* h_ehat, int nthreads) {
   if (lambda < 0 || lambda > QLDPC_OSD_CS_MAX_LAMBDA)
     return fail(QLDPC_EINVAL, "OSD-CS lambda must lie in 0..%d (got %d)", QLDPC_OSD_CS_MAX_LAMBDA, lambda);
   if (count > 0 && (!h_perm || !h_ehat || (!h_syn && code && code->m))) return fail(QLDPC_EINVAL, "null argument");
-  return osd_batch(code, count, h_syn, h_perm, 0, lambda, h_ehat, nthreads);
+  return osd_batch(code, count, h_syn, h_perm, 0, lambda, h_ehat, nthreads, Wo);
+}
+
+extern "C" int qldpc_osd_decode_batch_cs(const qldpc_code* code, int64_t count, const uint8_t* h_syn,
+                                         const int32_t* h_perm, int lambda, uint8_t* h_ehat, int nthreads) {
+  return osd_batch_cs(code, count, h_syn, h_perm, lambda, nullptr, h_ehat, nthreads);
+}
+
+extern "C" int qldpc_osd_decode_batch_cs_prior(const qldpc_code* code, int64_t count, const uint8_t* h_syn,
+                                               const int32_t* h_perm, int lambda, const qldpc_prior* prior,
+                                               uint8_t* h_ehat, int nthreads) {
+  if (const int rc = osd_cs_prior_checked(code, prior)) return rc;
+  return osd_batch_cs(code, count, h_syn, h_perm, lambda, prior->Wo.data(), h_ehat, nthreads);
 }

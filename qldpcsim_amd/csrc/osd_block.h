@@ -1,4 +1,5 @@
-// osd_block.h — osd_block_kernel<NW, SL, RT>, its OSD-CS twin and their helpers; the body is osd_block_body.inc.
+// osd_block.h — osd_block_kernel<NW, SL, RT>, its two OSD-CS twins (Hamming and prior-weighted cost) and their
+// helpers; the body is osd_block_body.inc.
 #pragma once
 #include "osd_common.h"
 
@@ -377,6 +378,200 @@ __device__ __forceinline__ void osd_cs_epilogue(const OsdArgs& a, const uint64_t
   }
 }
 
+// ---------------------------------------------------------------------------
+// OSD-CS epilogue with the prior-weighted cost: the same
+// candidates, order and index coding as osd_cs_epilogue; the cost of an
+// estimate is the sum of w over its support, w = a.cs_w by original column
+// (llrint(L 2^20), |w| < 2^30, negative where p > 1/2). Pivot row r carries its
+// signed weight sw_r = w[perm[J[r]]] (1 - 2 e0_J[r]) (0 for rows without
+// pivot): the cost change of a flip set is the flips' own signed weights plus
+// the sum of sw_r over the set bits r of x = the XOR of its columns.
+//
+// A column's sum: each lane adds sw of its rows that hold a 1, split as
+// sw = hi 2^21 + lo (0 <= lo < 2^21, |hi| < 2^9) so that a wave's sums of 128
+// terms fit 32 bits; two DPP wave sums, joined to one int64 that lane 0 adds
+// to the column's LDS counter. A pair's sum over the XOR of its two stored
+// columns is their two counters less twice the sum of sw over the set bits of
+// their AND. The key is (cost change + 2^42) << 13 | index: the
+// change is below 2^41 in magnitude (1088 columns of |w| < 2^30), 64 bits,
+// unsigned order = order of (cost, index).
+//
+// LDS (osd_cs_prior_lds bytes of osd_block_cs_room):
+//   colv [64][Q] u64 | cnt [64 NW] i64 | tmask [NW] u64 | red [2] u64 | sw [MR] i32 | tl [64] i32
+// ---------------------------------------------------------------------------
+constexpr int kCswSplit = 21, kCswBiasLog = 42;
+
+// sum over the wave (every lane active), wave-uniform
+__device__ __forceinline__ int wave_sum32(int x) {
+  x += __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xf, 0xf, false);    // quad_perm [1,0,3,2]
+  x += __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xf, 0xf, false);    // quad_perm [2,3,0,1]
+  x += __builtin_amdgcn_update_dpp(0, x, 0x141, 0xf, 0xf, false);   // row_half_mirror
+  x += __builtin_amdgcn_update_dpp(0, x, 0x140, 0xf, 0xf, false);   // row_mirror
+  return __builtin_amdgcn_readlane(x, 0) + __builtin_amdgcn_readlane(x, 16) + __builtin_amdgcn_readlane(x, 32) +
+         __builtin_amdgcn_readlane(x, 48);
+}
+
+template <int NW, int RT>
+__device__ __forceinline__ void osd_cs_prior_epilogue(const OsdArgs& a, const uint64_t (&R)[RT][NW],
+                                                      const bool (&own)[RT], const int (&mypos)[RT], int nJ,
+                                                      const int* Jl, const unsigned char* inJ, const uint64_t* emask,
+                                                      uint64_t* region, const int32_t* perm, uint8_t* ehat) {
+  const int n = a.n, t = threadIdx.x, B = blockDim.x, lane = t & 63;
+  const int nwaves = B >> 6, wave = __builtin_amdgcn_readfirstlane(t >> 6), Q = RT * nwaves;
+  const int L = min(a.cs_lambda, n - nJ);
+  uint64_t* colv = region;
+  unsigned long long* cnt = (unsigned long long*)(colv + 64 * Q);   // int64 sums, two's complement
+  uint64_t* tmask = (uint64_t*)(cnt + 64 * NW);
+  unsigned long long* red = (unsigned long long*)(tmask + NW);
+  int* sw = (int*)(red + 2);                          // [MR], row t + h B at that index = bit of colv's word
+  int* tl = sw + RT * B;
+  const int64_t* wcol = a.cs_w;
+
+  // e0_J as the order-0 epilogue, and each pivot row's signed weight
+  bool piv[RT];
+  uint32_t ej[RT];
+  int swlo[RT], swhi[RT];
+#pragma unroll
+  for (int h = 0; h < RT; ++h) {
+    piv[h] = own[h] && mypos[h] < nJ;
+    uint64_t acc = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      if (w == (n >> 6)) acc ^= (R[h][w] >> (n & 63)) & 1ull;
+      acc ^= (uint64_t)(__builtin_popcountll(R[h][w] & emask[w]) & 1);
+    }
+    ej[h] = piv[h] ? (uint32_t)(acc & 1ull) : 0u;
+    int s = 0;
+    if (piv[h]) {
+      const int wj = (int)wcol[perm[Jl[mypos[h]]]];
+      s = ej[h] ? -wj : wj;
+    }
+    sw[t + h * B] = s;
+    swlo[h] = s & ((1 << kCswSplit) - 1);
+    swhi[h] = s >> kCswSplit;                         // (arithmetic: s = swhi 2^21 + swlo)
+  }
+  for (int i0w = 64 * wave; i0w < 64 * NW; i0w += B) {
+    const int i = i0w + lane;
+    const uint64_t bits = __ballot(i < n && !inJ[i]);
+    if (lane == 0) tmask[i0w >> 6] = bits;
+  }
+  for (int i = t; i < 64 * NW; i += B) cnt[i] = 0ull;
+  if (t == 0) red[0] = 1ull << (kCswBiasLog + kCsIdxBits);   // e0: cost change 0, index 0
+  __syncthreads();
+
+  // every T column's sum into cnt, the first L columns' ballots into colv
+  int k = 0;
+  for (int w = 0; w < NW && 64 * w < n; ++w) {
+    uint64_t rw[RT];
+#pragma unroll
+    for (int h = 0; h < RT; ++h) {
+      uint64_t v = 0;
+#pragma unroll
+      for (int x = 0; x < NW; ++x)
+        if (x == w) v = R[h][x];
+      rw[h] = piv[h] ? v : 0ull;
+    }
+    const uint64_t tm = tmask[w];
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      uint32_t bits = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(tm >> (32 * half)));
+      uint32_t r32[RT];
+#pragma unroll
+      for (int h = 0; h < RT; ++h) r32[h] = (uint32_t)(rw[h] >> (32 * half));
+      while (bits) {
+        bits = (uint32_t)__builtin_amdgcn_readfirstlane((int)bits);
+        k = __builtin_amdgcn_readfirstlane(k);
+        const int b = (int)__builtin_ctz(bits);
+        bits &= bits - 1;
+        const int c = 64 * w + 32 * half + b;
+        int lo = 0, hi = 0;
+#pragma unroll
+        for (int h = 0; h < RT; ++h) {
+          const int mk = __builtin_amdgcn_sbfe((int)r32[h], b, 1);   // 0 / -1
+          lo += swlo[h] & mk;
+          hi += swhi[h] & mk;
+          if (k < L) {
+            const uint64_t bal = __ballot(mk != 0);
+            if (lane == 0) colv[k * Q + h * nwaves + wave] = bal;
+          }
+        }
+        const int slo = wave_sum32(lo), shi = wave_sum32(hi);
+        // (the two halves join here, after the lanes: no 64-bit value crosses them)
+        const long long d = (long long)shi * (1ll << kCswSplit) + (long long)slo;
+        if (lane == 0 && d != 0) atomicAdd(&cnt[c], (unsigned long long)d);
+        if (k < L && t == 0) tl[k] = c;
+        ++k;
+      }
+    }
+  }
+  __syncthreads();
+
+  auto flip_cost = [&](int c) {
+    const long long wc = (long long)wcol[perm[c]];
+    return ((emask[c >> 6] >> (c & 63)) & 1ull) ? -wc : wc;
+  };
+  auto key_of = [](long long d, int idx) {
+    return ((unsigned long long)(d + (1ll << kCswBiasLog)) << kCsIdxBits) | (unsigned long long)idx;
+  };
+  unsigned long long best = ~0ull;
+  for (int c = t; c < n; c += B)
+    if (!inJ[c]) best = min(best, key_of((long long)cnt[c] + flip_cost(c), 1 + c));
+  for (int idx = t; idx < 64 * L; idx += B) {
+    const int pa = idx >> 6, pb = idx & 63;
+    if (pa < pb && pb < L) {
+      // sum of sw over a ^ b = the two columns' sums less twice the sum over a & b (fewer set bits to walk
+      // than a ^ b while the columns are less than 2/3 full)
+      const int ca = tl[pa], cb = tl[pb];
+      long long both = 0;
+      for (int q = 0; q < Q; ++q) {
+        uint64_t x = colv[pa * Q + q] & colv[pb * Q + q];
+        // (word q's bit j is row slot 64 q + j: q = h nwaves + wave, j = lane)
+        while (x) {
+          both += (long long)sw[64 * q + (int)__builtin_ctzll(x)];
+          x &= x - 1;
+        }
+      }
+      const long long d = flip_cost(ca) + flip_cost(cb) + (long long)cnt[ca] + (long long)cnt[cb] - 2 * both;
+      best = min(best, key_of(d, kCsPair + idx));
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint32_t olo = (uint32_t)__shfl_xor((int)(uint32_t)best, off, 64);
+    const uint32_t ohi = (uint32_t)__shfl_xor((int)(uint32_t)(best >> 32), off, 64);
+    best = min(best, ((unsigned long long)ohi << 32) | olo);
+  }
+  if (lane == 0) atomicMin(&red[0], best);
+  __syncthreads();
+
+  // the winner's columns into e0_J (pivot rows), its T flips into e_hat
+  const int idx = (int)(red[0] & ((1ull << kCsIdxBits) - 1));
+  int c1 = -1, c2 = -1;
+  if (idx >= kCsPair) {
+    c1 = tl[(idx - kCsPair) >> 6];
+    c2 = tl[(idx - kCsPair) & 63];
+  } else if (idx > 0) {
+    c1 = idx - 1;
+  }
+#pragma unroll
+  for (int h = 0; h < RT; ++h)
+    if (piv[h]) {
+      uint64_t v1 = 0, v2 = 0;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) {
+        if (c1 >= 0 && w == (c1 >> 6)) v1 = R[h][w];
+        if (c2 >= 0 && w == (c2 >> 6)) v2 = R[h][w];
+      }
+      const uint32_t e = ej[h] ^ (c1 >= 0 ? (uint32_t)(v1 >> (c1 & 63)) & 1u : 0u) ^
+                         (c2 >= 0 ? (uint32_t)(v2 >> (c2 & 63)) & 1u : 0u);
+      ehat[perm[Jl[mypos[h]]]] = (uint8_t)e;
+    }
+  if (t == 0) {
+    if (c1 >= 0) ehat[perm[c1]] ^= 1;
+    if (c2 >= 0) ehat[perm[c2]] ^= 1;
+  }
+}
+
 // SL = rows per wave-0 lane (m <= 64 SL), sized to the code so the state stays
 // in VGPRs; RT = rows per thread (thread t holds rows t, t + blockDim, ..):
 // with 2, a 450-row shot takes 4 waves and a CU holds 4 shots (4 engines, one
@@ -392,6 +587,14 @@ __global__ void __launch_bounds__(64 * SL / RT) __attribute__((amdgpu_waves_per_
 template <int NW, int SL, int RT>
 __global__ void __launch_bounds__(64 * SL / RT) __attribute__((amdgpu_waves_per_eu(RT == 2 ? QLDPC_OSD_WPE : 1))) osd_block_cs_kernel(OsdArgs a) {
 #define QLDPC_OSD_BLOCK_CS 1
+#include "osd_block_body.inc"
+#undef QLDPC_OSD_BLOCK_CS
+}
+
+// and by the OSD-CS epilogue with the prior-weighted cost (osd_cs_prior_epilogue)
+template <int NW, int SL, int RT>
+__global__ void __launch_bounds__(64 * SL / RT) __attribute__((amdgpu_waves_per_eu(RT == 2 ? QLDPC_OSD_WPE : 1))) osd_block_cs_prior_kernel(OsdArgs a) {
+#define QLDPC_OSD_BLOCK_CS 2
 #include "osd_block_body.inc"
 #undef QLDPC_OSD_BLOCK_CS
 }

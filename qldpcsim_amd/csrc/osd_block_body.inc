@@ -1,7 +1,7 @@
-// osd_block_body.inc — the body of osd_block_kernel and osd_block_cs_kernel
+// osd_block_body.inc — the body of osd_block_kernel, osd_block_cs_kernel and osd_block_cs_prior_kernel
 // (osd_block.h; template parameters NW, SL, RT, argument `a`; LDS bytes: osd_block_lds, osd_kernels.h),
 // included once per kernel. QLDPC_OSD_BLOCK_CS = 1 ends it with the OSD-CS epilogue
-// (osd_cs_epilogue) instead of the order-0 one; with 0 the text is the
+// (osd_cs_epilogue), 2 with the prior-weighted one (osd_cs_prior_epilogue) instead of the order-0 one; with 0 the text is the
 // order-0 kernel's alone, so that kernel's machine code does not depend on
 // the other's.
   // LDS: inv_perm[n] | J list [m+2] | inJ bytes [n] | emask [NW] | Wd [MR] | Cm [MR] |
@@ -320,7 +320,11 @@
   }
   __syncthreads();
 #if QLDPC_OSD_BLOCK_CS
+#if QLDPC_OSD_BLOCK_CS == 2
+  osd_cs_prior_epilogue<NW, RT>(a, R, own, mypos, nJ, Jl, inJ, emask, Wd, perm, ehat);
+#else
   osd_cs_epilogue<NW, RT>(a, R, own, mypos, nJ, Jl, inJ, emask, Wd, perm, ehat);
+#endif
   if (t == 0) a.status[shot] = 0;
   return;
 #endif

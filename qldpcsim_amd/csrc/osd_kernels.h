@@ -34,6 +34,8 @@ struct OsdArgs {
                            // (left by osd_block_kernel: syndrome outside H's column space)
   int cs_lambda;           // osd_block_kernel's OSD-CS instances only: pairs among the first
                            // min(cs_lambda, |T|) information positions (0 .. 64); `order` is 0
+  const int64_t* cs_w;     // osd_block_cs_prior_kernel only: weight of each original column
+                           // (qldpc_prior::d_Wo, |w| < 2^30), the cost in place of the Hamming weight
 };
 
 // Reliability order on the device (decoders.py:320-325): NumPy's exact order
@@ -68,8 +70,10 @@ inline size_t osd_hbm_lds(int m, int nwr) { return 8 * (size_t)((m + 63) / 64 * 
 int osd_nw_of(int words);
 const void* osd_hbm_kernel_ptr(const char** name);   // __global__ osd_hbm_kernel(OsdArgs, OsdHbmArgs)
 const void* select_osd_kernel(int nw, const char** name);
-// block elimination (the default), or null: osd_kernel runs alone. cs: the OSD-CS instance
-const void* select_osd_block_kernel(int nw, int m, bool cs, int* rows_per_thread, const char** name);
+// block elimination (the default), or null: osd_kernel runs alone. cs: 0 order 0 / 1, kOsdCsHamming or
+// kOsdCsPrior the OSD-CS instance of that cost
+constexpr int kOsdCsHamming = 1, kOsdCsPrior = 2;
+const void* select_osd_block_kernel(int nw, int m, int cs, int* rows_per_thread, const char** name);
 
 // Dynamic LDS bytes of osd_kernel<nw> and osd_block_kernel<nw, ..>: one term per array, in the order the
 // kernels carve them (osd_column.h, osd_block_body.inc). mr = the block kernel's row slots, table_ints =
@@ -87,6 +91,9 @@ inline size_t osd_block_cs_room(size_t nw, size_t mr) {
          + 8 * 64 * nw + (QLDPC_OSD_PAIRS ? 8 * 32 * nw : 0) + 8 * 64;   // PW [64][NW], PX [32][NW], CT [64] u64
 }
 inline size_t osd_cs_lds(int nw, int mr) { return 8 * (size_t)mr + (size_t)mr / 8 + 264 * (size_t)nw + 272; }
+// osd_cs_prior_epilogue's carve of the same room: colv [64][MR / 64] u64 | cnt [64 NW] i64 | tmask [NW] u64 |
+// red [2] u64 | sw [MR] i32 | tl [64] i32
+inline size_t osd_cs_prior_lds(int nw, int mr) { return 12 * (size_t)mr + 520 * (size_t)nw + 272; }
 inline size_t osd_block_lds(int m, int n, size_t nw, size_t mr, size_t table_ints) {
   return osd_head_lds(m, n) + 8 * nw               // emask [NW] u64
          + osd_block_cs_room(nw, mr)               // Wd | Cm | PW | PX | CT

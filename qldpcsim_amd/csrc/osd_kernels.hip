@@ -68,11 +68,13 @@ const void* osd_hbm_kernel_ptr(const char** name) { QLDPC_NAMED((&osd_hbm_kernel
 // spills (m <= 512 rows, n <= 1087 columns): SL = 4 engine slots and one row
 // per thread up to 256 rows, SL = 8 and two rows per thread up to 512; null ->
 // osd_kernel (the engine state would spill). cs: the OSD-CS instance of the
-// same configuration
-const void* select_osd_block_kernel(int nw, int m, bool cs, int* rows_per_thread, const char** name) {
+// same configuration, with the Hamming (kOsdCsHamming) or the prior cost (kOsdCsPrior)
+const void* select_osd_block_kernel(int nw, int m, int cs, int* rows_per_thread, const char** name) {
 #define QLDPC_OSD_BLK(NW, SL, RT)                                                                                 \
   if (nw > 0 && nw <= NW && m <= 64 * SL) {                                                                       \
     *rows_per_thread = RT;                                                                                        \
+    if (cs == kOsdCsPrior)                                                                                        \
+      QLDPC_NAMED((&osd_block_cs_prior_kernel<NW, SL, RT>), "osd_block_cs_prior_kernel<" #NW ", " #SL ", " #RT ">"); \
     if (cs) QLDPC_NAMED((&osd_block_cs_kernel<NW, SL, RT>), "osd_block_cs_kernel<" #NW ", " #SL ", " #RT ">");    \
     QLDPC_NAMED((&osd_block_kernel<NW, SL, RT>), "osd_block_kernel<" #NW ", " #SL ", " #RT ">");                  \
   }

@@ -53,7 +53,7 @@ __all__ = ["MS_decoder", "BP_decoder", "NG_decoder", "BF_decoder", "OSDdec", "de
            "Relay_decoder", "RelayConfig", "relay_gammas",
            "osd_perm", "pack_bits", "unpack_bits",
            "osd_perms", "apply_osd", "apply_osd_device", "apply_osd_device_many", "osd_device_stage",
-           "osd_device_finish", "osd_host_orders", "osd_status_check", "osd_method_checked", "numpy_order_pinned",
+           "osd_device_finish", "osd_host_orders", "osd_status_check", "osd_method_checked", "osd_cost_checked", "numpy_order_pinned",
            "numpy_libm_pinned", "parity_pins"]
 
 
@@ -132,7 +132,8 @@ def unpack_bits(words, k):
 
 def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, eps=1e-9,
                  want_post=False, osd_order=-1, layer_ptr=None, layer_rows=None, stream=None,
-                 out=None, ehat_bits=False, prior_mask=None, p_masked=None, relay=None, prior=None, osd_method="ref"):
+                 out=None, ehat_bits=False, prior_mask=None, p_masked=None, relay=None, prior=None, osd_method="ref",
+                 osd_cost="hamming"):
     """Decode a batch of syndromes of one matrix on the GPU.
 
     syndromes: uint8 [B, m] NumPy array (host; staged, synchronous) or a
@@ -174,6 +175,12 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
     every single flip of an information position and every pair among the
     first lambda, lowest Hamming weight wins. MS / BP only: "cs" with
     osd_order < 0, with RELAY, NG or BF, or an unknown method raises ValueError.
+    `osd_cost` (with osd_method="cs"): "hamming", or "prior" (DESIGN.md §3.19):
+    the candidate of least prior weight wins, sum over its support of
+    llrint(L_j 2^20) with L_j the prior LLR of column j, an exact int64. The
+    row is this decode's `prior=`; "prior" without osd_method="cs" or without
+    `prior=` raises ValueError. A uniform row with p < 1/2 gives the "hamming"
+    result bit for bit.
     `algo="RELAY"` with `relay=RelayConfig(...)`: relay min-sum (DESIGN.md
     §3.11), flooding only. `max_iter` is ignored: the legs carry their own
     counts (relay.leg_iters). layers other than flooding, prior_mask and
@@ -188,6 +195,7 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
     refused with RELAY.
     """
     osd_method_checked(osd_method, osd_order, algo)
+    osd_cost_checked(osd_cost, osd_method, prior, "prior=")
     if prior is not None:
         if p is not None:
             raise ValueError("give either p (one scalar prior) or prior (one per column), not both")
@@ -239,7 +247,8 @@ def decode_batch(H, syndromes, p, max_iter, layers=None, algo="MS", beta=0.75, e
             *head, *ins, float(p), int(max_iter), float(beta), float(eps), *outs))
     if host and osd_order >= 0:
         syn, post = held[:2]
-        apply_osd(H, syn, res.ehat, post, res.flags, osd_order, **_method_kw("method", osd_method))
+        apply_osd(H, syn, res.ehat, post, res.flags, osd_order, **_method_kw("method", osd_method),
+                  **_cost_kw(osd_cost, prior, eps))
     return res
 
 
@@ -437,6 +446,34 @@ def osd_method_checked(method, order, algo="MS"):
             raise ValueError(f'osd_method="cs" takes its lambda from the OSD order: 0..{OSD_CS_MAX_LAMBDA}, '
                              f"got {order}")
     return method
+
+
+OSD_COSTS = ("hamming", "prior")
+
+
+def osd_cost_checked(cost, method, prior=None, where="prior="):
+    """The OSD-CS cost of a call, checked: "hamming" or "prior" (DESIGN.md
+    §3.19). ValueError for an unknown cost, and for "prior" without method
+    "cs" or without a prior row (`where` names the argument that gives it)."""
+    if cost not in OSD_COSTS:
+        raise ValueError(f"osd_cost must be one of {OSD_COSTS}, got {cost!r}")
+    if cost == "prior":
+        if method != "cs":
+            raise ValueError(f'osd_cost="prior" is OSD-CS\'s cost: it needs osd_method="cs", not {method!r}')
+        if prior is None:
+            raise ValueError(f'osd_cost="prior" weighs candidates by a prior row: give it ({where})')
+    return cost
+
+
+def _cost_kw(cost, prior, eps=1e-9, name="cost"):
+    """The OSD-CS cost with its row and eps as keywords, given only for
+    "prior": a "hamming" call is the call earlier releases made."""
+    return {} if cost == "hamming" else {name: cost, "prior": prior, "eps": eps}
+
+
+def _osd_prior_handle(code, cost, prior, eps):
+    """The qldpc_prior handle of an OSD call's row, or None with cost "hamming"."""
+    return None if cost == "hamming" else code.prior(prior, eps).handle
 
 
 def _method_kw(name, method):
@@ -649,22 +686,26 @@ def _pinned(key, shape, dtype):
     return buf[:need].view(*shape)
 
 
-def apply_osd_device(H, syn, res, order, stream=None, method="ref"):
+def apply_osd_device(H, syn, res, order, stream=None, method="ref", cost="hamming", prior=None, eps=1e-9):
     """GPU OSD for the non-converged shots of a device decode `res`
     (DecodeResult of torch tensors, with posteriors). The reliability order is
     NumPy's, computed on the device (qldpc_osd_device_ordered); only the shots
     it leaves to NumPy (NaN posteriors, x86-simd-sort's std::sort fallback)
     have their posteriors copied to the host. Updates res.ehat in place. See
     apply_osd_device_many for several decodes at once. `method`: "ref", or "cs"
-    for OSD-CS with lambda = `order` (decode_batch's osd_method)."""
-    return apply_osd_device_many([(H, syn, res)], order, stream, method)[0]
+    for OSD-CS with lambda = `order` (decode_batch's osd_method); `cost`:
+    decode_batch's osd_cost, with "prior" the row `prior` (one probability per
+    column of H) and the `eps` of its LLRs."""
+    return apply_osd_device_many([(H, syn, res)], order, stream, method, cost, None if prior is None else [prior],
+                                 eps)[0]
 
 
-def apply_osd_device_many(items, order, stream=None, method="ref"):
+def apply_osd_device_many(items, order, stream=None, method="ref", cost="hamming", prior=None, eps=1e-9):
     """apply_osd_device for several (H, syn, res) decodes (the X and Z halves
-    of a batch): every device order and elimination is queued first."""
-    staged = osd_device_stage(items, stream, order=order, method=method)
-    osd_device_finish(items, staged, order, stream, method=method)
+    of a batch): every device order and elimination is queued first. `prior`
+    (cost "prior"): one row per item, in the items' order."""
+    staged = osd_device_stage(items, stream, order=order, method=method, cost=cost, prior=prior, eps=eps)
+    osd_device_finish(items, staged, order, stream, method=method, cost=cost, prior=prior, eps=eps)
     with _on_stream(stream):                      # the status check reads on the same stream
         osd_status_check(items)
     return [r.ehat for _, _, r in items]
@@ -732,7 +773,19 @@ def release_workspaces():
     _lib.release_hbm_workspaces()
 
 
-def osd_device_stage(items, stream=None, slot0=0, order=0, method="ref"):
+def _item_priors(items, method, cost, prior):
+    """osd_cost_checked for every item of a staged call -> one row (or None) per item."""
+    if osd_cost_checked(cost, method, prior, "prior=, one row per item") == "hamming":
+        return [None] * len(items)
+    rows = list(prior)
+    if len(rows) != len(items):
+        raise ValueError(f"prior must hold one row per item: {len(items)} items, {len(rows)} rows")
+    for row in rows:
+        osd_cost_checked(cost, method, row, "prior=, one row per item")
+    return rows
+
+
+def osd_device_stage(items, stream=None, slot0=0, order=0, method="ref", cost="hamming", prior=None, eps=1e-9):
     """First half of the device OSD: find each decode's non-converged shots
     (one device sync), then queue asynchronously on the device: the
     reliability order (decoders.py:320-325) and the elimination of every shot
@@ -741,12 +794,14 @@ def osd_device_stage(items, stream=None, slot0=0, order=0, method="ref"):
     by osd_device_finish. `slot0` selects the pinned buffer set (pipelined
     callers alternate). OSD_POLICY["host_order"] (A/B, or an unpinned NumPy)
     or n > 2048 sends every shot through the host order (osd_perms).
-    `method` as apply_osd_device's; osd_device_finish takes the same one."""
+    `method`, `cost`, `prior` (one row per item) and `eps` as
+    apply_osd_device_many's; osd_device_finish takes the same ones."""
     osd_method_checked(method, order)
+    rows = _item_priors(items, method, cost, prior)
     staged = []
     with _on_stream(stream):
-        for slot, (H, syn, res) in enumerate(items):
-            staged.append(_osd_stage_one(H, syn, res, slot0 + slot, order, method))
+        for slot, ((H, syn, res), row) in enumerate(zip(items, rows)):
+            staged.append(_osd_stage_one(H, syn, res, slot0 + slot, order, method, cost, row, eps))
     return staged
 
 
@@ -772,7 +827,7 @@ class _Staged:
     cap: int = 0
 
 
-def _osd_stage_one(H, syn, res, slot, order, method="ref"):
+def _osd_stage_one(H, syn, res, slot, order, method="ref", cost="hamming", prior=None, eps=1e-9):
     import torch
     if res.post is None:
         raise ValueError("apply_osd_device needs the decode's posteriors (want_post=True)")
@@ -791,6 +846,7 @@ def _osd_stage_one(H, syn, res, slot, order, method="ref"):
         return None
     OSD_STATS["osd_shots"] += k
     code = _lib.code_for(H, dev.index)
+    weights = _osd_prior_handle(code, cost, prior, eps)
     post_b = res.post.index_select(0, bad)
     syn_b = syn.index_select(0, bad)
     e_b = res.ehat.index_select(0, bad)
@@ -813,10 +869,11 @@ def _osd_stage_one(H, syn, res, slot, order, method="ref"):
         sp_idx = _device_buf(("spill_idx", slot), (cap,), torch.int32, dev)
         sp_cnt = _device_buf(("spill_cnt", slot), (1,), torch.int32, dev)
         sp_cnt.zero_()
-        ordered = _lib.lib.qldpc_osd_device_ordered_ex_cs if method == "cs" else _lib.lib.qldpc_osd_device_ordered_ex
+        ordered = (_lib.lib.qldpc_osd_device_ordered_ex_cs_prior if weights is not None else
+                   _lib.lib.qldpc_osd_device_ordered_ex_cs if method == "cs" else _lib.lib.qldpc_osd_device_ordered_ex)
         _lib.check(ordered(
-            code.handle, k, syn_b.data_ptr(), post_b.data_ptr(), int(order), e_b.data_ptr(),
-            status.data_ptr(), perm.data_ptr(), tie.data_ptr(), sp_post.data_ptr(), sp_idx.data_ptr(),
+            code.handle, k, syn_b.data_ptr(), post_b.data_ptr(), int(order),
+            *(() if weights is None else (weights,)), e_b.data_ptr(), status.data_ptr(), perm.data_ptr(), tie.data_ptr(), sp_post.data_ptr(), sp_idx.data_ptr(),
             sp_cnt.data_ptr(), cap, st))
         cnt_h = _pinned(("spill_cnt", slot), (1,), torch.int32)
         cnt_h.copy_(sp_cnt, non_blocking=True)
@@ -849,7 +906,8 @@ def _device_buf(key, shape, dtype, dev):
     return buf[:need].view(shape)
 
 
-def osd_device_finish(items, staged, order, stream=None, host=None, method="ref"):
+def osd_device_finish(items, staged, order, stream=None, host=None, method="ref", cost="hamming", prior=None,
+                      eps=1e-9):
     """Second half: for each staged decode, the shots the device order could
     not decide (status 2) get NumPy's reliability order on the host (their
     posteriors only, pinned copies) and the GPU elimination; then the
@@ -858,12 +916,13 @@ def osd_device_finish(items, staged, order, stream=None, host=None, method="ref"
     it (e.g. on a worker thread while the GPU ran the next batch); otherwise
     it runs here. res.osd_status keeps 0 / 1 per shot (1: the reference's
     IndexError case, raised by osd_status_check)."""
+    rows = _item_priors(items, method, cost, prior)
     if host is None:
         host = osd_host_orders(staged)
     with _on_stream(stream):
-        for (H, syn, res), sg, hr in zip(items, staged, host):
+        for (H, syn, res), sg, hr, row in zip(items, staged, host, rows):
             if sg is not None:
-                _osd_finish_device(H, syn, res, sg, hr, order, method)
+                _osd_finish_device(H, syn, res, sg, hr, order, method, cost, row, eps)
     return staged
 
 
@@ -925,7 +984,7 @@ def osd_host_orders(staged):
     return out
 
 
-def _osd_finish_device(H, syn, res, sg, hr, order, method="ref"):
+def _osd_finish_device(H, syn, res, sg, hr, order, method="ref", cost="hamming", prior=None, eps=1e-9):
     import torch
     e_b, status = sg.e_b, sg.status
     dev = res.ehat.device
@@ -941,9 +1000,11 @@ def _osd_finish_device(H, syn, res, sg, hr, order, method="ref"):
         e_r = e_b.index_select(0, idx)
         st2 = torch.empty(k2, dtype=torch.int32, device=dev)
         st = torch.cuda.current_stream(dev).cuda_stream
-        device = _lib.lib.qldpc_osd_device_cs if method == "cs" else _lib.lib.qldpc_osd_device
-        _lib.check(device(code.handle, k2, syn_r.data_ptr(), perms.data_ptr(), int(order), e_r.data_ptr(),
-                          st2.data_ptr(), st))
+        weights = _osd_prior_handle(code, cost, prior, eps)
+        device = (_lib.lib.qldpc_osd_device_cs_prior if weights is not None else
+                  _lib.lib.qldpc_osd_device_cs if method == "cs" else _lib.lib.qldpc_osd_device)
+        _lib.check(device(code.handle, k2, syn_r.data_ptr(), perms.data_ptr(), int(order),
+                          *(() if weights is None else (weights,)), e_r.data_ptr(), st2.data_ptr(), st))
         e_b.index_copy_(0, idx, e_r)
         status.index_copy_(0, idx, st2)
     res.ehat.index_copy_(0, sg.bad, e_b)
@@ -972,13 +1033,18 @@ def osd_status_raise(flags):
         raise IndexError("OSD: column basis search ran past the last column")
 
 
-def apply_osd(H, syn, ehat, post, flags, order, nthreads=None, method="ref"):
+def apply_osd(H, syn, ehat, post, flags, order, nthreads=None, method="ref", cost="hamming", prior=None, eps=1e-9):
     """OSD post-step for every non-converged row (decoders.py:179-180, :287-288).
 
     ehat (uint8 [B, n]) is updated in place. `method`: "ref", or "cs" for
-    OSD-CS with lambda = `order` (decode_batch's osd_method).
+    OSD-CS with lambda = `order` (decode_batch's osd_method); `cost`:
+    decode_batch's osd_cost, with "prior" the row `prior` (one probability per
+    column of H) and the `eps` of its LLRs.
     """
     osd_method_checked(method, order)
+    osd_cost_checked(cost, method, prior)
+    if cost == "prior":
+        _lib.code_for(H).prior(prior, eps)         # a bad row is refused whether or not a shot needs OSD
     idx = np.flatnonzero((np.asarray(flags) & _lib.FLAG_CONVERGED) == 0)
     if idx.size == 0:
         return ehat
@@ -988,8 +1054,11 @@ def apply_osd(H, syn, ehat, post, flags, order, nthreads=None, method="ref"):
     perms = np.ascontiguousarray(osd_perms(post[idx]), dtype=np.int32)
     sub_syn = np.ascontiguousarray(syn[idx], dtype=np.uint8)
     sub_e = np.ascontiguousarray(ehat[idx], dtype=np.uint8)
-    batch = _lib.lib.qldpc_osd_decode_batch_cs if method == "cs" else _lib.lib.qldpc_osd_decode_batch
-    _lib.check(batch(code.handle, idx.size, _lib.ptr(sub_syn), _lib.ptr(perms), int(order), _lib.ptr(sub_e),
+    weights = _osd_prior_handle(code, cost, prior, eps)
+    batch = (_lib.lib.qldpc_osd_decode_batch_cs_prior if weights is not None else
+             _lib.lib.qldpc_osd_decode_batch_cs if method == "cs" else _lib.lib.qldpc_osd_decode_batch)
+    _lib.check(batch(code.handle, idx.size, _lib.ptr(sub_syn), _lib.ptr(perms), int(order),
+                     *(() if weights is None else (weights,)), _lib.ptr(sub_e),
                      int(nthreads or hostcores.rank_cores())))
     ehat[idx] = sub_e
     return ehat
@@ -1012,47 +1081,51 @@ def _row(H, syndrome):
     return syndrome.reshape(1, m)
 
 
-def _soft(H, syndrome, p, max_iter, layers, algo, beta, eps, OSDorder, dtype, osd_method="ref"):
+def _soft(H, syndrome, p, max_iter, layers, algo, beta, eps, OSDorder, dtype, osd_method="ref", osd_cost="hamming"):
     """MS_decoder / BP_decoder of a non-empty shot: (e_hat of `dtype`, n_iter)."""
     row = _row(H, syndrome)
     if osd_method != "ref" or OSDorder >= 0:
         osd_method_checked(osd_method, OSDorder, algo)
+    vec = np.ndim(p) > 0
+    osd_cost_checked(osd_cost, osd_method, p if vec else None, "an array of n probabilities for p")
     if int(max_iter) < 1:
         # the reference's iteration loop never binds e_hat (decoders.py:153/:182)
         raise UnboundLocalError("local variable 'e_hat' referenced before assignment")
     lp, lr = pack_layers(layers, H.shape[0])
     # p may be an array of n probabilities, one per column (the reference
     # raises on max(array, eps) there: DESIGN.md §7)
-    vec = np.ndim(p) > 0
     r = decode_batch(H, row, None if vec else p, max_iter, algo=algo, beta=beta, eps=eps,
                      want_post=True, layer_ptr=lp, layer_rows=lr, prior=p if vec else None)
     e_hat = r.ehat[0].astype(dtype)
     if OSDorder >= 0 and not r.converged[0]:       # (:179-180, :287-288)
-        e_hat = OSDdec(H, e_hat, syndrome, r.post[0], OSDorder, **_method_kw("osd_method", osd_method))
+        e_hat = OSDdec(H, e_hat, syndrome, r.post[0], OSDorder, **_method_kw("osd_method", osd_method),
+                       **_cost_kw(osd_cost, p, eps, "osd_cost"))
     return e_hat, int(r.iters[0])
 
 
 def MS_decoder(H: np.ndarray, syndrome: np.ndarray, p: float, max_iter: int = 99,
                layers: Optional[list] = None, beta: float = 0.75, OSDorder: int = -1,
-               eps: float = 1e-9, osd_method: str = "ref"):
+               eps: float = 1e-9, osd_method: str = "ref", osd_cost: str = "hamming"):
     """Normalized min-sum (reference decoders.py:110-182) on the GPU.
-    osd_method="cs": OSD-CS with lambda = OSDorder (decode_batch)."""
+    osd_method="cs": OSD-CS with lambda = OSDorder (decode_batch);
+    osd_cost="prior" with it and an array for `p`: that row prices the candidates."""
     H, syndrome, bare = _shot(H, syndrome)
     if bare is not None:
         return bare
-    return _soft(H, syndrome, p, max_iter, layers, "MS", beta, eps, OSDorder, np.int8, osd_method)
+    return _soft(H, syndrome, p, max_iter, layers, "MS", beta, eps, OSDorder, np.int8, osd_method, osd_cost)
 
 
 def BP_decoder(H: np.ndarray, syndrome: np.ndarray, p: float, max_iter: int = 99,
                layers: Optional[list] = None, OSDorder: int = -1, eps: float = 1e-9,
-               osd_method: str = "ref"):
+               osd_method: str = "ref", osd_cost: str = "hamming"):
     """Sum-product BP (reference decoders.py:189-290) on the GPU.
-    osd_method="cs": OSD-CS with lambda = OSDorder (decode_batch)."""
+    osd_method="cs": OSD-CS with lambda = OSDorder (decode_batch);
+    osd_cost="prior" with it and an array for `p`: that row prices the candidates."""
     H, syndrome, bare = _shot(H, syndrome)
     if bare is not None:
         return bare
     # dtype int: (L_post < 0).astype(int) (:280)
-    return _soft(H, syndrome, p, max_iter, layers, "BP", 0.75, eps, OSDorder, int, osd_method)
+    return _soft(H, syndrome, p, max_iter, layers, "BP", 0.75, eps, OSDorder, int, osd_method, osd_cost)
 
 
 def Relay_decoder(H: np.ndarray, syndrome: np.ndarray, p: float, leg_iters, gammas, sols: int = 1,
@@ -1092,20 +1165,28 @@ def BF_decoder(H: np.ndarray, syndrome: np.ndarray, max_iter: int = 50):
 
 
 def OSDdec(H: np.ndarray, e_hat: np.ndarray, syndrome: np.ndarray, posteriorLLRs: np.ndarray,
-           order: int = 0, osd_method: str = "ref") -> np.ndarray:
+           order: int = 0, osd_method: str = "ref", osd_cost: str = "hamming", prior=None,
+           eps: float = 1e-9) -> np.ndarray:
     """OSD post-decoder (reference decoders.py:299-370), host C++ GF(2).
 
     Mutates and returns `e_hat`, like the reference's `e_hat[perm] = ...`.
-    osd_method="cs": OSD-CS with lambda = `order`.
+    osd_method="cs": OSD-CS with lambda = `order` (DESIGN.md §3.15);
+    osd_cost="prior" with it: the candidates are priced with the row `prior`
+    (one probability per column of H; `eps` as the decoders') instead of by
+    Hamming weight.
     """
     osd_method_checked(osd_method, order)
+    osd_cost_checked(osd_cost, osd_method, prior)
     H = np.asarray(H)
     m, n = H.shape
     perm = np.ascontiguousarray(osd_perm(posteriorLLRs), dtype=np.int32)
     syn = np.ascontiguousarray(np.asarray(syndrome) % 2, dtype=np.uint8)
     e = np.ascontiguousarray(np.asarray(e_hat) & 1, dtype=np.uint8)
     code = _lib.code_for(H)
-    if osd_method == "cs":
+    if osd_cost == "prior":
+        _lib.check(_lib.lib.qldpc_osd_decode_batch_cs_prior(code.handle, 1, _lib.ptr(syn), _lib.ptr(perm), int(order),
+                                                            code.prior(prior, eps).handle, _lib.ptr(e), 1))
+    elif osd_method == "cs":
         _lib.check(_lib.lib.qldpc_osd_decode_batch_cs(code.handle, 1, _lib.ptr(syn), _lib.ptr(perm), int(order),
                                                       _lib.ptr(e), 1))
     else:

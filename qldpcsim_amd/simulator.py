@@ -501,15 +501,17 @@ class _Decode(NamedTuple):
     kw: dict                     # the path's keywords (_path_kw)
     masked: tuple = None         # correlated: (p, p_masked) of the second half
     osd_method: str = "ref"      # "cs": OSD-CS with lambda = osd (decoders.decode_batch)
+    osd_cost: str = "hamming"    # "prior": OSD-CS prices candidates with each half's prior row
 
 
-def _path_kw(use_dev, osd, osd_method="ref"):
+def _path_kw(use_dev, osd, osd_method="ref", osd_cost="hamming"):
     """decode_batch's keywords of a shot path -> (packed, keywords). Device:
     bit-packed syndromes and estimates (one bit per check / qubit in HBM)
     unless OSD needs posteriors and byte rows of the failing shots, and OSD
     is the caller's step; host: decode_batch applies OSD itself."""
     packed = use_dev and osd < 0
-    host = {"osd_order": osd, **decoders._method_kw("osd_method", osd_method)}
+    host = {"osd_order": osd, **decoders._method_kw("osd_method", osd_method),
+            **({} if osd_cost == "hamming" else {"osd_cost": osd_cost})}
     return packed, ({"want_post": osd >= 0, "ehat_bits": packed} if use_dev else host)
 
 
@@ -521,6 +523,26 @@ def _osd_method(osd_method, OSDorder, decType):
         decoders.osd_method_checked(osd_method, OSDorder)
         raise ValueError(f'osd_method="{osd_method}" needs decType MS: {decType} shots get no OSD step')
     return decoders.osd_method_checked(osd_method, OSDorder)
+
+
+def _osd_cost(osd_cost, osd_method, rows):
+    """osd_cost of a run, checked before a shot is drawn: "hamming", or "prior"
+    with osd_method "cs" where every matrix that gets an OSD step decodes with a
+    prior row (`rows`: each one's row or None). A half that decodes with one
+    scalar prior has no row to weigh with: ValueError, as relay_cost="prior"."""
+    if osd_cost not in decoders.OSD_COSTS:
+        raise ValueError(f"osd_cost must be one of {decoders.OSD_COSTS}, got {osd_cost!r}")
+    if osd_cost == "prior":
+        decoders.osd_cost_checked(osd_cost, osd_method, True)
+        if any(r is None for r in rows):
+            raise ValueError('osd_cost="prior" weighs candidates by a prior row: this half decodes with one scalar '
+                             "prior (uniform marginals); unequal priors give it a row")
+    return osd_cost
+
+
+def _osd_cost_kw(dec, half):
+    """apply_osd_device's cost keywords for a half's OSD step (none with "hamming")."""
+    return decoders._cost_kw(dec.osd_cost, half.kw.get("prior"))
 
 
 def _relay_cost(cost, vector):
@@ -578,7 +600,7 @@ class _Plan(NamedTuple):
 
 
 def _plan(Hx, Hz, p, decType, decIterations, decSchedule, OSDorder, rngSeed, samples, sampler, logical, correlated,
-          correlated_q1, relay, channel_weights, osd_method="ref"):
+          correlated_q1, relay, channel_weights, osd_method="ref", osd_cost="hamming"):
     """simulate_p's argument checks, in the order they have always been made
     (all before a shot is drawn or the device is touched), and what they
     establish. `relay`: the six relay_* arguments by name."""
@@ -613,6 +635,7 @@ def _plan(Hx, Hz, p, decType, decIterations, decSchedule, OSDorder, rngSeed, sam
         _relay_cost(relay.get("cost"), bool(priors[1][1]))
     elif relay.get("priors") or relay.get("cost") is not None:
         raise ValueError("relay_priors and relay_cost go with decType RELAY")
+    _osd_cost(osd_cost, osd_method, [kw.get("prior") for _, kw in priors])
     if rngSeed is not None:
         np.random.seed(rngSeed)                    # reference side effect (:187-188); it refuses a bad seed here
     if Hz.size and Hz.shape[1] != n:
@@ -658,8 +681,8 @@ def _plan(Hx, Hz, p, decType, decIterations, decSchedule, OSDorder, rngSeed, sam
                          "with sampler='device' (which draws its own Philox shots)")
     use_dev = sampler == "device" or (sampler is None and samples is None and _device_ok()
                                       and _channel_ok(Hx, Hz))
-    dec = _Decode(decType, 50 if hard else decIterations, osd, *_path_kw(use_dev, osd, osd_method), masked,
-                  osd_method)
+    dec = _Decode(decType, 50 if hard else decIterations, osd, *_path_kw(use_dev, osd, osd_method, osd_cost), masked,
+                  osd_method, osd_cost)
     return _Plan(halves, (1, 0) if correlated == "ZX" else (0, 1), dec, probs, pair_logicals, use_dev)
 
 
@@ -731,6 +754,7 @@ def _pipelined_loop(ch, count, acc, plan, p, my_shots, batch_size, osd_flags, sh
     `osd_flags` collects the IndexError flags, checked once at the end."""
     Hz, Hx = plan.halves[0].H, plan.halves[1].H
     osd, method = plan.dec.osd, plan.dec.osd_method
+    cost = decoders._cost_kw(plan.dec.osd_cost, [h.kw.get("prior") for h in plan.halves])   # one row per half
     done = 0
     pending = None
     phase = 0
@@ -743,7 +767,7 @@ def _pipelined_loop(ch, count, acc, plan, p, my_shots, batch_size, osd_flags, sh
         orders to the worker thread."""
         nonlocal phase
         b.staged = decoders.osd_device_stage([(Hz, b.sy_z, b.rX), (Hx, b.sy_x, b.rZ)], slot0=2 * phase, order=osd,
-                                              method=method)
+                                              method=method, **cost)
         b.orders = _host_worker().submit(_host_orders_on, ch.dev, b.staged)
         phase ^= 1
 
@@ -775,7 +799,7 @@ def _pipelined_loop(ch, count, acc, plan, p, my_shots, batch_size, osd_flags, sh
             if osd >= 0:                               # (decoders.py:179-180), on the GPU
                 # the status-2 shots' NumPy orders were computed on the
                 # worker thread while the GPU decoded this batch
-                decoders.osd_device_finish(items, b.staged, osd, host=b.orders.result(), method=method)
+                decoders.osd_device_finish(items, b.staged, osd, host=b.orders.result(), method=method, **cost)
                 decoders.osd_status_check(items, defer=osd_flags)
             count(b.sy_z, b.sy_x, b.errX, b.errZ, b.rX.ehat, b.rZ.ehat, b.rX.iters, b.rZ.iters, acc)
         if cur is not None and osd >= 0 and cur.staged is None:
@@ -796,7 +820,8 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
                logical: bool = False, correlated: Optional[str] = None, correlated_q1: float = 0.49,
                relay_legs: int = 11, relay_leg_iters: int = 60, relay_sols: int = 1, relay_gamma0: float = 0.125,
                relay_gamma_range=(-0.24, 0.66), relay_seed: int = 0, channel_weights=None,
-               osd_method: str = "ref", relay_priors: bool = False, relay_cost: Optional[str] = None) -> dict:
+               osd_method: str = "ref", relay_priors: bool = False, relay_cost: Optional[str] = None,
+               osd_cost: str = "hamming") -> dict:
     """One depolarizing probability: sample, decode both halves, count.
 
     Returns the reference's dict (simulator.py:308-315). `samples`, if given,
@@ -809,7 +834,11 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
     order OSDorder; "cs" is OSD-CS, the combination sweep with lambda =
     OSDorder in 0..64, on the device and on the host path.
     "cs" with OSDorder < 0, with another decType, or an unknown method raises
-    ValueError.
+    ValueError. `osd_cost` (with "cs"): "hamming", or "prior" (DESIGN.md §3.19):
+    OSD-CS keeps the candidate of least prior weight, each half priced with its
+    own row of marginals (channel_weights). "prior" without "cs", and where a
+    half decodes with one scalar prior (no channel_weights, or equal marginals
+    on every qubit), raises ValueError before a shot is drawn.
 
     `logical` (extension): also test every residual against the pair's logical
     operators (count_logical_outcomes; on the device one counter kernel forms
@@ -867,7 +896,7 @@ def simulate_p(Hx: np.ndarray, Hz: np.ndarray, p: float, shots: int = 1000, decT
                  correlated, correlated_q1,
                  dict(legs=relay_legs, leg_iters=relay_leg_iters, sols=relay_sols, gamma0=relay_gamma0,
                       gamma_range=relay_gamma_range, seed=relay_seed, priors=bool(relay_priors), cost=relay_cost),
-                 channel_weights, osd_method)
+                 channel_weights, osd_method, osd_cost)
     osd = plan.dec.osd
     rank, my_shots, my_start, seed = _shard(shots, rngSeed)
     keys = COUNTER_KEYS + LOGICAL_KEYS if logical else COUNTER_KEYS
@@ -1106,7 +1135,7 @@ def _decode_windows(recs, s, wins, det, dec, use_dev):
         h = recs[w[1], w[2]]
         r = _decode_half(h, syn, dec)
         if use_dev and dec.osd >= 0:
-            decoders.apply_osd_device(h.H, syn, r, dec.osd, method=dec.osd_method)
+            decoders.apply_osd_device(h.H, syn, r, dec.osd, method=dec.osd_method, **_osd_cost_kw(dec, h))
         last = w
     s.advance(det, ehat, iters, last, r.ehat, r.iters, None)
     return ehat, iters
@@ -1117,7 +1146,8 @@ def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float
                               OSDorder: int = -1, rngSeed: Optional[int] = None, *,
                               batch_size: Optional[int] = None, sampler: Optional[str] = None,
                               verbose: bool = True, window: Optional[int] = None, commit: Optional[int] = None,
-                              osd_method: str = "ref", hbm_priors: bool = False, **unsupported) -> dict:
+                              osd_method: str = "ref", hbm_priors: bool = False, osd_cost: str = "hamming",
+                              **unsupported) -> dict:
     """Phenomenological noise (extension; no reference counterpart): `rounds`
     = T rounds of syndrome extraction with measurement error probability `q`,
     the last round measured perfectly, decoded over each half's space-time
@@ -1145,6 +1175,10 @@ def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float
     `osd_method` as in simulate_p ("cs": OSD-CS with lambda = OSDorder, on every
     window's decode too; on the device its limits are the block kernel's,
     m <= 512 and n <= 1087 of the matrix decoded, else NotImplementedError).
+    `osd_cost` as in simulate_p: "prior" prices every decode's OSD-CS, each
+    window's too, with the prior row of the matrix decoded; with p_data == q
+    (or a matrix of data columns alone) the decode takes one scalar prior and
+    "prior" raises ValueError before a shot is drawn.
     `sampler`: "device" (phenom_kernels.hip, the default with a device) or
     "host" (the NumPy twins in spacetime.py, drawn from
     np.random.default_rng([rngSeed, rank]), the X half first in every batch).
@@ -1186,7 +1220,7 @@ def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float
             return simulate_phenomenological(Hx, Hz, p, q, rounds, shots, decType, decIterations, decSchedule,
                                              OSDorder, rngSeed, batch_size=batch_size, sampler=sampler,
                                              verbose=verbose, window=window, commit=commit, osd_method=osd_method,
-                                             **unsupported)
+                                             osd_cost=osd_cost, **unsupported)
     for k_ in unsupported:
         if k_ in ("correlated", "channel_weights", "correlated_q1", "logical", "samples"):
             raise ValueError(f"simulate_phenomenological does not take {k_}=: the phenomenological model has "
@@ -1220,7 +1254,8 @@ def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float
     if batch_size is None:
         # posteriors (OSD) and byte rows cost 9 N bytes per half-shot
         batch_size = ((1 << 18) if osd < 0 else (1 << 14)) if use_dev else (1 << 14)
-    dec = _Decode(decType, decIterations, osd, *_path_kw(use_dev, osd, osd_method), osd_method=osd_method)
+    dec = _Decode(decType, decIterations, osd, *_path_kw(use_dev, osd, osd_method, osd_cost), osd_method=osd_method,
+                  osd_cost=osd_cost)
     # the matrices decoded: (rounds, closed) -> a _Half per CSS half. Without
     # window= (and with T <= W) that is the closed matrix of all T rounds
     kinds = sorted({(R, closed) for _, R, closed, _ in (wins or [(0, T, True, T)])})
@@ -1234,6 +1269,7 @@ def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float
             lp, lr = pack_layers(layers, Hw.shape[0])
             recs[R, closed] = _Half(Hw, lp, lr, *_half_prior(pr, False), (H, L))
         halves.append(recs)
+    _osd_cost(osd_cost, osd_method, [h.kw.get("prior") for recs in halves for h in recs.values()])
     sliding = wins is not None and len(wins) > 1
     show = _progress(f"(p={p:5.2e}, q={q:5.2e}, T={T})", my_shots, verbose and rank == 0)
     if use_dev:
@@ -1267,7 +1303,7 @@ def simulate_phenomenological(Hx: np.ndarray, Hz: np.ndarray, p: float, q: float
                 h = recs[kinds[0]]
                 r = _decode_half(h, det, dec)
                 if use_dev and osd >= 0:
-                    decoders.apply_osd_device(h.H, det, r, osd, method=osd_method)
+                    decoders.apply_osd_device(h.H, det, r, osd, method=osd_method, **_osd_cost_kw(dec, h))
                 ehat, iters = r.ehat, r.iters
             cls.append(s.count_device(det, E, ehat, iters, acc, want_class=True)[1])
         both += ((cls[0] | cls[1]) == 0).sum()
@@ -1398,7 +1434,7 @@ def simulate_dem(dem, shots: int = 1000, decType: str = "MS", decIterations: int
                  sampler: Optional[str] = None, verbose: bool = True, osd_method: str = "ref",
                  hbm_priors: bool = False, relay_priors: bool = False, relay_cost: Optional[str] = None,
                  relay_legs: int = 11, relay_leg_iters: int = 60, relay_sols: int = 1, relay_gamma0: float = 0.125,
-                 relay_gamma_range=(-0.24, 0.66), relay_seed: int = 0) -> dict:
+                 relay_gamma_range=(-0.24, 0.66), relay_seed: int = 0, osd_cost: str = "hamming") -> dict:
     """Monte-Carlo decoding of a detector error model (extension; no reference
     counterpart): `dem` is a dem.Dem (dem.load_dem reads Stim's .dem text).
     Each shot fires every mechanism independently with its own probability,
@@ -1418,7 +1454,9 @@ def simulate_dem(dem, shots: int = 1000, decType: str = "MS", decIterations: int
     instead of raising; a model within them decodes as without it. decSchedule "F", or "L" / "S" with
     layers from schedule.layerize(dem.H). OSDorder >= 0 applies to MS and to
     BP here (decoders.apply_osd_device on the device path, decoders.apply_osd
-    on the host), `osd_method` as in simulate_p. `sampler`: "device"
+    on the host), `osd_method` as in simulate_p; `osd_cost` "prior" (with "cs",
+    DESIGN.md §3.19) prices OSD-CS's candidates with the mechanisms' own
+    probabilities (ValueError where they are all equal). `sampler`: "device"
     (dem_kernels.hip, the default with a device; Philox key
     SeedSequence([rngSeed, rank]) as simulate_p) or "host" (dem.sample_dem
     from np.random.default_rng([rngSeed, rank])). With torch.distributed
@@ -1456,7 +1494,8 @@ def simulate_dem(dem, shots: int = 1000, decType: str = "MS", decIterations: int
     if _hbm_priors_checked(hbm_priors):
         with _lib.options(vprior_hbm=1):       # once around the run: an option change drops the cached launch plans
             return simulate_dem(dem, shots, decType, decIterations, decSchedule, OSDorder, rngSeed,
-                                batch_size=batch_size, sampler=sampler, verbose=verbose, osd_method=osd_method)
+                                batch_size=batch_size, sampler=sampler, verbose=verbose, osd_method=osd_method,
+                                osd_cost=osd_cost)
     if decType in _lib.HARD_ALGOS or (decType == "RELAY" and not relay_on):
         raise ValueError(f"decType {decType} is not available on detector error models (MS or BP)")
     if decType not in ("MS", "BP", "RELAY"):
@@ -1481,6 +1520,7 @@ def simulate_dem(dem, shots: int = 1000, decType: str = "MS", decIterations: int
         gammas[1:] = np.random.default_rng(relay_seed).uniform(lo, hi, (len(leg_iters) - 1, dem.num_errors))
         relay_kw = {"relay": _relay_config(leg_iters, gammas, relay_sols, kw_half.get("prior"), relay_cost)}
     decoders.osd_method_checked(osd_method, OSDorder, decType)
+    _osd_cost(osd_cost, osd_method, [_half_prior(dem.priors, False)[1].get("prior")])
     if sampler not in (None, "device", "host"):
         raise ValueError("sampler must be 'device', 'host' or None")
     if int(shots) < 0:
@@ -1490,7 +1530,8 @@ def simulate_dem(dem, shots: int = 1000, decType: str = "MS", decIterations: int
     use_dev = sampler == "device" or (sampler is None and _device_ok())
     if batch_size is None:
         batch_size = ((1 << 18) if osd < 0 else (1 << 14)) if use_dev else (1 << 14)
-    dec = _Decode(decType, decIterations, osd, *_path_kw(use_dev, osd, osd_method), osd_method=osd_method)
+    dec = _Decode(decType, decIterations, osd, *_path_kw(use_dev, osd, osd_method, osd_cost), osd_method=osd_method,
+                  osd_cost=osd_cost)
     layers = None if decSchedule == "F" else layerize(dem.H, serial=decSchedule == "S")
     if relay_on:                                   # the row, if any, travels in the RelayConfig
         half = _Half(dem.H, *pack_layers(layers, dem.num_detectors), p_half, relay_kw)
@@ -1518,7 +1559,7 @@ def simulate_dem(dem, shots: int = 1000, decType: str = "MS", decIterations: int
         det, obs = src.sample(B, bits=dec.packed)
         r = _decode_half(half, det, dec)
         if use_dev and osd >= 0:
-            decoders.apply_osd_device(half.H, det, r, osd, method=osd_method)
+            decoders.apply_osd_device(half.H, det, r, osd, method=osd_method, **_osd_cost_kw(dec, half))
         src.count_device(det, obs, r.ehat, r.iters, acc)
         done += B
         show(done)
@@ -1547,10 +1588,10 @@ def format_dem_results(name, r, shots):
 
 
 def _run_dem(path, shots, decType, decIterations, decSchedule, OSDorder, rngSeed, batch_size, sampler, resultsFile,
-             osd_method, hbm_priors=False, relay=None):
+             osd_method, hbm_priors=False, relay=None, osd_cost="hamming"):
     """The command line's --dem mode: load the model, simulate_dem, print the
     table; rank 0 writes the record (with the run's parameters; "hbm_priors"
-    only when set; `relay`, simulate_dem's relay_* keywords under
+    only when set; "osd_cost" only when it is "prior"; `relay`, simulate_dem's relay_* keywords under
     --relay-priors, only when given) to --results."""
     relay = dict(relay or {})
     from .dem import load_dem
@@ -1561,13 +1602,14 @@ def _run_dem(path, shots, decType, decIterations, decSchedule, OSDorder, rngSeed
     res = simulate_dem(dem, shots=shots, decType=decType, decIterations=decIterations, decSchedule=decSchedule,
                        OSDorder=OSDorder, rngSeed=rngSeed, batch_size=batch_size, sampler=sampler, verbose=True,
                        osd_method=osd_method, **({"hbm_priors": True} if _hbm_priors_checked(hbm_priors) else {}),
-                       **relay)
+                       **({"osd_cost": osd_cost} if osd_cost != "hamming" else {}), **relay)
     if rank == 0:
         print(format_dem_results(path, res, shots))
         if resultsFile:
             meta = {"dem": path, "shots": shots, "decType": decType, "decIterations": decIterations,
                     "decSchedule": decSchedule, "OSDorder": OSDorder, "rngSeed": rngSeed, "world": world,
                     "sampler": sampler, **decoders._method_kw("osd_method", osd_method),
+                    **({"osd_cost": osd_cost} if osd_cost != "hamming" else {}),
                     **({"hbm_priors": True} if hbm_priors else {}),
                     **{k: (list(v) if k == "relay_gamma_range" else v) for k, v in relay.items()}}
             import json
@@ -1657,7 +1699,8 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
              relay_gamma_range=(-0.24, 0.66), relay_seed: int = 0, bias: Optional[float] = None,
              channel_weights=None, rounds: Optional[int] = None, meas_error: Optional[float] = None,
              window: Optional[int] = None, commit: Optional[int] = None, osd_method: str = "ref",
-             hbm_priors: bool = False, relay_priors: bool = False, relay_cost: Optional[str] = None):
+             hbm_priors: bool = False, relay_priors: bool = False, relay_cost: Optional[str] = None,
+             osd_cost: str = "hamming"):
     """p-sweep + results table (simulator.py:319-347). Returns None like the
     reference unless return_results=True.
 
@@ -1700,7 +1743,10 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
     OSD method for every point, "ref" or "cs" (OSD-CS, lambda = OSDorder). A
     method other than "ref" enters the results file's meta as "osd_method" (a
     file without the key is a "ref" sweep), so a sweep is never resumed across
-    methods.
+    methods. osd_cost (with osd_method "cs"): simulate_p's /
+    simulate_phenomenological's cost for every point; "prior" enters the
+    results file's meta as "osd_cost" (a file without the key is a "hamming"
+    sweep) and is refused as there, before the first point runs.
 
     resultsFile (extension): a JSON file the sweep writes after every
     p-point; a rerun with the same arguments skips the points already there
@@ -1712,6 +1758,11 @@ def simulate(HxFile: str, HzFile: str, p, shots: int = 1000, decType: str = "MS"
     assert max(p) <= 1. and min(p) >= 0.
     _, rank, world = _dist()
     method = {} if _osd_method(osd_method, OSDorder, decType) == "ref" else {"osd_method": osd_method}
+    if osd_cost not in decoders.OSD_COSTS:
+        raise ValueError(f"osd_cost must be one of {decoders.OSD_COSTS}, got {osd_cost!r}")
+    if osd_cost == "prior":
+        decoders.osd_cost_checked(osd_cost, osd_method, True)
+        method["osd_cost"] = osd_cost
     if rounds is None and meas_error is not None:
         raise ValueError("meas_error needs rounds (the phenomenological model)")
     if rounds is None and (window is not None or commit is not None):
@@ -1863,6 +1914,11 @@ def main(argv=None):
     parser.add_argument("--osd-method", dest="osd_method", choices=["ref", "cs"], default="ref",
                         help="OSD method (decType MS): ref = the reference's OSDdec of order --OSDorder; cs = OSD-CS, "
                              "the combination sweep with lambda = --OSDorder (0..64).")
+    # (argparse.SUPPRESS: without the flag the printed namespace is what it was)
+    parser.add_argument("--osd-cost", dest="osd_cost", choices=["hamming", "prior"], default=argparse.SUPPRESS,
+                        help="With --osd-method cs: what OSD-CS minimises, the Hamming weight (default) or the prior "
+                             "weight under the decode's per-column priors (--bias, --channel-weights, --rounds with "
+                             "--meas-error, --dem).")
     parser.add_argument("--batch", type=int, default=None,
                         help="Shots per batch (default on the GPU: 2^20 without OSD, 2^18 with OSD; "
                              "2^16 on the host path).")
@@ -1907,6 +1963,9 @@ def main(argv=None):
                              "size, min-sum rows of more than 32 entries, state past the LDS) with the HBM-resident "
                              "per-variable-prior kernel instead of refusing them.")
     args = parser.parse_args(argv)
+    osd_cost = getattr(args, "osd_cost", "hamming")
+    if osd_cost == "prior" and args.osd_method != "cs":
+        parser.error("--osd-cost prior needs --osd-method cs")
     relay_priors = getattr(args, "relay_priors", False)
     if hasattr(args, "relay_cost") and not relay_priors:
         parser.error("--relay-cost needs --relay-priors")
@@ -1937,7 +1996,7 @@ def main(argv=None):
         try:
             _run_dem(dem_file, args.shots, args.decType, args.decIterations, args.decSchedule, args.OSDorder,
                      args.rngSeed, args.batch, args.sampler, args.results, args.osd_method,
-                     hbm_priors=getattr(args, "hbm_priors", False),
+                     hbm_priors=getattr(args, "hbm_priors", False), osd_cost=osd_cost,
                      relay=({**{k: getattr(args, k) for k in relay_names}, "relay_priors": True,
                              "relay_cost": getattr(args, "relay_cost", None)} if relay_priors else None))
         finally:
@@ -1988,6 +2047,7 @@ def main(argv=None):
                  **({"window": window, "commit": commit} if window is not None else {}),
                  **({"hbm_priors": True} if getattr(args, "hbm_priors", False) else {}),
                  **({"osd_method": args.osd_method} if args.osd_method != "ref" else {}),
+                 **({"osd_cost": osd_cost} if osd_cost != "hamming" else {}),
                  **({k: getattr(args, k) for k in relay_names} if args.decType == "RELAY" else {}),
                  **({"relay_priors": True, "relay_cost": getattr(args, "relay_cost", None)} if relay_priors else {}))
     finally:
