@@ -341,15 +341,15 @@ static int build_plan(qldpc_schedule* s, int algo, PlanKind kind, LaunchPlan* p)
         algo, c->max_row_deg, &p->name);
     p->waves = p->blocks_per_cu = p->lds = p->team = 0;
     plan_static_hbm(s, &p->hargs);
-    if (kind == PLAN_VPRIOR && algo == QLDPC_ALGO_BP && c->max_col_deg > 128) {
+    if (algo == QLDPC_ALGO_BP && c->max_col_deg > 128) {
       // np.sum splits a column of more than 128 entries: one pending sum per
-      // level and lane, for the deepest column the code has
+      // level and lane, for the deepest column the code has (both kernels)
       int depth = 0;
       for (int v = 0; v < c->n; ++v) depth = std::max(depth, qldpc::hbm_column_depth(c->csc_ptr[v + 1] - c->csc_ptr[v]));
       p->hbm_lds = qldpc::hbm_vprior_lds(depth);
       if (p->hbm_lds > (size_t)max_lds / 2)
-        return fail(QLDPC_EUNSUP, "%s: BP column degree %d needs %zu B of LDS for its column sums", twin_name(kind),
-                    c->max_col_deg, p->hbm_lds);
+        return fail(QLDPC_EUNSUP, "%s: BP column degree %d needs %zu B of LDS for its column sums",
+                    kind == PLAN_SCALAR ? "HBM decode" : twin_name(kind), c->max_col_deg, p->hbm_lds);
       HIP_TRY(qldpc::configure_kernel(p->kernel, max_lds / 2));   // (beside 6.4 KB of static LDS)
     }
     int per_cu = 0;                                  // resident tiles at the kernel's register use
@@ -530,7 +530,8 @@ static int decode_hbm(const qldpc_code* code, qldpc_schedule* s, int algo, const
     HIP_TRY(qldpc::launch_hbm_vprior(plan.kernel, a, qldpc::HbmPrior{vp->d_L, vp->filt0}, (int)tiles, s->d_h_fl_var,
                                      s->d_h_fl_pos, s->hbm_lazy ? 1 : 0, plan.hbm_lds, q.st));
   else
-    HIP_TRY(qldpc::launch_hbm(plan.kernel, a, (int)tiles, s->d_h_fl_var, s->d_h_fl_pos, s->hbm_lazy ? 1 : 0, q.st));
+    HIP_TRY(qldpc::launch_hbm(plan.kernel, a, (int)tiles, s->d_h_fl_var, s->d_h_fl_pos, s->hbm_lazy ? 1 : 0,
+                              plan.hbm_lds, q.st));
   if (int rc = timing_end(&t, q.st)) return rc;
   HIP_TRY(hipEventRecord(s->hbm_ev, q.st));
   return QLDPC_OK;

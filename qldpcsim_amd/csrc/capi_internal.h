@@ -153,7 +153,7 @@ struct LaunchPlan {
   qldpc::DecodeArgs args{};  // every static field filled (LDS kernels)
   qldpc::HbmArgs hargs{};    // the same for hbm_tile_kernel
   int hbm_tiles_cap = 0;    // CUs x resident 64-slot tiles per CU
-  size_t hbm_lds = 0;       // hbm_tile_vprior_kernel, BP: dynamic LDS bytes (qldpc::hbm_vprior_lds; 0 up to 128 entries per column)
+  size_t hbm_lds = 0;       // hbm_tile_kernel / hbm_tile_vprior_kernel, BP: dynamic LDS bytes (qldpc::hbm_vprior_lds; 0 up to 128 entries per column)
   uint32_t gen = 0;         // g_opt.gen the plan was built under
   bool ok = false;
 };

@@ -61,12 +61,13 @@ const void* select_hbm_kernel(int algo, int dcmax, const char** name);
 // hbm_tile_vprior_kernel<algo, D, 4>, chosen by the row degree in the same way
 const void* select_hbm_vprior_kernel(int algo, int dcmax, const char** name);
 // fl_var / fl_pos: first layer reaching each variable / CSC position; lazy =
-// the layers partition the rows (no state initialisation pass)
+// the layers partition the rows (no state initialisation pass); lds: the
+// plan's hbm_vprior_lds (BP with a column past 128 entries; else 0)
 hipError_t launch_hbm(const void* kernel, const HbmArgs& a, int tiles, const int32_t* fl_var, const int32_t* fl_pos,
-                      int lazy, hipStream_t stream);
+                      int lazy, size_t lds, hipStream_t stream);
 // NumPy's pairwise summation splits a column of more than 128 entries in two,
-// again and again: the levels below the root for d entries (0 up to 128). BP's
-// hbm_tile_vprior_kernel keeps one pending sum per level and lane in dynamic
+// again and again: the levels below the root for d entries (0 up to 128). The
+// BP instances of both kernels keep one pending sum per level and lane in dynamic
 // LDS, hbm_vprior_lds(deepest column of the code) bytes (0 for most codes).
 inline int hbm_column_depth(int d) {
   if (d <= 128) return 0;

@@ -77,17 +77,17 @@ __device__ __forceinline__ T tb(const T* p, int i) {
   return ((const __attribute__((address_space(4))) T*)p)[i];
 }
 
-// np.sum of a column of more than 128 entries, hbm_tile_vprior_kernel's: there
-// DOUBLE_pairwise_sum halves the range (the left half a multiple of 8) and adds
-// the halves' sums; a leaf of 65..128 entries is the 8-accumulator block.
+// np.sum of a column of more than 128 entries, for the BP instances of
+// hbm_tile_kernel and hbm_tile_vprior_kernel alike: there DOUBLE_pairwise_sum
+// halves the range (the left half a multiple of 8) and adds the halves' sums;
+// a leaf of 64..128 entries is the 8-accumulator block.
 // Walked leaf by leaf, left to right: the node in hand is a depth and a word of
 // turns (bit k: right at depth k), its range found again from the root each
 // time (uniform scalar work: d is the wave's), and the one per-lane state is
 // the sum of the left sibling pending at each depth: stack[(k - 1) * stride],
 // k = 1 .. hbm_column_depth(d), in the launch's dynamic LDS (hbm_kernels.h).
-// (hbm_tile_kernel keeps np_pairwise_strided at every degree: it runs the 8
-// accumulators over the whole column and so leaves NumPy's association above
-// 128 entries.)
+// (np_pairwise_strided above runs the 8 accumulators over the whole column: it
+// is NumPy's association up to 128 entries and is called for those alone.)
 template <typename Get>
 __device__ __forceinline__ double np_pairwise_deep(int d, Get get, double* stack, int stride) {
   uint32_t turns = 0;
@@ -193,9 +193,9 @@ const void* select_hbm_vprior_kernel(int algo, int dcmax, const char** name) {
 #undef QLDPC_HBM_VP
 
 hipError_t launch_hbm(const void* kernel, const HbmArgs& a, int tiles, const int32_t* fl_var, const int32_t* fl_pos,
-                      int lazy, hipStream_t stream) {
+                      int lazy, size_t lds, hipStream_t stream) {
   void* params[] = {(void*)&a, (void*)&fl_var, (void*)&fl_pos, (void*)&lazy};
-  return hipLaunchKernel(kernel, dim3(tiles), dim3(64 * kHbmWaves), params, 0, stream);
+  return hipLaunchKernel(kernel, dim3(tiles), dim3(64 * kHbmWaves), params, lds, stream);
 }
 
 hipError_t launch_hbm_vprior(const void* kernel, const HbmArgs& a, const HbmPrior& pr, int tiles, const int32_t* fl_var,

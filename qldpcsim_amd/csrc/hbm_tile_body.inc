@@ -292,9 +292,7 @@
       if (__ballot(act)) {
         for (int qb = v0 + wave * UV; qb < v1; qb += W * UV) {
           int vv[UV], p0[UV], dg[UV];
-#if QLDPC_HBM_VPRIOR
-          uint32_t wide = 0;                            // BP: columns past 128 entries, summed behind this step
-#endif
+          [[maybe_unused]] uint32_t wide = 0;           // BP: columns past 128 entries, summed behind this step
           double old[UV];
           Msg cv[UV][KV];
           Post ro[UV];
@@ -349,19 +347,16 @@
                 }
                 nw = d == 0 ? QLDPC_HBM_L(vv[u]) : QLDPC_HBM_L(vv[u]) + (0.0 + r);   // (:269, :276; no edges: L0, :277-278)
               } else {
-#if QLDPC_HBM_VPRIOR
                 if (d > 128) {                             // (uniform) NumPy splits the column: below
                   wide |= 1u << u;
                   continue;
                 }
-#endif
                 nw = QLDPC_HBM_L(vv[u]) + np_pairwise_strided(d, get);
               }
               POST(vv[u]) = nw;
             }
             if ((old[u] < 0.0) != (nw < 0.0)) Fp ^= tb(a.avar, vv[u]);   // hard decision flipped
           }
-#if QLDPC_HBM_VPRIOR
           if constexpr (ALGO == ALGO_BP) {
             // The step's columns of more than 128 entries, one at a time and
             // from memory alone (their posterior is still the old one): a cold
@@ -388,7 +383,6 @@
               }
             }
           }
-#endif
         }
       }
       // filters of every wave's flips; the barrier inside also publishes the

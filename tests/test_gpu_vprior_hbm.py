@@ -10,6 +10,7 @@ import pytest
 
 import dem_model as dm
 import prior_model as pm
+from wide_column_model import bp_flood_numpy as _bp_flood_numpy   # (the NumPy loop this file held)
 from qldpcsim_amd import _lib, codes, decoders, simulator
 
 pytestmark = pytest.mark.gpu
@@ -228,43 +229,6 @@ def test_more_than_65535_edges(qopt):
     assert _name(H, None, "MS") == NAME % (0, 64)
     got = _np(_decode(H, decoders.pack_bits(_dev(syn)), 4, "MS", None, q, ehat_bits=True), n)
     _same(got, pm.decode("MS", H, syn, np.broadcast_to(_llr(q), (B, n)), 4), "against the model")
-
-
-def _bp_flood_numpy(H, syn, L, max_iter, eps=1e-9):
-    """The reference's flooding BP with L_j per variable, shot by shot, every
-    column summed with np.sum on a contiguous float64 vector (NumPy's pairwise
-    summation at any length). -> (ehat, iters, post)."""
-    m, n = H.shape
-    rows = [np.flatnonzero(H[c]) for c in range(m)]
-    cols = [np.flatnonzero(H[:, j]) for j in range(n)]
-    out_e, out_it, out_p = [], [], []
-    for s in syn:
-        c2v = np.zeros((m, n))
-        post = L.copy()
-        iters = max_iter
-        for it in range(max_iter):
-            new = np.zeros((m, n))
-            for c in range(m):
-                t = np.tanh((post[rows[c]] - c2v[c, rows[c]]) / 2.0)
-                prod = np.float64(1.0)
-                for x in t:
-                    prod = prod * x
-                for k, j in enumerate(rows[c]):
-                    th2 = prod / t[k]
-                    if np.abs(th2) >= 1 - eps:
-                        th2 = th2 - eps * np.sign(th2)
-                    val = 2 * np.arctanh(th2)
-                    new[c, j] = -val if s[c] else val
-            c2v = new
-            for j in range(n):
-                post[j] = L[j] + np.sum(np.ascontiguousarray(c2v[cols[j], j])) if len(cols[j]) else L[j]
-            if np.array_equal((H.astype(np.int64) @ (post < 0)) % 2, s):
-                iters = it + 1
-                break
-        out_e.append((post < 0).astype(np.uint8))
-        out_it.append(iters)
-        out_p.append(post.copy())
-    return np.array(out_e), np.array(out_it, np.int32), np.array(out_p)
 
 
 def test_bp_column_of_129_entries(qopt):
