@@ -1,11 +1,13 @@
-// capi_decode.cpp — launch plans, the decode entry points, launch timing, the
-// HBM-resident path and the host staging entry point.
+// capi_decode.cpp — the soft decoders (MS, BP): kernel choice, LDS layouts and
+// launch plans, the decode entry points (scalar, two-level and per-variable
+// priors; device and host buffers) and the HBM-resident path. The plumbing
+// shared with the other families is in capi_launch.h.
 
 #include <cmath>
 #include <cstdio>
 #include <memory>
 
-#include "capi_internal.h"
+#include "capi_launch.h"
 #include "../../include/qldpc_libm.h"   // after hip_runtime.h
 #include "qc_tables.h"
 #include "tuning.h"
@@ -158,14 +160,14 @@ KernelChoice capi::choose_kernel(const qldpc_schedule* s, int algo) {
 // what both prior twins of the generic LDS kernel refuse (`what` names the caller's feature)
 static int twin_limits(const qldpc_schedule* s, int algo, const char* what) {
   const qldpc_code* c = s->code;
-  if (!s->lds_ok)
+  const LdsLimit l = lds_limit(s->lds_ok, c, algo);
+  if (l == LDS_TABLES16)
     return fail(QLDPC_EUNSUP, "%s: %d x %d with %d edges is past the LDS kernels' 16-bit tables "
                 "(m, n, edges, layer rows <= 65535); there is no HBM-resident variant", what, c->m, c->n, c->E);
-  if (algo == QLDPC_ALGO_MS && c->max_row_deg > 32)
-    return fail(QLDPC_EUNSUP, "%s: MS row degree %d > 32 has no LDS kernel", what, c->max_row_deg);
-  if (algo == QLDPC_ALGO_BP && c->max_col_deg > 128)
+  if (l == LDS_MS_ROW_DEG) return fail(QLDPC_EUNSUP, "%s: MS row degree %d > 32 has no LDS kernel", what, c->max_row_deg);
+  if (l == LDS_BP_COL_DEG)
     return fail(QLDPC_EUNSUP, "%s: BP column degree %d > 128 has no LDS kernel", what, c->max_col_deg);
-  if (opt(&Options::force_hbm) != 0)
+  if (l == LDS_FORCE_HBM)
     return fail(QLDPC_EUNSUP, "%s: option force_hbm is set and there is no HBM-resident variant", what);
   return QLDPC_OK;
 }
@@ -177,12 +179,8 @@ static const char* twin_name(PlanKind kind) { return kind == PLAN_PRIOR ? "two-l
 // hbm_tile_vprior_kernel (the two-level twin has no HBM-resident variant)
 static bool vprior_hbm_on(PlanKind kind) { return kind == PLAN_VPRIOR && opt(&Options::vprior_hbm) != 0; }
 
-// twin_limits without the message: no LDS twin runs this (schedule, algo)
-static bool past_twin_limits(const qldpc_schedule* s, int algo) {
-  const qldpc_code* c = s->code;
-  return !s->lds_ok || (algo == QLDPC_ALGO_MS && c->max_row_deg > 32) ||
-         (algo == QLDPC_ALGO_BP && c->max_col_deg > 128) || opt(&Options::force_hbm) != 0;
-}
+// twin_limits without the message: no LDS kernel runs this (schedule, algo)
+static bool past_lds_limits(const qldpc_schedule* s, int algo) { return lds_limit(s->lds_ok, s->code, algo) != LDS_FITS; }
 
 uint32_t capi::prior_filter_word(const qldpc_code* c, const std::vector<double>& L) {
   uint32_t f = 0;
@@ -197,7 +195,7 @@ int capi::choose_twin_kernel(const qldpc_schedule* s, int algo, PlanKind kind, K
   *k = KernelChoice{};
   k->max_waves = QLDPC_MAX_THREADS / 64;
   k->kind = kind;
-  if (vprior_hbm_on(kind) && past_twin_limits(s, algo)) {
+  if (vprior_hbm_on(kind) && past_lds_limits(s, algo)) {
     k->hbm = true;
     k->kernel = qldpc::select_hbm_vprior_kernel(algo, c->max_row_deg, &k->name);
     return QLDPC_OK;
@@ -277,15 +275,12 @@ void capi::plan_static_hbm(const qldpc_schedule* s, qldpc::HbmArgs* a) {
 static int build_plan(qldpc_schedule* s, int algo, PlanKind kind, LaunchPlan* p) {
   const bool prior = kind != PLAN_SCALAR;             // a twin of the generic LDS kernel, or nothing
   const qldpc_code* c = s->code;
-  int dev = 0, max_lds = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  HIP_TRY(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-  HIP_TRY(hipDeviceGetAttribute(&p->cus, hipDeviceAttributeMultiprocessorCount, dev));
+  int max_lds = 0;
+  if (int rc = device_limits(&max_lds, &p->cus)) return rc;
   // The LDS-resident kernels when their tables and per-half-shot state fit,
   // else the HBM-resident kernel (hbm_kernels.hip). Option force_hbm takes the
   // HBM kernel for any code (tests: the two families agree bit for bit).
-  p->hbm = !s->lds_ok || opt(&Options::force_hbm) != 0 || (algo == QLDPC_ALGO_MS && c->max_row_deg > 32) ||
-           (algo == QLDPC_ALGO_BP && c->max_col_deg > 128);
+  p->hbm = past_lds_limits(s, algo);
   KernelChoice pk;
   if (prior) {
     if (int rc = choose_twin_kernel(s, algo, kind, &pk)) return rc;
@@ -297,41 +292,17 @@ static int build_plan(qldpc_schedule* s, int algo, PlanKind kind, LaunchPlan* p)
     p->hs_per_wave = k.family == FAM_MS_FLOOD_QC ? 4 : 1;
     const int image_lds = plan_static(s, algo, k, &p->args);
     HIP_TRY(qldpc::configure_kernel(k.kernel, max_lds));
-    int best_waves = 0, max_waves = k.max_waves;
-    auto occupancy = [&](int w, int lds, int* nb) {
-      return hipOccupancyMaxActiveBlocksPerMultiprocessor(nb, k.kernel, 64 * w, (size_t)lds);
-    };
-    auto take = [&](int w, int nb, int lds) { p->waves = w, p->blocks_per_cu = nb, p->lds = lds, best_waves = nb * w; };
-    if (k.team) {  // one team (workgroup of `team` waves) per half-shot
-      const int lds = plan_lds(algo, image_lds, k.team, k.team, &p->args);
-      int nb = 0;
-      if (lds <= max_lds) HIP_TRY(occupancy(k.team, lds, &nb));
-      take(k.team, nb, lds);
-      max_waves = 0;  // skip the wave-kernel search below
-    }
-    for (int w = max_waves; w >= 1; --w) {
-      const int lds = plan_lds(algo, image_lds, 0, w, &p->args);
-      if (lds > max_lds) continue;
-      int nb = 0;
-      HIP_TRY(occupancy(w, lds, &nb));
-      if (nb * w > best_waves) take(w, nb, lds);
-    }
-    // Tuning overrides (experiments only): options waves_per_wg, wg_per_cu.
-    if (const int64_t ow = k.team ? 0 : opt(&Options::waves_per_wg)) {
-      const int w = (int)ow;
-      const int lds = plan_lds(algo, image_lds, 0, w, &p->args);
-      int nb = 0;
-      if (w >= 1 && w <= max_waves && lds <= max_lds && occupancy(w, lds, &nb) == hipSuccess && nb > 0)
-        take(w, nb, lds);
-    }
-    if (const int64_t ok = opt(&Options::wg_per_cu)) {
-      const int k2 = (int)ok;
-      if (k2 >= 1 && k2 < p->blocks_per_cu) p->blocks_per_cu = k2;
-    }
-    (void)plan_lds(algo, image_lds, k.team, p->waves, &p->args);   // off_libm of the chosen width
+    auto lds_of = [&](int w) { return plan_lds(algo, image_lds, k.team, w, &p->args); };
+    // wave kernels: any width the kernel was compiled for; a team (one workgroup of `team` waves per
+    // half-shot) has that one width, so no search and no waves_per_wg, while wg_per_cu still applies
+    WaveChoice wc;
+    HIP_TRY(wave_search(k.team ? k.team : 1, k.team ? k.team : k.max_waves, max_lds, lds_of, occupancy_of(k.kernel), true,
+                        &wc));
+    p->waves = wc.waves, p->blocks_per_cu = wc.blocks_per_cu, p->lds = wc.lds;
+    (void)lds_of(p->waves);                           // off_libm of the chosen width
     // no LDS kernel holds the graph's per-half-shot state and tables: the
     // HBM-resident kernel decodes it; decided once per plan, not per launch
-    p->hbm = best_waves == 0;
+    p->hbm = wc.waves == 0;
     if (prior && p->hbm && !vprior_hbm_on(kind))
       return fail(QLDPC_EUNSUP, "%s: the tables and one wave's state (%d + %d B) do not fit the %d B "
                   "of LDS; there is no HBM-resident variant", twin_name(kind), image_lds, p->args.wave_bytes, max_lds);
@@ -359,109 +330,29 @@ static int build_plan(qldpc_schedule* s, int algo, PlanKind kind, LaunchPlan* p)
   return QLDPC_OK;
 }
 
-// The one validating way to a plan: copied into *out under the schedule's
-// lock, so a launch keeps its own consistent snapshot even if an option change
-// (qldpc_set_option) rebuilds the cached one meanwhile.
+// The one validating way to a plan (cached_plan, under the schedule's lock)
 static int resolve_plan(const qldpc_code* code, qldpc_schedule* s, int algo, LaunchPlan* out,
                         PlanKind kind = PLAN_SCALAR) {
   if (algo != QLDPC_ALGO_MS && algo != QLDPC_ALGO_BP) return fail(QLDPC_EINVAL, "Unrecognized decoder type.");
   if (code->device < 0 || !s->generic.dev)
     return fail(QLDPC_EHIP, "no HIP device was visible when the code/schedule was created");
-  std::lock_guard<std::mutex> lk(s->mu);
-  const uint32_t gen = g_opt.gen.load();
-  LaunchPlan& slot = s->plan[kind][algo];
-  if (!slot.ok || slot.gen != gen) {
-    LaunchPlan p{};                                   // built aside, published whole
-    const int rc = build_plan(s, algo, kind, &p);
-    if (rc) return rc;
-    p.ok = true;
-    p.gen = gen;
-    slot = p;
-  }
-  *out = slot;
-  return QLDPC_OK;
-}
-
-// ---------------------------------------------------------------------------
-// timing
-// ---------------------------------------------------------------------------
-static std::mutex g_tmu;
-static bool g_timing = false;
-static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_events;
-static double g_total_ms = 0.0;
-static int64_t g_launches = 0;
-
-extern "C" int qldpc_timing_enable(int on) {
-  std::lock_guard<std::mutex> lk(g_tmu);
-  g_timing = on != 0;
-  return QLDPC_OK;
-}
-
-static int drain_events_locked() {
-  for (auto& ev : g_events) {
-    HIP_TRY(hipEventSynchronize(ev.second));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev.first, ev.second));
-    g_total_ms += ms;
-    g_launches++;
-    (void)hipEventDestroy(ev.first);
-    (void)hipEventDestroy(ev.second);
-  }
-  g_events.clear();
-  return QLDPC_OK;
-}
-
-extern "C" int qldpc_timing_reset(void) {
-  std::lock_guard<std::mutex> lk(g_tmu);
-  int rc = drain_events_locked();
-  g_total_ms = 0.0;
-  g_launches = 0;
-  return rc;
-}
-
-extern "C" int qldpc_timing_read(double* total_ms, int64_t* launches) {
-  std::lock_guard<std::mutex> lk(g_tmu);
-  int rc = drain_events_locked();
-  if (total_ms) *total_ms = g_total_ms;
-  if (launches) *launches = g_launches;
-  return rc;
-}
-
-// A timed launch: timing_begin before the kernel is enqueued, timing_end
-// after. The event pair goes to g_events; drain_events_locked destroys it.
-int capi::timing_begin(TimedLaunch* t, hipStream_t st) {
-  {
-    std::lock_guard<std::mutex> lk(g_tmu);
-    if (!g_timing) return QLDPC_OK;
-  }
-  HIP_TRY(hipEventCreate(&t->e0));
-  HIP_TRY(hipEventCreate(&t->e1));
-  HIP_TRY(hipEventRecord(t->e0, st));
-  return QLDPC_OK;
-}
-
-int capi::timing_end(TimedLaunch* t, hipStream_t st) {
-  if (!t->e0) return QLDPC_OK;
-  HIP_TRY(hipEventRecord(t->e1, st));
-  std::lock_guard<std::mutex> lk(g_tmu);
-  g_events.emplace_back(t->e0, t->e1);
-  return QLDPC_OK;
+  return cached_plan(s->mu, s->plan[kind][algo], out, [&](LaunchPlan* p) { return build_plan(s, algo, kind, p); });
 }
 
 // ---------------------------------------------------------------------------
 // decode
 // ---------------------------------------------------------------------------
-struct DecodeCall {  // the per-call arguments of qldpc_decode_device_ex
-  const void* syn;
-  void* ehat;
-  int syn_format, ehat_format, max_iter;
-  int64_t batch;
-  double p, beta, eps;
-  int32_t *iters, *flags;
-  double* post;
+// One decode call's arguments, as qldpc_decode_device_ex lists them (host entries: host buffers in io, st unread)
+struct DecodeCall {
+  const qldpc_code* code;
+  const qldpc_schedule* sched;
+  int algo;
+  CallIO io;
+  double p;
+  int max_iter;
+  double beta, eps;
   hipStream_t st;
 };
-
 // hbm_tile_kernel's workspace for t tiles of 64 half-shot slots
 struct HbmLayout { size_t off_post, off_syn, bytes; };
 static HbmLayout hbm_layout(const qldpc_code* c, size_t w, int64_t t) {
@@ -478,13 +369,13 @@ static HbmLayout hbm_layout(const qldpc_code* c, size_t w, int64_t t) {
 // workspace belongs to the schedule and an event orders launches that share it.
 // With `vp` (hbm_tile_vprior_kernel) the priors come from the handle's row and
 // its filter word; q.p is unread.
-static int decode_hbm(const qldpc_code* code, qldpc_schedule* s, int algo, const LaunchPlan& plan,
-                      const DecodeCall& q, const qldpc_prior* vp) {
+static int decode_hbm(qldpc_schedule* s, const LaunchPlan& plan, const DecodeCall& q, const qldpc_prior* vp) {
+  const qldpc_code* code = q.code;
   if (vp && !vp->d_L.p) return fail(QLDPC_EHIP, "no HIP device was visible when the prior handle was created");
-  const size_t w = algo == QLDPC_ALGO_MS ? 4 : 8;   // message / posterior row element (MS: f32 S)
+  const size_t w = q.algo == QLDPC_ALGO_MS ? 4 : 8;   // message / posterior row element (MS: f32 S)
   const size_t per_tile = ((size_t)code->E * w + (size_t)code->n * w + (size_t)code->m) * 64;
   std::lock_guard<std::mutex> lk(s->mu);
-  int64_t tiles = std::min<int64_t>((q.batch + 63) / 64, (int64_t)plan.hbm_tiles_cap);
+  int64_t tiles = std::min<int64_t>((q.io.batch + 63) / 64, (int64_t)plan.hbm_tiles_cap);
   // the workspace those tiles need; grown (never shrunk: qldpc_schedule_release_workspace
   // frees it) within half of the free device memory, at most 64 GiB
   if (hbm_layout(code, w, tiles).bytes > s->hbm_ws_bytes) {
@@ -511,11 +402,10 @@ static int decode_hbm(const qldpc_code* code, qldpc_schedule* s, int algo, const
   a.c2v = s->hbm_ws;
   a.post = (char*)s->hbm_ws + lay.off_post;
   a.synT = (uint8_t*)s->hbm_ws + lay.off_syn;
-  a.syn = (const uint8_t*)q.syn, a.ehat = (uint8_t*)q.ehat;
-  a.iters = q.iters, a.out_post = q.post, a.flags = q.flags;
-  a.syn_bits = q.syn_format == QLDPC_FMT_BITS, a.eh_bits = q.ehat_format == QLDPC_FMT_BITS;
-  a.batch = q.batch;
-  a.queue = s->d_queue + (s->qnext.fetch_add(1) % qldpc_schedule::kQueueSlots);
+  a.syn = (const uint8_t*)q.io.syn, a.ehat = (uint8_t*)q.io.ehat;
+  a.iters = q.io.iters, a.out_post = q.io.post, a.flags = q.io.flags;
+  a.syn_bits = q.io.syn_format == QLDPC_FMT_BITS, a.eh_bits = q.io.ehat_format == QLDPC_FMT_BITS;
+  a.batch = q.io.batch;
   if (vp) {
     a.L = 0.0, a.L32 = 0.0f;                        // (unread: every prior comes from the handle's row)
   } else {
@@ -523,7 +413,7 @@ static int decode_hbm(const qldpc_code* code, qldpc_schedule* s, int algo, const
     a.L32 = (float)a.L;
   }
   a.beta = q.beta, a.eps = q.eps, a.max_iter = q.max_iter;
-  HIP_TRY(hipMemsetAsync(a.queue, 0, sizeof(uint32_t), q.st));
+  if (int rc = s->queue.claim(q.st, &a.queue)) return rc;   // (always: this kernel has no static schedule)
   TimedLaunch t;
   if (int rc = timing_begin(&t, q.st)) return rc;
   if (vp)
@@ -596,52 +486,41 @@ static int validate_twin(const qldpc_code* code, const qldpc_schedule* sched, in
 
 // The device-free checks of a decode call, in the order decode_device reports
 // them (decode_host makes them before its staging copies where it can)
-static int validate_call(const qldpc_code* code, const qldpc_schedule* sched, int algo, int syn_format,
-                         int ehat_format, int64_t batch, double p, int max_iter, const PriorCall* pr,
-                         const qldpc_prior* vp) {
-  if ((syn_format != QLDPC_FMT_BYTES && syn_format != QLDPC_FMT_BITS) ||
-      (ehat_format != QLDPC_FMT_BYTES && ehat_format != QLDPC_FMT_BITS))
+static int validate_call(const DecodeCall& q, const PriorCall* pr, const qldpc_prior* vp) {
+  if ((q.io.syn_format != QLDPC_FMT_BYTES && q.io.syn_format != QLDPC_FMT_BITS) ||
+      (q.io.ehat_format != QLDPC_FMT_BYTES && q.io.ehat_format != QLDPC_FMT_BITS))
     return fail(QLDPC_EINVAL, "unknown syndrome / estimate format");
-  if (!code || !sched) return fail(QLDPC_EINVAL, "code/schedule is null");
-  if (sched->code != code) return fail(QLDPC_EINVAL, "schedule was built for a different code");
-  if (algo != QLDPC_ALGO_MS && algo != QLDPC_ALGO_BP) return fail(QLDPC_EINVAL, "Unrecognized decoder type.");
-  if (batch < 0) return fail(QLDPC_EINVAL, "negative batch");
-  if (max_iter < 1) return fail(QLDPC_EINVAL, "max_iter must be >= 1 (the reference leaves e_hat unbound)");
-  return validate_twin(code, sched, algo, batch, p, pr, vp);
+  if (!q.code || !q.sched) return fail(QLDPC_EINVAL, "code/schedule is null");
+  if (q.sched->code != q.code) return fail(QLDPC_EINVAL, "schedule was built for a different code");
+  if (q.algo != QLDPC_ALGO_MS && q.algo != QLDPC_ALGO_BP) return fail(QLDPC_EINVAL, "Unrecognized decoder type.");
+  if (q.io.batch < 0) return fail(QLDPC_EINVAL, "negative batch");
+  if (q.max_iter < 1) return fail(QLDPC_EINVAL, "max_iter must be >= 1 (the reference leaves e_hat unbound)");
+  return validate_twin(q.code, q.sched, q.algo, q.io.batch, q.p, pr, vp);
 }
 
-static int decode_device(const qldpc_code* code, const qldpc_schedule* sched_c, int algo,
-                         const void* d_syn, int syn_format, int64_t batch, double p, int max_iter,
-                         double beta, double eps, void* d_ehat, int ehat_format, int32_t* d_iters,
-                         double* d_post, int32_t* d_flags, void* stream, const PriorCall* pr,
-                         const qldpc_prior* vp = nullptr) {
-  auto* sched = const_cast<qldpc_schedule*>(sched_c);
-  if (int rc = validate_call(code, sched, algo, syn_format, ehat_format, batch, p, max_iter, pr, vp)) return rc;
-  if (batch == 0) return QLDPC_OK;
-  if (!d_syn || !d_ehat || !d_iters) return fail(QLDPC_EINVAL, "null device buffer");
+static int decode_device(const DecodeCall& q, const PriorCall* pr, const qldpc_prior* vp = nullptr) {
+  if (int rc = validate_call(q, pr, vp)) return rc;
+  const qldpc_code* code = q.code;
+  auto* sched = const_cast<qldpc_schedule*>(q.sched);
+  const double eps = q.eps;
+  if (q.io.batch == 0) return QLDPC_OK;
+  if (!q.io.syn || !q.io.ehat || !q.io.iters) return fail(QLDPC_EINVAL, "null device buffer");
   if (code->device < 0 || !sched->generic.dev)
     return fail(QLDPC_EHIP, "no HIP device was visible when the code/schedule was created");
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
   if (dev != code->device) return fail(QLDPC_EINVAL, "code lives on device %d, current device is %d", code->device, dev);
   LaunchPlan plan;
-  if (int rc = resolve_plan(code, sched, algo, &plan, kind_of(pr, vp))) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (plan.hbm)
-    return decode_hbm(code, sched, algo, plan,
-                      DecodeCall{d_syn, d_ehat, syn_format, ehat_format, max_iter, batch, p, beta, eps, d_iters,
-                                 d_flags, d_post, st},
-                      vp);
+  if (int rc = resolve_plan(code, sched, q.algo, &plan, kind_of(pr, vp))) return rc;
+  hipStream_t st = q.st;
+  if (plan.hbm) return decode_hbm(sched, plan, q, vp);
 
   DecodeArgs a = plan.args;
-  a.syn = (const uint8_t*)d_syn, a.ehat = (uint8_t*)d_ehat;
-  a.syn_bits = syn_format == QLDPC_FMT_BITS, a.eh_bits = ehat_format == QLDPC_FMT_BITS;
-  a.iters = d_iters, a.post = d_post, a.flags = d_flags;
-  a.batch = batch;
+  set_call_io(&a, q.io);
   // L_ch = np.log((1 - p) / max(p, eps))   (decoders.py:147, :232), with
   // NumPy's own log (SVML log8_ha, include/qldpc_libm.h): glibc's differs in
   // the last bit for ~0.2 % of priors
-  a.L = qldpc_prior_llr(p, eps);
+  a.L = qldpc_prior_llr(q.p, eps);
   a.L32 = (float)a.L;
   if (pr) {
     a.L1 = qldpc_prior_llr(pr->p1, eps);
@@ -653,9 +532,9 @@ static int decode_device(const qldpc_code* code, const qldpc_schedule* sched_c, 
     a.vprior = vp->d_L;
     a.L = 0.0, a.L32 = 0.0f;                          // (unread: every prior comes from the row)
   }
-  a.beta = beta, a.eps = eps;
+  a.beta = q.beta, a.eps = eps;
   bp_saturation(eps, &a.bp_csat, &a.bp_sat_hi);
-  a.max_iter = max_iter;
+  a.max_iter = q.max_iter;
   {
     // (L + (double)S < 0) == (S < hd_thresh) for every float S: the float at
     // or below -L, nudged up one step when -L is not a float
@@ -665,14 +544,10 @@ static int decode_device(const qldpc_code* code, const qldpc_schedule* sched_c, 
     a.hd_thresh = ((double)f == t) ? f : std::nextafter(f, INFINITY);
   }
   a.queue = nullptr;
-  if (!opt(&Options::static_sched)) {
-    a.queue = sched->d_queue + (sched->qnext.fetch_add(1) % qldpc_schedule::kQueueSlots);
-    HIP_TRY(hipMemsetAsync(a.queue, 0, sizeof(uint32_t), st));
-  }
-  const int64_t per_block = plan.team ? 1 : (int64_t)plan.waves * plan.hs_per_wave;
-  const int64_t need = (batch + per_block - 1) / per_block;
-  const int64_t resident = (int64_t)plan.blocks_per_cu * plan.cus;
-  const int grid = (int)std::max<int64_t>(1, std::min(need, resident));
+  if (!opt(&Options::static_sched))
+    if (int rc = sched->queue.claim(st, &a.queue)) return rc;
+  const int grid = launch_grid(q.io.batch, plan.team ? 1 : (int64_t)plan.waves * plan.hs_per_wave, plan.blocks_per_cu,
+                               plan.cus);
   TimedLaunch t;
   if (int rc = timing_begin(&t, st)) return rc;
   HIP_TRY(qldpc::launch_decode(plan.kernel, a, grid, 64 * plan.waves, plan.lds, st));
@@ -683,8 +558,9 @@ extern "C" int qldpc_decode_device_ex(const qldpc_code* code, const qldpc_schedu
                                       const void* d_syn, int syn_format, int64_t batch, double p, int max_iter,
                                       double beta, double eps, void* d_ehat, int ehat_format, int32_t* d_iters,
                                       double* d_post, int32_t* d_flags, void* stream) {
-  return decode_device(code, sched, algo, d_syn, syn_format, batch, p, max_iter, beta, eps, d_ehat, ehat_format,
-                       d_iters, d_post, d_flags, stream, nullptr);
+  const DecodeCall q{code, sched, algo, {d_syn, syn_format, batch, d_ehat, ehat_format, d_iters, d_flags, d_post}, p,
+                     max_iter, beta, eps, (hipStream_t)stream};
+  return decode_device(q, nullptr);
 }
 
 extern "C" int qldpc_decode_device_prior(const qldpc_code* code, const qldpc_schedule* sched, int algo,
@@ -693,8 +569,9 @@ extern "C" int qldpc_decode_device_prior(const qldpc_code* code, const qldpc_sch
                                          void* d_ehat, int ehat_format, int32_t* d_iters, double* d_post,
                                          int32_t* d_flags, void* stream) {
   const PriorCall pr{p1, d_mask, mask_format};
-  return decode_device(code, sched, algo, d_syn, syn_format, batch, p0, max_iter, beta, eps, d_ehat, ehat_format,
-                       d_iters, d_post, d_flags, stream, &pr);
+  const DecodeCall q{code, sched, algo, {d_syn, syn_format, batch, d_ehat, ehat_format, d_iters, d_flags, d_post}, p0,
+                     max_iter, beta, eps, (hipStream_t)stream};
+  return decode_device(q, &pr);
 }
 
 static int twin_kernel_name(const qldpc_code* code, const qldpc_schedule* sched, int algo, PlanKind kind, char* buf,
@@ -742,42 +619,11 @@ extern "C" int qldpc_decode_launch_info(const qldpc_code* code, const qldpc_sche
   return QLDPC_OK;
 }
 
-// The code's host staging workspace (under ws_mu), grown to hold `batch`
-// half-shots; the posterior buffers only once a caller wants posteriors.
-int capi::ws_reserve(qldpc_code* code, int64_t batch, bool want_post) {
-  const int m = code->m, n = code->n;
-  if (!code->ws_stream) HIP_TRY(hipStreamCreateWithFlags(&code->ws_stream, hipStreamNonBlocking));
-  if (batch > code->ws_cap) {
-    code->ws_cap = 0;
-    code->ws_post_cap = 0;
-    const int64_t cap = std::max<int64_t>(batch, 64);
-    const size_t cm = std::max<int64_t>(1, cap * m), cn = std::max<int64_t>(1, cap * n);
-    HIP_TRY(code->ws_syn.alloc(cm));
-    HIP_TRY(code->ws_ehat.alloc(cn));
-    HIP_TRY(code->ws_iters.alloc(cap));
-    HIP_TRY(code->ws_flags.alloc(cap));
-    HIP_TRY(code->hp_syn.alloc(cm));
-    HIP_TRY(code->hp_ehat.alloc(cn));
-    HIP_TRY(code->hp_iters.alloc(cap));
-    HIP_TRY(code->hp_flags.alloc(cap));
-    code->ws_cap = cap;
-  }
-  if (want_post && code->ws_post_cap < code->ws_cap) {
-    const size_t cn = std::max<int64_t>(1, code->ws_cap * n);
-    HIP_TRY(code->ws_post.alloc(cn));
-    HIP_TRY(code->hp_post.alloc(cn));
-    code->ws_post_cap = code->ws_cap;
-  }
-  return QLDPC_OK;
-}
-
 // qldpc_decode_host, with `pr` (a host byte mask) qldpc_decode_host_prior, and
 // with `vp` qldpc_decode_host_vprior
-static int decode_host(const qldpc_code* code_c, const qldpc_schedule* sched, int algo,
-                       const uint8_t* h_syn, int64_t batch, double p, int max_iter,
-                       double beta, double eps, uint8_t* h_ehat, int32_t* h_iters,
-                       double* h_post, int32_t* h_flags, const PriorCall* pr, const qldpc_prior* vp = nullptr) {
-  auto* code = const_cast<qldpc_code*>(code_c);
+static int decode_host(const DecodeCall& q, const PriorCall* pr, const qldpc_prior* vp = nullptr) {
+  auto* code = const_cast<qldpc_code*>(q.code);
+  const int64_t batch = q.io.batch;
   if (!code) return fail(QLDPC_EINVAL, "code is null");
   if (batch < 0) return fail(QLDPC_EINVAL, "negative batch");
   // Before the staging copies: with `vp` every check decode_device makes
@@ -785,61 +631,42 @@ static int decode_host(const qldpc_code* code_c, const qldpc_schedule* sched, in
   // errors come ahead of the schedule / algo / max_iter ones, which this entry
   // and the scalar one report from decode_device, behind the copies.
   if (vp) {
-    if (int rc = validate_call(code, sched, algo, QLDPC_FMT_BYTES, QLDPC_FMT_BYTES, batch, p, max_iter, nullptr, vp))
-      return rc;
+    if (int rc = validate_call(q, nullptr, vp)) return rc;
   } else if (pr) {
-    if (!sched) return fail(QLDPC_EINVAL, "code/schedule is null");
-    if (int rc = validate_twin(code, sched, algo, batch, p, pr, nullptr)) return rc;
+    if (!q.sched) return fail(QLDPC_EINVAL, "code/schedule is null");
+    if (int rc = validate_twin(code, q.sched, q.algo, batch, q.p, pr, nullptr)) return rc;
   }
   if (batch == 0) return QLDPC_OK;
-  if (!h_syn || !h_ehat || !h_iters) return fail(QLDPC_EINVAL, "null host buffer");
+  if (!q.io.syn || !q.io.ehat || !q.io.iters) return fail(QLDPC_EINVAL, "null host buffer");
   if (code->device < 0) return fail(QLDPC_EHIP, "no HIP device was visible when the code was created");
-  std::lock_guard<std::mutex> lk(code->ws_mu);
-  const int m = code->m, n = code->n;
-  if (int rc = ws_reserve(code, batch, h_post != nullptr)) return rc;
-  hipStream_t st = code->ws_stream;
-  if (batch * m) {
-    memcpy(code->hp_syn, h_syn, batch * m);
-    HIP_TRY(hipMemcpyAsync(code->ws_syn, code->hp_syn, batch * m, hipMemcpyHostToDevice, st));
-  }
-  PriorCall dpr{};
-  if (pr) {
+  return staged_call(code, q.io, [&](const CallIO& d, hipStream_t st) {
+    DecodeCall dq = q;
+    dq.io = d, dq.st = st;
+    if (!pr) return decode_device(dq, nullptr, vp);
     // the mask goes through the workspace's mask buffers, grown with it
+    const int64_t bn = batch * code->n;
     if (code->ws_mask_cap < code->ws_cap) {
-      const size_t cn = std::max<int64_t>(1, code->ws_cap * n);
+      const size_t cn = std::max<int64_t>(1, code->ws_cap * code->n);
       HIP_TRY(code->ws_mask.alloc(cn));
       HIP_TRY(code->hp_mask.alloc(cn));
       code->ws_mask_cap = code->ws_cap;
     }
-    if (batch * n) {
-      memcpy(code->hp_mask, pr->mask, batch * n);
-      HIP_TRY(hipMemcpyAsync(code->ws_mask, code->hp_mask, batch * n, hipMemcpyHostToDevice, st));
+    if (bn) {
+      memcpy(code->hp_mask, pr->mask, bn);
+      HIP_TRY(hipMemcpyAsync(code->ws_mask, code->hp_mask, bn, hipMemcpyHostToDevice, st));
     }
-    dpr = PriorCall{pr->p1, code->ws_mask.p, QLDPC_FMT_BYTES};
-  }
-  int rc = decode_device(code, sched, algo, code->ws_syn, QLDPC_FMT_BYTES, batch, p, max_iter, beta, eps,
-                         code->ws_ehat, QLDPC_FMT_BYTES, code->ws_iters, h_post ? code->ws_post.p : nullptr,
-                         code->ws_flags, st, pr ? &dpr : nullptr, vp);
-  if (rc) return rc;
-  if (batch * n) HIP_TRY(hipMemcpyAsync(code->hp_ehat, code->ws_ehat, batch * n, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(code->hp_iters, code->ws_iters, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(code->hp_flags, code->ws_flags, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, st));
-  if (h_post && batch * n)
-    HIP_TRY(hipMemcpyAsync(code->hp_post, code->ws_post, sizeof(double) * batch * n, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));                  // this stream only
-  if (batch * n) memcpy(h_ehat, code->hp_ehat, batch * n);
-  memcpy(h_iters, code->hp_iters, sizeof(int32_t) * batch);
-  if (h_flags) memcpy(h_flags, code->hp_flags, sizeof(int32_t) * batch);
-  if (h_post && batch * n) memcpy(h_post, code->hp_post, sizeof(double) * batch * n);
-  return QLDPC_OK;
+    const PriorCall dpr{pr->p1, code->ws_mask.p, QLDPC_FMT_BYTES};
+    return decode_device(dq, &dpr, vp);
+  });
 }
 
 extern "C" int qldpc_decode_host(const qldpc_code* code, const qldpc_schedule* sched, int algo,
                                  const uint8_t* h_syn, int64_t batch, double p, int max_iter,
                                  double beta, double eps, uint8_t* h_ehat, int32_t* h_iters,
                                  double* h_post, int32_t* h_flags) {
-  return decode_host(code, sched, algo, h_syn, batch, p, max_iter, beta, eps, h_ehat, h_iters, h_post, h_flags,
-                     nullptr);
+  const DecodeCall q{code, sched, algo, host_io(h_syn, batch, h_ehat, h_iters, h_post, h_flags), p, max_iter, beta,
+                     eps, nullptr};
+  return decode_host(q, nullptr);
 }
 
 extern "C" int qldpc_decode_host_prior(const qldpc_code* code, const qldpc_schedule* sched, int algo,
@@ -847,8 +674,9 @@ extern "C" int qldpc_decode_host_prior(const qldpc_code* code, const qldpc_sched
                                        const uint8_t* h_mask, int max_iter, double beta, double eps,
                                        uint8_t* h_ehat, int32_t* h_iters, double* h_post, int32_t* h_flags) {
   const PriorCall pr{p1, h_mask, QLDPC_FMT_BYTES};
-  return decode_host(code, sched, algo, h_syn, batch, p0, max_iter, beta, eps, h_ehat, h_iters, h_post, h_flags,
-                     &pr);
+  const DecodeCall q{code, sched, algo, host_io(h_syn, batch, h_ehat, h_iters, h_post, h_flags), p0, max_iter, beta,
+                     eps, nullptr};
+  return decode_host(q, &pr);
 }
 
 // ---------------------------------------------------------------------------
@@ -902,8 +730,9 @@ extern "C" int qldpc_decode_device_vprior(const qldpc_code* code, const qldpc_sc
                                           int max_iter, double beta, void* d_ehat, int ehat_format, int32_t* d_iters,
                                           double* d_post, int32_t* d_flags, void* stream) {
   if (!prior) return fail(QLDPC_EINVAL, "prior handle is null");
-  return decode_device(code, sched, algo, d_syn, syn_format, batch, 0.0, max_iter, beta, prior->eps, d_ehat,
-                       ehat_format, d_iters, d_post, d_flags, stream, nullptr, prior);
+  const DecodeCall q{code, sched, algo, {d_syn, syn_format, batch, d_ehat, ehat_format, d_iters, d_flags, d_post},
+                     0.0, max_iter, beta, prior->eps, (hipStream_t)stream};
+  return decode_device(q, nullptr, prior);
 }
 
 extern "C" int qldpc_decode_host_vprior(const qldpc_code* code, const qldpc_schedule* sched, int algo,
@@ -911,8 +740,9 @@ extern "C" int qldpc_decode_host_vprior(const qldpc_code* code, const qldpc_sche
                                         double beta, uint8_t* h_ehat, int32_t* h_iters, double* h_post,
                                         int32_t* h_flags) {
   if (!prior) return fail(QLDPC_EINVAL, "prior handle is null");
-  return decode_host(code, sched, algo, h_syn, batch, 0.0, max_iter, beta, prior->eps, h_ehat, h_iters, h_post,
-                     h_flags, nullptr, prior);
+  const DecodeCall q{code, sched, algo, host_io(h_syn, batch, h_ehat, h_iters, h_post, h_flags), 0.0, max_iter, beta,
+                     prior->eps, nullptr};
+  return decode_host(q, nullptr, prior);
 }
 
 extern "C" int qldpc_decode_vprior_kernel_name(const qldpc_code* code, const qldpc_schedule* sched, int algo,

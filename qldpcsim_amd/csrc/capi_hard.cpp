@@ -1,10 +1,11 @@
 // capi_hard.cpp — the hard-decision decoders' entry points (NG, BF): argument
-// validation, the per-code tables and launch plan, the device launch and its
-// host-buffer twin. These decoders take no schedule, prior or posteriors.
+// validation, the per-code tables, LDS layout and launch plan, the device
+// launch and its host-buffer twin. These decoders take no schedule, prior or
+// posteriors. The plumbing shared with the other families is in capi_launch.h.
 
 #include <cstdio>
 
-#include "capi_internal.h"
+#include "capi_launch.h"
 
 using namespace capi;
 using qldpc::HardArgs;
@@ -53,10 +54,8 @@ static int validate(const qldpc_code* code, int algo, int syn_format, int ehat_f
 }
 
 static int build_plan(qldpc_code* c, int algo, HardPlan* p) {
-  int dev = 0, max_lds = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  HIP_TRY(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-  HIP_TRY(hipDeviceGetAttribute(&p->cus, hipDeviceAttributeMultiprocessorCount, dev));
+  int max_lds = 0;
+  if (int rc = device_limits(&max_lds, &p->cus)) return rc;
   if (!c->d_hard_tab) {
     // row_ell [m][8] | col_ell [n][8] | row_ptr | row_var | col_ptr | col_chk
     const int m = c->m, n = c->n, E = c->E;
@@ -78,8 +77,8 @@ static int build_plan(qldpc_code* c, int algo, HardPlan* p) {
     tab.insert(tab.end(), cp.begin(), cp.end());
     tab.insert(tab.end(), chk.begin(), chk.end());
     HIP_TRY(c->d_hard_tab.upload(tab));
-    HIP_TRY(c->d_hard_queue.alloc(qldpc_code::kHardQueueSlots));
-    HIP_TRY(hipMemset(c->d_hard_queue, 0, sizeof(uint32_t) * qldpc_code::kHardQueueSlots));
+    HIP_TRY(c->hard_queue.buf.alloc(QueueRing::kSlots));
+    HIP_TRY(hipMemset(c->hard_queue.buf, 0, sizeof(uint32_t) * QueueRing::kSlots));
   }
   if (int rc = hard_layout(c, algo, &p->args)) return rc;
   p->args.row_ell = c->d_hard_tab;
@@ -90,18 +89,15 @@ static int build_plan(qldpc_code* c, int algo, HardPlan* p) {
   p->args.col_chk = p->args.col_ptr + c->n + 1;
   p->kernel = qldpc::select_hard_kernel(algo, &p->name);
   HIP_TRY(qldpc::configure_hard_kernel(p->kernel, max_lds));
-  // waves per workgroup: the width that keeps the most waves on a CU
-  int best = 0;
-  for (int w = qldpc::kHardMaxWaves; w >= 1; --w) {
-    const int lds = w * p->args.wave_bytes;
-    if (lds > max_lds) continue;
-    int nb = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, p->kernel, 64 * w, (size_t)lds));
-    if (nb * w > best) p->waves = w, p->blocks_per_cu = nb, p->lds = lds, best = nb * w;
-  }
-  if (best == 0)
+  // waves per workgroup: the width that keeps the most waves on a CU (the
+  // tuning options waves_per_wg, wg_per_cu have no say here)
+  auto lds_of = [&](int w) { return w * p->args.wave_bytes; };
+  WaveChoice wc;
+  HIP_TRY(wave_search(1, qldpc::kHardMaxWaves, max_lds, lds_of, occupancy_of(p->kernel), false, &wc));
+  if (!wc.waves)
     return fail(QLDPC_EUNSUP, "%s: a wave's state of %d B does not fit the %d B of LDS", p->name, p->args.wave_bytes,
                 max_lds);
+  p->waves = wc.waves, p->blocks_per_cu = wc.blocks_per_cu, p->lds = wc.lds;
   return QLDPC_OK;
 }
 
@@ -109,18 +105,8 @@ static int resolve_plan(qldpc_code* c, int algo, HardPlan* out) {
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
   if (dev != c->device) return fail(QLDPC_EINVAL, "code lives on device %d, current device is %d", c->device, dev);
-  std::lock_guard<std::mutex> lk(c->hard_mu);
-  HardPlan& slot = c->hard_plan[algo - QLDPC_ALGO_NG];
-  const uint32_t gen = g_opt.gen.load();
-  if (!slot.ok || slot.gen != gen) {
-    HardPlan p{};                                     // built aside, published whole
-    if (int rc = build_plan(c, algo, &p)) return rc;
-    p.ok = true;
-    p.gen = gen;
-    slot = p;
-  }
-  *out = slot;
-  return QLDPC_OK;
+  return cached_plan(c->hard_mu, c->hard_plan[algo - QLDPC_ALGO_NG], out,
+                     [&](HardPlan* p) { return build_plan(c, algo, p); });
 }
 
 extern "C" int qldpc_hard_decode_device(const qldpc_code* code_c, int algo, const void* d_syn, int syn_format,
@@ -139,13 +125,9 @@ extern "C" int qldpc_hard_decode_device(const qldpc_code* code_c, int algo, cons
   a.batch = batch;
   a.max_iter = max_iter;
   a.queue = nullptr;
-  if (!opt(&Options::static_sched)) {
-    a.queue = code->d_hard_queue + (code->hard_qnext.fetch_add(1) % qldpc_code::kHardQueueSlots);
-    HIP_TRY(hipMemsetAsync(a.queue, 0, sizeof(uint32_t), st));
-  }
-  const int64_t need = (batch + plan.waves - 1) / plan.waves;
-  const int64_t resident = (int64_t)plan.blocks_per_cu * plan.cus;
-  const int grid = (int)std::max<int64_t>(1, std::min(need, resident));
+  if (!opt(&Options::static_sched))
+    if (int rc = code->hard_queue.claim(st, &a.queue)) return rc;
+  const int grid = launch_grid(batch, plan.waves, plan.blocks_per_cu, plan.cus);
   TimedLaunch t;
   if (int rc = timing_begin(&t, st)) return rc;
   HIP_TRY(qldpc::launch_hard(plan.kernel, a, grid, 64 * plan.waves, plan.lds, st));
@@ -159,23 +141,10 @@ extern "C" int qldpc_hard_decode_host(const qldpc_code* code_c, int algo, const 
   if (int rc = validate(code, algo, QLDPC_FMT_BYTES, QLDPC_FMT_BYTES, batch, max_iter, h_syn, h_ehat, h_iters, &done))
     return rc;
   if (done) return QLDPC_OK;
-  std::lock_guard<std::mutex> lk(code->ws_mu);
-  const int64_t m = code->m, n = code->n;
-  if (int rc = ws_reserve(code, batch, false)) return rc;
-  hipStream_t st = code->ws_stream;
-  memcpy(code->hp_syn, h_syn, batch * m);
-  HIP_TRY(hipMemcpyAsync(code->ws_syn, code->hp_syn, batch * m, hipMemcpyHostToDevice, st));
-  if (int rc = qldpc_hard_decode_device(code, algo, code->ws_syn, QLDPC_FMT_BYTES, batch, max_iter, code->ws_ehat,
-                                        QLDPC_FMT_BYTES, code->ws_iters, code->ws_flags, st))
-    return rc;
-  HIP_TRY(hipMemcpyAsync(code->hp_ehat, code->ws_ehat, batch * n, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(code->hp_iters, code->ws_iters, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(code->hp_flags, code->ws_flags, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));                  // this stream only
-  memcpy(h_ehat, code->hp_ehat, batch * n);
-  memcpy(h_iters, code->hp_iters, sizeof(int32_t) * batch);
-  if (h_flags) memcpy(h_flags, code->hp_flags, sizeof(int32_t) * batch);
-  return QLDPC_OK;
+  return staged_call(code, host_io(h_syn, batch, h_ehat, h_iters, nullptr, h_flags), [&](const CallIO& d, hipStream_t st) {
+    return qldpc_hard_decode_device(code, algo, d.syn, d.syn_format, batch, max_iter, d.ehat, d.ehat_format, d.iters,
+                                    d.flags, st);
+  });
 }
 
 extern "C" int qldpc_hard_kernel_name(const qldpc_code* code, int algo, char* buf, int len) {

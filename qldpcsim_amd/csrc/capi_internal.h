@@ -1,6 +1,8 @@
 // capi_internal.h — private to the host translation units of the C ABI
-// (capi*.cpp): errors, options, owning device buffers, and the definitions of
-// qldpc_code / qldpc_schedule. Nothing declared in namespace capi is exported.
+// (capi*.cpp): errors, options, owning device buffers, the part every launch
+// plan shares, the half-shot queue ring, and the definitions of qldpc_code /
+// qldpc_schedule. What a launch does with them is in capi_launch.h. Nothing
+// declared in namespace capi is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -116,6 +118,24 @@ struct TableImage {
   }
 };
 
+// What every family's launch plan starts with: the kernel, its geometry and the option generation (cached_plan)
+struct PlanBase {
+  const void* kernel = nullptr;
+  const char* name = "";    // as rocprofv3 reports it
+  int waves = 0, blocks_per_cu = 0, lds = 0;   // waves per workgroup, workgroups per CU, LDS bytes
+  int cus = 0;              // compute units of the device
+  uint32_t gen = 0;         // g_opt.gen the plan was built under
+  bool ok = false;
+};
+
+// Half-shot work-queue counters: concurrent launches take different slots, each zeroed on the launch stream
+struct QueueRing {
+  static constexpr int kSlots = 64;
+  DevBuf<uint32_t> buf;     // [kSlots], allocated and zeroed by the owner
+  std::atomic<uint32_t> next{0};
+  int claim(hipStream_t st, uint32_t** slot);   // capi_launch.cpp
+};
+
 // ---------------------------------------------------------------------------
 // Launch plan of (schedule, algo) under one option generation: everything a
 // decode launch needs that does not depend on the call (capi_decode.cpp)
@@ -141,32 +161,22 @@ struct KernelChoice {
   bool hbm = false;
 };
 
-struct LaunchPlan {
+struct LaunchPlan : PlanBase {   // (waves, blocks_per_cu, lds: the LDS kernels'; 0 on the HBM path)
   // hbm_tile_kernel (PLAN_VPRIOR: hbm_tile_vprior_kernel) decodes: the LDS
   // kernels cannot hold this schedule, or force_hbm
   bool hbm = false;
-  const void* kernel = nullptr;
-  const char* name = "";
-  int waves = 0, blocks_per_cu = 0, lds = 0;   // LDS kernels: waves per workgroup, workgroups per CU, LDS bytes
-  int team = 0, cus = 0;    // BP teams: waves per half-shot; compute units of the device
+  int team = 0;             // BP teams: waves per half-shot
   int hs_per_wave = 1;      // half-shots a wave decodes at a time (register-resident ms_flood_kernel: 4)
   qldpc::DecodeArgs args{};  // every static field filled (LDS kernels)
   qldpc::HbmArgs hargs{};    // the same for hbm_tile_kernel
   int hbm_tiles_cap = 0;    // CUs x resident 64-slot tiles per CU
   size_t hbm_lds = 0;       // hbm_tile_kernel / hbm_tile_vprior_kernel, BP: dynamic LDS bytes (qldpc::hbm_vprior_lds; 0 up to 128 entries per column)
-  uint32_t gen = 0;         // g_opt.gen the plan was built under
-  bool ok = false;
 };
 
 // Launch plan of (code, NG | BF) under one option generation (capi_hard.cpp):
 // the hard-decision kernels need no schedule, so the plan belongs to the code
-struct HardPlan {
-  const void* kernel = nullptr;
-  const char* name = "";
-  int waves = 0, blocks_per_cu = 0, lds = 0, cus = 0;
+struct HardPlan : PlanBase {
   qldpc::HardArgs args{};    // every static field filled
-  uint32_t gen = 0;
-  bool ok = false;
 };
 
 }  // namespace capi
@@ -205,8 +215,8 @@ struct qldpc_code {
   uint32_t filt_all = 0;
   capi::DevBuf<uint32_t> d_wc, d_rtab;  // rtab: [m][8] relabeled variables per row
   capi::DevBuf<uint32_t> d_avar;        // [n] filter word per relabeled variable (layered BP)
-  // host staging workspace for qldpc_decode_host: device buffers, page-locked
-  // host mirrors (DMA copies) and a stream of its own (no device-wide sync)
+  // host staging workspace of every *_host entry (staged_call, capi_launch.h): device buffers,
+  // page-locked host mirrors (DMA copies) and a stream of its own (no device-wide sync)
   std::mutex ws_mu;
   int64_t ws_cap = 0, ws_post_cap = 0;   // half-shots held; of those, with posterior buffers
   capi::DevBuf<uint8_t> ws_syn, ws_ehat;
@@ -224,11 +234,9 @@ struct qldpc_code {
   // col_ptr | col_chk),
   // uploaded on first use; the launch plans per algo; a half-shot queue ring
   // as qldpc_schedule's
-  static constexpr int kHardQueueSlots = 64;
   std::mutex hard_mu;
   capi::DevBuf<uint16_t> d_hard_tab;
-  capi::DevBuf<uint32_t> d_hard_queue;
-  std::atomic<uint32_t> hard_qnext{0};
+  capi::QueueRing hard_queue;
   capi::HardPlan hard_plan[2];   // [algo - QLDPC_ALGO_NG]
 };
 
@@ -271,11 +279,7 @@ struct qldpc_schedule {
   void* hbm_ws = nullptr;
   size_t hbm_ws_bytes = 0;
   hipEvent_t hbm_ev = nullptr;
-  // half-shot work-queue counters (ring: concurrent launches on different
-  // streams take different slots; each is zeroed on the launch stream)
-  static constexpr int kQueueSlots = 64;
-  capi::DevBuf<uint32_t> d_queue;
-  std::atomic<uint32_t> qnext{0};
+  capi::QueueRing queue;      // half-shot work-queue counters
 };
 
 #pragma GCC visibility push(hidden)
@@ -323,15 +327,6 @@ void plan_static_hbm(const qldpc_schedule* s, qldpc::HbmArgs* a);
 // prior L[v] is negative: the filters of a decode whose posteriors all stand at
 // their priors (hbm_tile_vprior_kernel's HbmArgs::filt0); calls no HIP function
 uint32_t prior_filter_word(const qldpc_code* c, const std::vector<double>& L);
-// The code's host staging workspace (caller holds ws_mu), grown to `batch`
-// half-shots; posterior buffers only when wanted
-int ws_reserve(qldpc_code* code, int64_t batch, bool want_post);
-// HIP events around a kernel launch when qldpc_timing_enable is on
-struct TimedLaunch {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-};
-int timing_begin(TimedLaunch* t, hipStream_t st);
-int timing_end(TimedLaunch* t, hipStream_t st);
 
 // capi_hard.cpp. Calls no HIP function: the per-wave LDS layout of the
 // hard-decision kernels (every HardArgs field that depends on the code's

@@ -1,13 +1,14 @@
 // capi_relay.cpp — relay min-sum: the qldpc_relay handle
-// (legs, memory strengths, a flooding schedule of its own), its launch plans
-// and the decode entry points, the scalar-prior ones (relay_ms_kernel) and
-// the per-variable-prior ones (relay_vprior_kernel, §3.18).
+// (legs, memory strengths, a flooding schedule of its own), its LDS layout and
+// launch plans and the decode entry points, the scalar-prior ones
+// (relay_ms_kernel) and the per-variable-prior ones (relay_vprior_kernel,
+// §3.18). The plumbing shared with the other families is in capi_launch.h.
 
 #include <cmath>
 #include <cstdio>
 #include <memory>
 
-#include "capi_internal.h"
+#include "capi_launch.h"
 #include "relay_kernels.h"
 #include "../../include/qldpc_libm.h"   // after hip_runtime.h
 
@@ -17,13 +18,8 @@ using qldpc::RelayVpriorArgs;
 
 namespace {
 
-struct RelayPlan {
-  const void* kernel = nullptr;
-  const char* name = "";
-  int waves = 0, blocks_per_cu = 0, lds = 0, cus = 0;
+struct RelayPlan : PlanBase {
   RelayArgs args{};          // every static field filled
-  uint32_t gen = 0;
-  bool ok = false;
 };
 
 }  // namespace
@@ -47,12 +43,12 @@ struct qldpc_relay {
 // device-free half: limits, kernel, static arguments (no HIP function called)
 // ---------------------------------------------------------------------------
 static int relay_limits(const qldpc_code* c) {
-  if (!c->lds_ok)
+  const LdsLimit l = lds_limit(c->lds_ok, c, QLDPC_ALGO_MS);
+  if (l == LDS_TABLES16)
     return fail(QLDPC_EUNSUP, "relay min-sum: %d x %d with %d edges is past the LDS kernel's 16-bit tables "
                 "(m, n, edges <= 65535); there is no HBM-resident variant", c->m, c->n, c->E);
-  if (c->max_row_deg > 32)
-    return fail(QLDPC_EUNSUP, "relay min-sum: row degree %d > 32 has no LDS kernel", c->max_row_deg);
-  if (opt(&Options::force_hbm) != 0)
+  if (l == LDS_MS_ROW_DEG) return fail(QLDPC_EUNSUP, "relay min-sum: row degree %d > 32 has no LDS kernel", c->max_row_deg);
+  if (l == LDS_FORCE_HBM)
     return fail(QLDPC_EUNSUP, "relay min-sum: option force_hbm is set and there is no HBM-resident variant");
   return QLDPC_OK;
 }
@@ -182,56 +178,24 @@ extern "C" int qldpc_decode_relay_vprior_kernel_name(const qldpc_code* code, con
 // launch plan, device half: occupancy; cached in the handle per option generation
 // ---------------------------------------------------------------------------
 static int build_plan(qldpc_relay* r, bool vp, RelayPlan* p) {
-  int dev = 0, max_lds = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  HIP_TRY(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-  HIP_TRY(hipDeviceGetAttribute(&p->cus, hipDeviceAttributeMultiprocessorCount, dev));
+  int max_lds = 0;
+  if (int rc = device_limits(&max_lds, &p->cus)) return rc;
   p->kernel = relay_choose(r->code, vp, &p->name);
   const int image_lds = relay_plan_static(r, vp, &p->args);
   HIP_TRY(qldpc::configure_relay_kernel(p->kernel, max_lds));
-  const int max_waves = QLDPC_MAX_THREADS / 64;
   const int wb = p->args.d.wave_bytes;
-  int best = 0;
-  auto occupancy = [&](int w, int lds, int* nb) {
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(nb, p->kernel, 64 * w, (size_t)lds);
-  };
-  for (int w = max_waves; w >= 1; --w) {
-    const int lds = image_lds + w * wb;
-    if (lds > max_lds) continue;
-    int nb = 0;
-    HIP_TRY(occupancy(w, lds, &nb));
-    if (nb * w > best) p->waves = w, p->blocks_per_cu = nb, p->lds = lds, best = nb * w;
-  }
-  if (best == 0)
+  auto lds_of = [&](int w) { return image_lds + w * wb; };
+  WaveChoice wc;
+  HIP_TRY(wave_search(1, QLDPC_MAX_THREADS / 64, max_lds, lds_of, occupancy_of(p->kernel), true, &wc));
+  if (!wc.waves)
     return fail(QLDPC_EUNSUP, "relay min-sum: the tables%s and one wave's state (%d + %d B) do not fit the %d B of "
                 "LDS; there is no HBM-resident variant", vp ? ", the prior row" : "", image_lds, wb, max_lds);
-  // Tuning overrides (experiments, tests): options waves_per_wg, wg_per_cu.
-  if (const int64_t ow = opt(&Options::waves_per_wg)) {
-    const int w = (int)ow, lds = image_lds + w * wb;
-    int nb = 0;
-    if (w >= 1 && w <= max_waves && lds <= max_lds && occupancy(w, lds, &nb) == hipSuccess && nb > 0)
-      p->waves = w, p->blocks_per_cu = nb, p->lds = lds;
-  }
-  if (const int64_t ok = opt(&Options::wg_per_cu)) {
-    const int k2 = (int)ok;
-    if (k2 >= 1 && k2 < p->blocks_per_cu) p->blocks_per_cu = k2;
-  }
+  p->waves = wc.waves, p->blocks_per_cu = wc.blocks_per_cu, p->lds = wc.lds;
   return QLDPC_OK;
 }
 
 static int resolve_plan(qldpc_relay* r, bool vp, RelayPlan* out) {
-  std::lock_guard<std::mutex> lk(r->mu);
-  const uint32_t gen = g_opt.gen.load();
-  RelayPlan& slot = r->plan[vp ? 1 : 0];
-  if (!slot.ok || slot.gen != gen) {
-    RelayPlan p{};                                    // built aside, published whole
-    if (int rc = build_plan(r, vp, &p)) return rc;
-    p.ok = true;
-    p.gen = gen;
-    slot = p;
-  }
-  *out = slot;
-  return QLDPC_OK;
+  return cached_plan(r->mu, r->plan[vp ? 1 : 0], out, [&](RelayPlan* p) { return build_plan(r, vp, p); });
 }
 
 static int relay_launch_info(const qldpc_code* code, const qldpc_relay* relay_c, bool vp, int* waves_per_wg,
@@ -267,16 +231,15 @@ struct VpriorCall {
   int cost;
 };
 
-static int validate(const qldpc_code* code, const qldpc_relay* relay, int syn_format, int ehat_format, int64_t batch,
-                    const void* syn, const void* ehat, const void* iters, bool* done, const VpriorCall* vp = nullptr,
-                    double eps = 0.0) {
+static int validate(const qldpc_code* code, const qldpc_relay* relay, const CallIO& io, bool* done,
+                    const VpriorCall* vp, double eps) {
   *done = false;
-  if ((syn_format != QLDPC_FMT_BYTES && syn_format != QLDPC_FMT_BITS) ||
-      (ehat_format != QLDPC_FMT_BYTES && ehat_format != QLDPC_FMT_BITS))
+  if ((io.syn_format != QLDPC_FMT_BYTES && io.syn_format != QLDPC_FMT_BITS) ||
+      (io.ehat_format != QLDPC_FMT_BYTES && io.ehat_format != QLDPC_FMT_BITS))
     return fail(QLDPC_EINVAL, "unknown syndrome / estimate format");
   if (!code || !relay) return fail(QLDPC_EINVAL, "code/relay is null");
   if (relay->code != code) return fail(QLDPC_EINVAL, "relay handle was built for a different code");
-  if (batch < 0) return fail(QLDPC_EINVAL, "negative batch");
+  if (io.batch < 0) return fail(QLDPC_EINVAL, "negative batch");
   if (vp) {
     const qldpc_prior* pr = vp->prior;
     if (!pr) return fail(QLDPC_EINVAL, "prior handle is null");
@@ -289,11 +252,11 @@ static int validate(const qldpc_code* code, const qldpc_relay* relay, int syn_fo
                   vp->cost);
   }
   if (int rc = relay_limits(code)) return rc;
-  if (batch == 0) {
+  if (io.batch == 0) {
     *done = true;
     return QLDPC_OK;
   }
-  if (!syn || !ehat || !iters) return fail(QLDPC_EINVAL, "null buffer");
+  if (!io.syn || !io.ehat || !io.iters) return fail(QLDPC_EINVAL, "null buffer");
   if (code->device < 0 || !relay->sched->generic.dev)
     return fail(QLDPC_EHIP, "no HIP device was visible when the code/relay handle was created");
   if (vp && (!vp->prior->d_L.p || !vp->prior->d_W.p))
@@ -302,28 +265,21 @@ static int validate(const qldpc_code* code, const qldpc_relay* relay, int syn_fo
 }
 
 // qldpc_decode_device_relay, and with `vp` qldpc_decode_device_relay_vprior (p is then unread)
-static int relay_device(const qldpc_code* code, const qldpc_relay* relay_c, const VpriorCall* vp, const void* d_syn,
-                        int syn_format, int64_t batch, double p, double beta, double eps, void* d_ehat,
-                        int ehat_format, int32_t* d_iters, double* d_post, int32_t* d_flags, int32_t* d_info,
-                        void* stream) {
+static int relay_device(const qldpc_code* code, const qldpc_relay* relay_c, const VpriorCall* vp, const CallIO& io,
+                        double p, double beta, double eps, int32_t* d_info, hipStream_t st) {
   auto* relay = const_cast<qldpc_relay*>(relay_c);
   bool done = false;
-  if (int rc = validate(code, relay, syn_format, ehat_format, batch, d_syn, d_ehat, d_iters, &done, vp, eps))
-    return rc;
+  if (int rc = validate(code, relay, io, &done, vp, eps)) return rc;
   if (done) return QLDPC_OK;
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
   if (dev != code->device) return fail(QLDPC_EINVAL, "code lives on device %d, current device is %d", code->device, dev);
   RelayPlan plan;
   if (int rc = resolve_plan(relay, vp != nullptr, &plan)) return rc;
-  hipStream_t st = (hipStream_t)stream;
   RelayArgs ra = plan.args;
   qldpc::DecodeArgs& a = ra.d;
-  a.syn = (const uint8_t*)d_syn, a.ehat = (uint8_t*)d_ehat;
-  a.syn_bits = syn_format == QLDPC_FMT_BITS, a.eh_bits = ehat_format == QLDPC_FMT_BITS;
-  a.iters = d_iters, a.post = d_post, a.flags = d_flags;
+  set_call_io(&a, io);
   ra.info = d_info;
-  a.batch = batch;
   if (vp) {
     a.vprior = vp->prior->d_L;
     a.L = 0.0, a.L32 = 0.0f;                          // (unread: every prior comes from the row)
@@ -333,15 +289,10 @@ static int relay_device(const qldpc_code* code, const qldpc_relay* relay_c, cons
   }
   a.beta = beta, a.eps = eps;
   a.max_iter = relay->leg_iters[0];                   // (unread: the legs carry the counts)
-  qldpc_schedule* s = relay->sched;
   a.queue = nullptr;
-  if (!opt(&Options::static_sched)) {
-    a.queue = s->d_queue + (s->qnext.fetch_add(1) % qldpc_schedule::kQueueSlots);
-    HIP_TRY(hipMemsetAsync(a.queue, 0, sizeof(uint32_t), st));
-  }
-  const int64_t need = (batch + plan.waves - 1) / plan.waves;
-  const int64_t resident = (int64_t)plan.blocks_per_cu * plan.cus;
-  const int grid = (int)std::max<int64_t>(1, std::min(need, resident));
+  if (!opt(&Options::static_sched))
+    if (int rc = relay->sched->queue.claim(st, &a.queue)) return rc;
+  const int grid = launch_grid(io.batch, plan.waves, plan.blocks_per_cu, plan.cus);
   TimedLaunch t;
   if (int rc = timing_begin(&t, st)) return rc;
   if (vp)
@@ -356,8 +307,8 @@ extern "C" int qldpc_decode_device_relay(const qldpc_code* code, const qldpc_rel
                                          int syn_format, int64_t batch, double p, double beta, double eps,
                                          void* d_ehat, int ehat_format, int32_t* d_iters, double* d_post,
                                          int32_t* d_flags, int32_t* d_info, void* stream) {
-  return relay_device(code, relay, nullptr, d_syn, syn_format, batch, p, beta, eps, d_ehat, ehat_format, d_iters,
-                      d_post, d_flags, d_info, stream);
+  return relay_device(code, relay, nullptr, {d_syn, syn_format, batch, d_ehat, ehat_format, d_iters, d_flags, d_post}, p,
+                      beta, eps, d_info, (hipStream_t)stream);
 }
 
 extern "C" int qldpc_decode_device_relay_vprior(const qldpc_code* code, const qldpc_relay* relay,
@@ -366,58 +317,40 @@ extern "C" int qldpc_decode_device_relay_vprior(const qldpc_code* code, const ql
                                                 int32_t* d_iters, double* d_post, int32_t* d_flags, int32_t* d_info,
                                                 void* stream) {
   const VpriorCall vp{prior, cost};
-  return relay_device(code, relay, &vp, d_syn, syn_format, batch, 0.0, beta, eps, d_ehat, ehat_format, d_iters,
-                      d_post, d_flags, d_info, stream);
+  return relay_device(code, relay, &vp, {d_syn, syn_format, batch, d_ehat, ehat_format, d_iters, d_flags, d_post}, 0.0,
+                      beta, eps, d_info, (hipStream_t)stream);
 }
 
 // qldpc_decode_host_relay, and with `vp` qldpc_decode_host_relay_vprior
-static int relay_host(const qldpc_code* code_c, const qldpc_relay* relay_c, const VpriorCall* vp, const uint8_t* h_syn,
-                      int64_t batch, double p, double beta, double eps, uint8_t* h_ehat, int32_t* h_iters,
-                      double* h_post, int32_t* h_flags, int32_t* h_info) {
+static int relay_host(const qldpc_code* code_c, const qldpc_relay* relay_c, const VpriorCall* vp, const CallIO& h,
+                      double p, double beta, double eps, int32_t* h_info) {
   auto* code = const_cast<qldpc_code*>(code_c);
   auto* relay = const_cast<qldpc_relay*>(relay_c);
   bool done = false;
-  if (int rc = validate(code, relay, QLDPC_FMT_BYTES, QLDPC_FMT_BYTES, batch, h_syn, h_ehat, h_iters, &done, vp, eps))
-    return rc;
+  if (int rc = validate(code, relay, h, &done, vp, eps)) return rc;
   if (done) return QLDPC_OK;
-  std::lock_guard<std::mutex> lk(code->ws_mu);
-  const int64_t m = code->m, n = code->n;
-  if (int rc = ws_reserve(code, batch, h_post != nullptr)) return rc;
-  hipStream_t st = code->ws_stream;
-  if (h_info) {
-    std::lock_guard<std::mutex> lr(relay->mu);
-    if (relay->ws_info_cap < batch) {
-      HIP_TRY(hipStreamSynchronize(st));
-      HIP_TRY(relay->ws_info.alloc((size_t)2 * batch));
-      relay->ws_info_cap = batch;
+  // the info rows: a device buffer of the handle, grown once the stream is done with the old one
+  auto launch = [&](const CallIO& d, hipStream_t st) {
+    if (h_info) {
+      std::lock_guard<std::mutex> lr(relay->mu);
+      if (relay->ws_info_cap < h.batch) {
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(relay->ws_info.alloc((size_t)2 * h.batch));
+        relay->ws_info_cap = h.batch;
+      }
     }
-  }
-  if (batch * m) {
-    memcpy(code->hp_syn, h_syn, batch * m);
-    HIP_TRY(hipMemcpyAsync(code->ws_syn, code->hp_syn, batch * m, hipMemcpyHostToDevice, st));
-  }
-  if (int rc = relay_device(code, relay, vp, code->ws_syn, QLDPC_FMT_BYTES, batch, p, beta, eps, code->ws_ehat,
-                            QLDPC_FMT_BYTES, code->ws_iters, h_post ? code->ws_post.p : nullptr, code->ws_flags,
-                            h_info ? relay->ws_info.p : nullptr, st))
-    return rc;
-  if (batch * n) HIP_TRY(hipMemcpyAsync(code->hp_ehat, code->ws_ehat, batch * n, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(code->hp_iters, code->ws_iters, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(code->hp_flags, code->ws_flags, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, st));
-  if (h_post && batch * n)
-    HIP_TRY(hipMemcpyAsync(code->hp_post, code->ws_post, sizeof(double) * batch * n, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));                  // this stream only
-  if (h_info) HIP_TRY(hipMemcpy(h_info, relay->ws_info, sizeof(int32_t) * 2 * batch, hipMemcpyDeviceToHost));
-  if (batch * n) memcpy(h_ehat, code->hp_ehat, batch * n);
-  memcpy(h_iters, code->hp_iters, sizeof(int32_t) * batch);
-  if (h_flags) memcpy(h_flags, code->hp_flags, sizeof(int32_t) * batch);
-  if (h_post && batch * n) memcpy(h_post, code->hp_post, sizeof(double) * batch * n);
-  return QLDPC_OK;
+    return relay_device(code, relay, vp, d, p, beta, eps, h_info ? relay->ws_info.p : nullptr, st);
+  };
+  return staged_call(code, h, launch, [&] {
+    if (h_info) HIP_TRY(hipMemcpy(h_info, relay->ws_info, sizeof(int32_t) * 2 * h.batch, hipMemcpyDeviceToHost));
+    return (int)QLDPC_OK;
+  });
 }
 
 extern "C" int qldpc_decode_host_relay(const qldpc_code* code, const qldpc_relay* relay, const uint8_t* h_syn,
                                        int64_t batch, double p, double beta, double eps, uint8_t* h_ehat,
                                        int32_t* h_iters, double* h_post, int32_t* h_flags, int32_t* h_info) {
-  return relay_host(code, relay, nullptr, h_syn, batch, p, beta, eps, h_ehat, h_iters, h_post, h_flags, h_info);
+  return relay_host(code, relay, nullptr, host_io(h_syn, batch, h_ehat, h_iters, h_post, h_flags), p, beta, eps, h_info);
 }
 
 extern "C" int qldpc_decode_host_relay_vprior(const qldpc_code* code, const qldpc_relay* relay,
@@ -425,5 +358,5 @@ extern "C" int qldpc_decode_host_relay_vprior(const qldpc_code* code, const qldp
                                               double beta, double eps, uint8_t* h_ehat, int32_t* h_iters,
                                               double* h_post, int32_t* h_flags, int32_t* h_info) {
   const VpriorCall vp{prior, cost};
-  return relay_host(code, relay, &vp, h_syn, batch, 0.0, beta, eps, h_ehat, h_iters, h_post, h_flags, h_info);
+  return relay_host(code, relay, &vp, host_io(h_syn, batch, h_ehat, h_iters, h_post, h_flags), 0.0, beta, eps, h_info);
 }

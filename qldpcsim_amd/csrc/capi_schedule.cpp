@@ -248,7 +248,7 @@ extern "C" int qldpc_schedule_create(const qldpc_code* code, int n_layers, const
     *out = s;
     return QLDPC_OK;
   }
-  hipError_t e1 = s->d_queue.alloc(qldpc_schedule::kQueueSlots);
+  hipError_t e1 = s->queue.buf.alloc(QueueRing::kSlots);
   for (TableImage* t : {&s->generic, &s->flood_ms, &s->layered_bp, &s->layered_ms})
     if (e1 == hipSuccess && !t->empty()) e1 = t->dev.upload(t->bytes);
   auto up = [&](DevBuf<int32_t>& d, const std::vector<int32_t>& h) { e1 = e1 == hipSuccess ? d.upload(h) : e1; };
