@@ -371,6 +371,64 @@ __device__ __forceinline__ void min12_tree(const double* v, double& lo, double& 
   }
 }
 
+// Leave-one-out minima of |v[0..N)|, N >= 2: loo[e] = min over e' != e of
+// |v[e']|. A recursion over halves, split as min12_tree's: going up, each
+// subtree's minimum is formed once; going down, a subtree is handed the minimum
+// of everything outside it, min(sibling's minimum, parent's outside), and a leaf's
+// outside is its loo. Abs modifiers on the leaf reads. The root forms nothing:
+// its halves' outsides are each other's minima, top0 (of |v[0..A)|) and top1 (of
+// the rest), and min(top0, top1) is the minimum of all. 3 N - 6 instructions:
+// N - 2 going up, 2 N - 4 going down (8: 4 + 2 and 4 + 8; min12_tree: 20).
+template <int N>
+constexpr int loo_split() {
+  constexpr int H = (N / 2 + 1) & ~1;     // min12_tree's even split
+  return H < N ? H : N - 1;
+}
+template <int N>
+__device__ __forceinline__ double loo_up(const double* v, double* sub) {
+  // sub: the minima of this subtree's inner nodes of two leaves or more, in
+  // pre-order (N - 1 of them, the node's own first)
+  static_assert(N >= 2, "a leaf is read where it is used");
+  constexpr int A = loo_split<N>(), B = N - A;
+  if constexpr (N == 2) {
+    return sub[0] = vmin_abs2_f64(v[0], v[1]);
+  } else if constexpr (B == 1) {
+    return sub[0] = vmin_abs_f64(v[A], loo_up<A>(v, sub + 1));
+  } else {
+    const double a = loo_up<A>(v, sub + 1);
+    return sub[0] = vmin_f64(a, loo_up<B>(v + A, sub + A));
+  }
+}
+// min(minimum of the K values at v, whose inner nodes' minima are at sub; out)
+template <int K>
+__device__ __forceinline__ double loo_with(const double* v, const double* sub, double out) {
+  if constexpr (K == 1) return vmin_abs_f64(v[0], out);
+  else return vmin_f64(sub[0], out);
+}
+template <int N>
+__device__ __forceinline__ void loo_down(const double* v, const double* sub, double out, double* loo) {
+  constexpr int A = loo_split<N>(), B = N - A;
+  if constexpr (N == 1) {
+    loo[0] = out;
+  } else {
+    // (sub[0] is this node's own minimum; the halves' nodes follow it)
+    loo_down<A>(v, sub + 1, loo_with<B>(v + A, sub + A, out), loo);
+    loo_down<B>(v + A, sub + A, loo_with<A>(v, sub + 1, out), loo + A);
+  }
+}
+template <int N>
+__device__ __forceinline__ void loo_min_tree(const double* v, double* loo, double& top0, double& top1) {
+  static_assert(N >= 2, "a single value has no others");
+  constexpr int A = loo_split<N>(), B = N - A;
+  double sub[N];                          // (slot 0 unused: the root's minimum is not formed)
+  if constexpr (A == 1) top0 = __builtin_fabs(v[0]);
+  else top0 = loo_up<A>(v, sub + 1);
+  if constexpr (B == 1) top1 = __builtin_fabs(v[A]);
+  else top1 = loo_up<B>(v + A, sub + A);
+  loo_down<A>(v, sub + 1, top1, loo);
+  loo_down<B>(v + A, sub + A, top0, loo + A);
+}
+
 // Unsigned minimum / median of three (non-negative float32 bit patterns order
 // as unsigned integers; no canonicalisation, no denormal mode)
 __device__ __forceinline__ uint32_t umin3(uint32_t x, uint32_t y, uint32_t z) {

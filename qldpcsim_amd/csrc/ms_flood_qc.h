@@ -139,7 +139,7 @@ struct RowQueue {
 // Where check block B's minimum and select are taken (-DQLDPC_QC_CN32=n for
 // A/B; DESIGN.md §3.1.1 for the measured choice):
 //   0  on the float64 |v|: min12_tree, fl32(beta * min) twice, a float64
-//      compare and select per edge (qc_min_select_f64)
+//      compare and select per edge (qc_min_select_f64), or QLDPC_QC_LOO's form
 //   1  on w_e = bits(fl32(beta * |v_e|)) as unsigned integers: min12_tree_u32,
 //      then per edge med3(w_e, w1, w2) ^ (w1 ^ w2), the other one of the two
 // Rounding to float32 and multiplying by beta > 0 are monotone, so the smallest
@@ -213,6 +213,53 @@ __device__ __forceinline__ void qc_min_select_f64(const DecodeArgs& a, const dou
   });
 }
 
+// What a check block's float64 check node computes (-DQLDPC_QC_LOO=n for A/B,
+// read with QLDPC_QC_CN32 == 0; DESIGN.md §3.1.1 for the measured choice):
+//   0  min1 and min2, fl32(beta * min) of both and per edge a float64 compare
+//      and select between them (qc_min_select_f64)
+//   1  per edge the minimum over the other edges, loo_e (loo_min_tree), and
+//      fl32(beta * loo_e) (qc_loo_f64)
+// loo_e is min2 for the argmin and for every edge tied at min1 (then min2 ==
+// min1, the reference's "first min / min of the rest") and min1 for the others,
+// so fl32(beta * loo_e) has the bits of the select wherever the substitutions of
+// decoders.py:165-166 do not apply (min1 != 0, min2 finite). They are tested on
+// the tree's two top minima t0, t1: min1 == 0 exactly when one of them is 0, and
+// an infinite min2 makes one of them infinite (not the other way round: a wave
+// with an infinite t takes the unchanged select form as a whole, which is exact).
+// The message's sign npm ^ sign(v_e): npm goes into beta's sign once per check,
+// round-to-nearest is symmetric, so fl32((-beta) * x) is fl32(beta * x) with the
+// sign bit set, underflow to -0 and overflow to -inf included.
+// (A NaN v_e, inf - inf, exists only after a message overflowed float32, outside
+// the contract of DESIGN.md §4; v_min_f64 skips it in both forms, but the
+// select's v_e == min1 is false for it and the two forms may then differ.)
+#ifndef QLDPC_QC_LOO
+#define QLDPC_QC_LOO 1
+#endif
+
+__device__ __forceinline__ bool zero_or_inf(double x) {   // v_cmp_class_f64: +-0, +-inf
+  return __builtin_amdgcn_class(x, 0x264);
+}
+
+// The check node of qc_min_select_f64 through the leave-one-out minima
+template <int DC>
+__device__ __forceinline__ void qc_loo_f64(const DecodeArgs& a, const double (&v)[DC], const uint32_t (&hv)[DC],
+                                           uint32_t npm, float (&cv)[DC], int& fl) {
+  double loo[DC], t0, t1;
+  loo_min_tree<DC>(v, loo, t0, t1);
+  if (__builtin_expect(ballot_b(zero_or_inf(t0) | zero_or_inf(t1)) != 0, 0)) {
+    qc_min_select_f64<DC>(a, v, hv, npm, cv, fl);
+    return;
+  }
+  // beta with the sign npm (opaque: otherwise the word is formed again per edge)
+  const uint64_t bu = __builtin_bit_cast(uint64_t, a.beta);
+  const uint32_t bh = opaque_always((uint32_t)(bu >> 32) ^ npm);
+  const double bs = __builtin_bit_cast(double, ((uint64_t)bh << 32) | (uint32_t)bu);
+  static_for<DC>([&](auto E) __attribute__((always_inline)) {
+    constexpr int e = E;
+    cv[e] = __builtin_bit_cast(float, and_xor(hv[e], 0x80000000u, __builtin_bit_cast(uint32_t, (float)(bs * loo[e]))));
+  });
+}
+
 // posterior of the variable behind edge E of check block B, rotated to the
 // check's lane
 template <typename T, int B, int E>
@@ -280,6 +327,8 @@ __device__ __forceinline__ uint32_t qc_check(const DecodeArgs& a, double L, floa
       c2v[B][E] = __builtin_bit_cast(float, umed3(w[E], w1, w2) ^ and_xor(hv[E], 0x80000000u, w12n));
     });
   }
+#elif QLDPC_QC_LOO
+  qc_loo_f64<DC>(a, v, hv, npm, c2v[B], fl);
 #else
   qc_min_select_f64<DC>(a, v, hv, npm, c2v[B], fl);
 #endif

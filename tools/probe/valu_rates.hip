@@ -43,7 +43,7 @@ enum Op {
   ADD_F32, MIN_F32, MAX_F32, MIN3_F32, MED3_F32, AND_B32, MIN_U32, MAX_U32, MIN3_U32, MED3_U32, BITOP3_B32, CNDMASK_VCC, MOV_B32, MOV_ROW_ROR, VALU_THEN_DPP,
   VALU_NOP_PAIR,
   OR_B32_ROW_ROR, AND_B32_ROW_ROR, ADD_F32_ROW_ROR, MOV_B64, LSHLREV_B32, LSHRREV_B32, CNDMASK_ALONE, CMP_EQ_F64_VCC,
-  CMP_EQ_F64_SGPR, BFI_B32, XOR_B32, NUM_OPS
+  CMP_EQ_F64_SGPR, BFI_B32, XOR_B32, CMP_CLASS_F64_VCC, CMP_CLASS_F64_SGPR, MUL_F64_CVT_F32_BITOP3, NUM_OPS
 };
 struct OpInfo { const char* name; int inst_per_step; };   // instructions per chain step
 static const OpInfo kOps[NUM_OPS] = {
@@ -63,6 +63,8 @@ static const OpInfo kOps[NUM_OPS] = {
     {"v_cndmask_b32 alone (mask in an SGPR pair set before the loop)", 1},
     {"v_cmp_eq_f64 alone, into vcc", 1}, {"v_cmp_eq_f64 alone, into an SGPR pair", 1},
     {"v_bfi_b32", 1}, {"v_xor_b32", 1},
+    {"v_cmp_class_f64 alone, into vcc", 1}, {"v_cmp_class_f64 alone, into an SGPR pair", 1},
+    {"v_mul_f64 + v_cvt_f32_f64 + v_bitop3_b32 (dependent triple)", 3},
 };
 
 constexpr int kChains = 8, kUnroll = 32;  // 256 steps per loop trip
@@ -89,6 +91,8 @@ __global__ void __launch_bounds__(256) rate_kernel(uint64_t* cyc, uint32_t* done
   asm volatile("" : "+v"(one));
   uint32_t zero = 0, ones = 0xffffffffu;
   asm volatile("" : "+v"(zero), "+v"(ones));
+  uint32_t cls = 0x264;                                       // v_cmp_class's mask: +-0, +-inf
+  asm volatile("" : "+v"(cls));
   uint64_t sel = 0x5555aaaa3333ccccull, cm[kChains] = {};   // cndmask's mask; the compares' SGPR results
   asm volatile("" : "+s"(sel));
   const uint64_t t0 = __builtin_readcyclecounter();
@@ -159,6 +163,13 @@ __global__ void __launch_bounds__(256) rate_kernel(uint64_t* cyc, uint32_t* done
         if constexpr (OP == BFI_B32)
           asm volatile("v_bfi_b32 %0, %1, %2, %0" : "+v"(u[i]) : "v"(w[i]), "v"(w[(i + 1) % kChains]));
         if constexpr (OP == XOR_B32) asm volatile("v_xor_b32 %0, %0, %1" : "+v"(u[i]) : "v"(w[i]));
+        if constexpr (OP == CMP_CLASS_F64_VCC) asm volatile("v_cmp_class_f64 vcc, %0, %1" : : "v"(d[i]), "v"(cls) : "vcc");
+        if constexpr (OP == CMP_CLASS_F64_SGPR) asm volatile("v_cmp_class_f64 %0, %1, %2" : "=s"(cm[i]) : "v"(d[i]), "v"(cls));
+        if constexpr (OP == MUL_F64_CVT_F32_BITOP3) {   // the leave-one-out check node's per-edge part
+          asm volatile("v_mul_f64 %0, %1, %2" : "=v"(e[i]) : "v"(d[i]), "v"(one));
+          asm volatile("v_cvt_f32_f64 %0, %1" : "=v"(f[i]) : "v"(e[i]));
+          asm volatile("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x6c" : "=v"(u[i]) : "v"(w[i]), "v"(f[i]), "s"(0x80000000u));
+        }
       }
     }
   }
