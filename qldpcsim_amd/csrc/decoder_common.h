@@ -479,6 +479,59 @@ __device__ __forceinline__ void min12_tree_u32(const uint32_t* w, uint32_t& lo, 
   }
 }
 
+// Leave-one-out minima of w[0..N) as unsigned integers, N >= 2: loo[e] = min
+// over e' != e of w[e']. Up to four values each take the minimum of the other
+// three (or two; of two, the other one). More are cut into N / 3 groups of
+// three and N % 3 single values: a group's minimum is one min3, the groups'
+// minima and the single values are the items of the same problem one level up,
+// whose result is each item's outside (the minimum of everything not in it);
+// a single value's outside is its loo, and a group's member takes min3(the
+// other two, the group's outside). N = 8 as 3 + 3 + 1 + 1:
+//   mA = min3(w0, w1, w2)      mB = min3(w3, w4, w5)
+//   oA = min3(mB, w6, w7)      oB = min3(mA, w6, w7)
+//   loo6 = min3(mA, mB, w7)    loo7 = min3(mA, mB, w6)
+//   loo0 = min3(w1, w2, oA) ... loo5 = min3(w3, w4, oB)
+// 12 instructions (loo_min_tree on float64: 18). top0 and top1 are the first two
+// items of the top level (mA and mB; w[0] and w[1] for N <= 4) and out0 the
+// first one's outside (oA; loo[0]): min(top0, out0) is the minimum of all, and
+// where at most one value is below some bound, top0 or top1 is not.
+constexpr int loo_min_tree_u32_ops(int n) {               // (tests/test_loo32_identity.py reads this line)
+  return n <= 2 ? 0 : n <= 4 ? n : 4 * (n / 3) + loo_min_tree_u32_ops(n / 3 + n % 3);
+}
+__device__ __forceinline__ uint32_t umin2(uint32_t x, uint32_t y) { return x < y ? x : y; }
+template <int N>
+__device__ __forceinline__ void loo_min_tree_u32(const uint32_t* w, uint32_t* loo, uint32_t& top0, uint32_t& top1,
+                                                 uint32_t& out0) {
+  static_assert(N >= 2, "a single value has no others");
+  if constexpr (N == 2) {
+    loo[0] = w[1], loo[1] = w[0];
+  } else if constexpr (N == 3) {
+    loo[0] = umin2(w[1], w[2]), loo[1] = umin2(w[0], w[2]), loo[2] = umin2(w[0], w[1]);
+  } else if constexpr (N == 4) {
+    loo[0] = umin3(w[1], w[2], w[3]), loo[1] = umin3(w[0], w[2], w[3]);
+    loo[2] = umin3(w[0], w[1], w[3]), loo[3] = umin3(w[0], w[1], w[2]);
+  } else {
+    constexpr int G = N / 3, R = N % 3, K = G + R;
+    uint32_t t[K], o[K], t0, t1, o0;
+#pragma unroll
+    for (int g = 0; g < G; ++g) t[g] = umin3(w[3 * g], w[3 * g + 1], w[3 * g + 2]);
+#pragma unroll
+    for (int r = 0; r < R; ++r) t[G + r] = w[3 * G + r];
+    loo_min_tree_u32<K>(t, o, t0, t1, o0);
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      loo[3 * g] = umin3(w[3 * g + 1], w[3 * g + 2], o[g]);
+      loo[3 * g + 1] = umin3(w[3 * g], w[3 * g + 2], o[g]);
+      loo[3 * g + 2] = umin3(w[3 * g], w[3 * g + 1], o[g]);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) loo[3 * G + r] = o[G + r];
+    top0 = t[0], top1 = t[1], out0 = o[0];
+    return;
+  }
+  top0 = w[0], top1 = w[1], out0 = loo[0];
+}
+
 // XOR of N words as a balanced tree (v_xor3_b32-friendly)
 __device__ __forceinline__ uint32_t xor3(uint32_t x, uint32_t y, uint32_t z) {
   uint32_t r;

@@ -219,6 +219,8 @@ __device__ __forceinline__ void qc_min_select_f64(const DecodeArgs& a, const dou
 //      and select between them (qc_min_select_f64)
 //   1  per edge the minimum over the other edges, loo_e (loo_min_tree), and
 //      fl32(beta * loo_e) (qc_loo_f64)
+//   2  per edge w_e = bits(fl32(beta * |v_e|)) first, then the leave-one-out
+//      minima of the words as unsigned integers (loo_min_tree_u32, qc_loo_u32)
 // loo_e is min2 for the argmin and for every edge tied at min1 (then min2 ==
 // min1, the reference's "first min / min of the rest") and min1 for the others,
 // so fl32(beta * loo_e) has the bits of the select wherever the substitutions of
@@ -233,7 +235,7 @@ __device__ __forceinline__ void qc_min_select_f64(const DecodeArgs& a, const dou
 // the contract of DESIGN.md §4; v_min_f64 skips it in both forms, but the
 // select's v_e == min1 is false for it and the two forms may then differ.)
 #ifndef QLDPC_QC_LOO
-#define QLDPC_QC_LOO 1
+#define QLDPC_QC_LOO 2
 #endif
 
 __device__ __forceinline__ bool zero_or_inf(double x) {   // v_cmp_class_f64: +-0, +-inf
@@ -257,6 +259,59 @@ __device__ __forceinline__ void qc_loo_f64(const DecodeArgs& a, const double (&v
   static_for<DC>([&](auto E) __attribute__((always_inline)) {
     constexpr int e = E;
     cv[e] = __builtin_bit_cast(float, and_xor(hv[e], 0x80000000u, __builtin_bit_cast(uint32_t, (float)(bs * loo[e]))));
+  });
+}
+
+// Whether qc_loo_u32's sign tree takes the syndrome word as a ninth input
+// (-DQLDPC_QC_SYNFOLD=n for A/B, read with QLDPC_QC_LOO == 2 and QLDPC_QC_S31;
+// DESIGN.md §3.1.1 for the measured choice):
+//   0  npm = (xor of the eight high words ^ s31) & 0x80000000, beta's high word ^ npm
+//   1  sn = xor of the eight high words and s31 (four xor3), beta's signed high
+//      word as one and_xor(sn, 0x80000000, beta's high word); npm itself is
+//      formed only where the fallback reads it
+#ifndef QLDPC_QC_SYNFOLD
+#define QLDPC_QC_SYNFOLD 0
+#endif
+
+__device__ __forceinline__ bool zero_or_inf(float x) {    // v_cmp_class_f32: +-0, +-inf
+  return __builtin_amdgcn_classf(x, 0x264);
+}
+
+// The leave-one-out check node on w_e = bits(fl32(bs * |v_e|)), bs = beta with
+// the sign npm: the roundings go in front of the tree, which then runs on 32-bit
+// words (loo_min_tree_u32). x -> fl32(bs * x) is monotone in magnitude on x >= 0
+// and all words of a lane carry npm's sign bit (on +-0 and +-inf too), so the
+// unsigned order of the words is the order of the |v_e| for either sign and the
+// minimum over e' != e of w_e' is bits(fl32(bs * loo_e)), the word qc_loo_f64
+// forms. The rare test is a float32 class test on the tree's mA, mB and oA
+// (top0, top1, out0): min1 == 0 makes min(mA, oA), the minimum of all, zero; an
+// infinite min2 leaves at most one finite value, so mA or mB is infinite. A
+// product that underflows to zero or overflows float32 there fires it as well.
+// A wave that it fires on takes the unchanged select form on the v[] still held.
+// (SN, QLDPC_QC_SYNFOLD: npm is given as a word whose bit 31 is npm's, the bits
+// below it not used)
+template <int DC, bool SN = false>
+__device__ __forceinline__ void qc_loo_u32(const DecodeArgs& a, const double (&v)[DC], const uint32_t (&hv)[DC],
+                                           uint32_t npm, float (&cv)[DC], int& fl) {
+  // beta with the sign npm (opaque: otherwise the word is formed again per edge)
+  const uint64_t bu = __builtin_bit_cast(uint64_t, a.beta);
+  const uint32_t bh = opaque_always(SN ? and_xor(npm, 0x80000000u, (uint32_t)(bu >> 32)) : (uint32_t)(bu >> 32) ^ npm);
+  const double bs = __builtin_bit_cast(double, ((uint64_t)bh << 32) | (uint32_t)bu);
+  uint32_t w[DC], loo[DC], mA, mB, oA;
+  static_for<DC>([&](auto E) __attribute__((always_inline)) {
+    constexpr int e = E;
+    w[e] = __builtin_bit_cast(uint32_t, (float)(bs * __builtin_fabs(v[e])));
+  });
+  loo_min_tree_u32<DC>(w, loo, mA, mB, oA);
+  const bool rare = zero_or_inf(__builtin_bit_cast(float, mA)) | zero_or_inf(__builtin_bit_cast(float, mB)) |
+                    zero_or_inf(__builtin_bit_cast(float, oA));
+  if (__builtin_expect(ballot_b(rare) != 0, 0)) {
+    qc_min_select_f64<DC>(a, v, hv, SN ? npm & 0x80000000u : npm, cv, fl);
+    return;
+  }
+  static_for<DC>([&](auto E) __attribute__((always_inline)) {
+    constexpr int e = E;
+    cv[e] = __builtin_bit_cast(float, and_xor(hv[e], 0x80000000u, loo[e]));
   });
 }
 
@@ -301,10 +356,16 @@ __device__ __forceinline__ uint32_t qc_check(const DecodeArgs& a, double L, floa
     hp[E] = hi_word(post);
   });
   const uint32_t ph = xor_tree<DC>(hp);                   // hard-decision parity (:174)
+#if QLDPC_QC_S31 && QLDPC_QC_SYNFOLD && QLDPC_QC_LOO == 2 && !QLDPC_QC_CN32
+  uint32_t hs[DC + 1];
+  static_for<DC>([&](auto E) __attribute__((always_inline)) { hs[E] = hv[E]; });
+  hs[DC] = synb;
+  const uint32_t npm = xor_tree<DC + 1>(hs);              // bit 31: np.sign product ^ syndrome bit
+#elif QLDPC_QC_S31
   const uint32_t sh = xor_tree<DC>(hv);                   // np.sign product (:157-159)
-#if QLDPC_QC_S31
   const uint32_t npm = (sh ^ synb) & 0x80000000u;
 #else
+  const uint32_t sh = xor_tree<DC>(hv);                   // np.sign product (:157-159)
   const uint32_t npm = ((sh >> 31) ^ synb) << 31;
 #endif
 #if QLDPC_QC_CN32
@@ -327,6 +388,8 @@ __device__ __forceinline__ uint32_t qc_check(const DecodeArgs& a, double L, floa
       c2v[B][E] = __builtin_bit_cast(float, umed3(w[E], w1, w2) ^ and_xor(hv[E], 0x80000000u, w12n));
     });
   }
+#elif QLDPC_QC_LOO == 2
+  qc_loo_u32<DC, QLDPC_QC_S31 && QLDPC_QC_SYNFOLD>(a, v, hv, npm, c2v[B], fl);
 #elif QLDPC_QC_LOO
   qc_loo_f64<DC>(a, v, hv, npm, c2v[B], fl);
 #else

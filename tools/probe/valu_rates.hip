@@ -43,7 +43,8 @@ enum Op {
   ADD_F32, MIN_F32, MAX_F32, MIN3_F32, MED3_F32, AND_B32, MIN_U32, MAX_U32, MIN3_U32, MED3_U32, BITOP3_B32, CNDMASK_VCC, MOV_B32, MOV_ROW_ROR, VALU_THEN_DPP,
   VALU_NOP_PAIR,
   OR_B32_ROW_ROR, AND_B32_ROW_ROR, ADD_F32_ROW_ROR, MOV_B64, LSHLREV_B32, LSHRREV_B32, CNDMASK_ALONE, CMP_EQ_F64_VCC,
-  CMP_EQ_F64_SGPR, BFI_B32, XOR_B32, CMP_CLASS_F64_VCC, CMP_CLASS_F64_SGPR, MUL_F64_CVT_F32_BITOP3, NUM_OPS
+  CMP_EQ_F64_SGPR, BFI_B32, XOR_B32, CMP_CLASS_F64_VCC, CMP_CLASS_F64_SGPR, MUL_F64_CVT_F32_BITOP3,
+  CMP_CLASS_F32_VCC, CMP_CLASS_F32_SGPR, CVT_F32_F64_MIN3_U32, MUL_ABS_F64_CVT_F32_INDEP, NUM_OPS
 };
 struct OpInfo { const char* name; int inst_per_step; };   // instructions per chain step
 static const OpInfo kOps[NUM_OPS] = {
@@ -65,6 +66,9 @@ static const OpInfo kOps[NUM_OPS] = {
     {"v_bfi_b32", 1}, {"v_xor_b32", 1},
     {"v_cmp_class_f64 alone, into vcc", 1}, {"v_cmp_class_f64 alone, into an SGPR pair", 1},
     {"v_mul_f64 + v_cvt_f32_f64 + v_bitop3_b32 (dependent triple)", 3},
+    {"v_cmp_class_f32 alone, into vcc", 1}, {"v_cmp_class_f32 alone, into an SGPR pair", 1},
+    {"v_cvt_f32_f64 + v_min3_u32 of its result (dependent pair)", 2},
+    {"8 x v_mul_f64 |x|, then 8 x v_cvt_f32_f64 of them (independent pairs)", 2},
 };
 
 constexpr int kChains = 8, kUnroll = 32;  // 256 steps per loop trip
@@ -169,6 +173,20 @@ __global__ void __launch_bounds__(256) rate_kernel(uint64_t* cyc, uint32_t* done
           asm volatile("v_mul_f64 %0, %1, %2" : "=v"(e[i]) : "v"(d[i]), "v"(one));
           asm volatile("v_cvt_f32_f64 %0, %1" : "=v"(f[i]) : "v"(e[i]));
           asm volatile("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x6c" : "=v"(u[i]) : "v"(w[i]), "v"(f[i]), "s"(0x80000000u));
+        }
+        if constexpr (OP == CMP_CLASS_F32_VCC) asm volatile("v_cmp_class_f32 vcc, %0, %1" : : "v"(f[i]), "v"(cls) : "vcc");
+        if constexpr (OP == CMP_CLASS_F32_SGPR) asm volatile("v_cmp_class_f32 %0, %1, %2" : "=s"(cm[i]) : "v"(f[i]), "v"(cls));
+        if constexpr (OP == CVT_F32_F64_MIN3_U32) {     // the 32-bit leave-one-out tree's first level
+          asm volatile("v_cvt_f32_f64 %0, %1" : "=v"(f[i]) : "v"(d[i]));
+          asm volatile("v_min3_u32 %0, %0, %1, %2" : "+v"(u[i]) : "v"(f[i]), "v"(w[i]));
+        }
+        if constexpr (OP == MUL_ABS_F64_CVT_F32_INDEP) {   // its roundings: every conversion eight instructions behind its product
+          if (i == 0) {
+#pragma unroll
+            for (int j = 0; j < kChains; ++j) asm volatile("v_mul_f64 %0, |%1|, %2" : "=v"(e[j]) : "v"(d[j]), "v"(one));
+#pragma unroll
+            for (int j = 0; j < kChains; ++j) asm volatile("v_cvt_f32_f64 %0, %1" : "=v"(f[j]) : "v"(e[j]));
+          }
         }
       }
     }
